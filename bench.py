@@ -15,6 +15,12 @@ every kernel of a batch and `roofline.end_to_end` the whole step, each against 8
 
 cpu_baseline: the oracle (C restatement of the Go plugins, oracle/) scheduling a prefix of the same
 queue on the host's cores at 1 thread, 16 threads (upstream Parallelism) and every usable core.
+
+A plain run sets up, warms up, times the steps and prints the result line (the figures of the timed steps
+themselves: rate, latencies, kernel times, roofline).  What takes work of its own after the timed region runs
+only with --full: `parity` (the oracle's full-queue fixture), `stream_roofline` (the B=1 streaming sweep) and
+`cpu_baseline` / `speedup_vs_cpu`.  --dump-outputs DIR writes what the last timed step returned to its caller
+(chosen.npy, score.npy) for output-by-output comparison of two builds.
 """
 import argparse
 import json
@@ -50,16 +56,27 @@ def parse():
     ap.add_argument("--nodes", type=int, default=None)
     ap.add_argument("--pods", type=int, default=None)
     ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="host time of each CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beyond the headline figure: parity with the oracle "
+                         "fixture, the B=1 streaming sweep (--stream-nodes) and the CPU baseline (--no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned (chosen, score) as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="host time of each CPU baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-pipeline", action="store_true", help="one-stream schedule (A/B of the pipelined one)")
     ap.add_argument("--pipeline-fixup", action="store_true",
                     help="pipelined with exact lists from k_fixup (ke_set_pipeline 2, the round-3 schedule)")
     ap.add_argument("--profile-every", type=int, default=8, help="HIP-event-sample every n-th batch (0 = off)")
     ap.add_argument("--sync", action="store_true", help="one ke_schedule call per step (no submit-ahead)")
     ap.add_argument("--stream-nodes", type=int, default=4_000_000,
-                    help="B=1 streaming sweep size (N*row > 512 MB, past the 256 MB Infinity Cache); 0 = skip")
-    return ap.parse_args()
+                    help="with --full: B=1 streaming sweep size (N*row > 512 MB, past the 256 MB Infinity Cache); "
+                         "0 = skip")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
 
 
 def sizes():
@@ -253,6 +270,14 @@ def stream_sweep(n_nodes, cfg_batch):
             "achieved": by / ms / 1e6, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": by / ms / 1e6 / HBM_PEAK_GBS}
 
 
+def dump_outputs(d, chosen, score):
+    """What the last timed step's ke_schedule_wait / ke_schedule handed its caller: the chosen node and its score
+    per pod of the slice (int32, exact in float64)."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "chosen.npy"), np.asarray(chosen, np.float64))
+    np.save(os.path.join(d, "score.npy"), np.asarray(score, np.float64))
+
+
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -283,6 +308,8 @@ def main():
     cfg = synth.config(N, pod_batch=a.batch)
     cfg.device_ordinal = local_rank
     slice_len = P // K
+    if slice_len < 1:
+        raise SystemExit(f"--steps {K} leaves no pod per step of a {P}-pod queue")
 
     # warmup on a throwaway context (same cluster, different pods) so the timed job starts pristine
     if W > 0:
@@ -389,10 +416,13 @@ def main():
                              a.pipeline_fixup and not a.no_pipeline),
     }
     ev.close()
-    out["parity"] = c3_parity(np.concatenate(got_c), np.concatenate(got_s), N, K * slice_len, a.config)
-    if world == 1 and a.stream_nodes > 0:
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, got_c[-1], got_s[-1])
+    if a.full:
+        out["parity"] = c3_parity(np.concatenate(got_c), np.concatenate(got_s), N, K * slice_len, a.config)
+    if a.full and world == 1 and a.stream_nodes > 0:
         out["stream_roofline"] = stream_sweep(a.stream_nodes, a.batch)
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cl, pods, cfg, a.cpu_seconds)
         out["speedup_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
     if rank == 0:

@@ -12,8 +12,10 @@ if [[ $STEPS == *tests* ]]; then
     > gpurun_out/gpu_tests_$TAG.log 2>&1 && tail -2 gpurun_out/gpu_tests_$TAG.log || { tail -40 gpurun_out/gpu_tests_$TAG.log; exit 1; }
 fi
 if [[ $STEPS == *bench* ]]; then
-  timeout -k 10 400 python -u bench.py ${BENCH_ARGS:-} > gpurun_out/bench_$TAG.log 2>&1 || { tail -30 gpurun_out/bench_$TAG.log; exit 1; }
-  tail -1 gpurun_out/bench_$TAG.log
+  B=${OUT_DIR:-bench_out}/bench_$TAG.log
+  mkdir -p "$(dirname "$B")"
+  timeout -k 10 400 python -u bench.py --full ${BENCH_ARGS:-} > "$B" 2>&1 || { tail -30 "$B"; exit 1; }
+  tail -1 "$B"
 fi
 cd /tmp && export TMPDIR=/tmp
 if [[ $STEPS == *prof* ]]; then
