@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define KE_ABI_VERSION 13
+#define KE_ABI_VERSION 14
 #define KE_ABSENT (-1)
 
 typedef struct ke_ctx ke_ctx; /* one evaluator context (ke_create) */
@@ -885,6 +885,39 @@ int ke_reservations_get(ke_ctx* ctx, int32_t n, ke_reservation* out);
  * topology policy; ke_eval of such a pod.  (Node-sharded contexts pick over every rank's pairs.)  The lists
  * are consumed by the next ke_schedule call, a refused one included. */
 int ke_pod_reservations(ke_ctx* ctx, int32_t n_pods, const int32_t* offsets, const int32_t* ids);
+/* ---- per-pod node eligibility sets (ABI v14) ---------------------------------------------------
+ * A koord-scheduler profile removes nodes before the koordinator plugins see them: NodeName, NodeUnschedulable,
+ * NodeAffinity / nodeSelector, TaintToleration, the PreFilter's NodeNames.  The caller runs those in-tree Filter
+ * plugins once per distinct pod signature into a node bitmap, loads the bitmaps as a table of
+ * sets and gives every pod of a call its set id; a node outside the pod's set is treated as if an earlier plugin's
+ * Filter had failed there.  Node indices are the global ones (those of chosen[]).
+ *  - ke_eval: an ineligible (pod, node) pair reports KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE with
+ *    KE_REASON_NODE_SET ahead of every other filter, plugin scores 0 and total -1; best[] and DeviceShare's
+ *    NormalizeScore maximum are taken over the eligible nodes only (a filtered node never reaches Score).
+ *  - ke_schedule / ke_schedule_submit: the pod is placed as if every node outside its set failed Filter;
+ *    selection, Reserve and sequential visibility are otherwise unchanged, bit-exact with one pod at a time for
+ *    every pod_batch, pipelined or not, submitted ahead or not.  A pod without a feasible node in its set gets -1.
+ *    A call carrying a non-zero id must be a plain queue: no reservation-matched / ignored / affinity pod, no
+ *    NUMA-policy, quota, DeviceShare or cpuset pod, no NUMA or CPU-bind state, no staged ke_pod_reservations
+ *    lists, not node-sharded -- anything else is KE_ERR_UNSUPPORTED before any state changes (the message names
+ *    the condition).  Pods with ke_pod.xres requests are plain.
+ * Without a table, or with every id 0, every call behaves as before. */
+#define KE_MAX_NODE_SETS 4096
+#define KE_REASON_NODE_SET 96 /* "node(s) didn't match the pod's node set" (the caller's in-tree Filter plugins) */
+/* Replace the whole table.  Set s (1..n_sets) is words_per_set uint64 words at bits + (s-1)*words_per_set; bit
+ * (i & 63) of word (i >> 6) = node index i is eligible.  Nodes at or beyond 64*words_per_set are ineligible.
+ * n_sets = 0 drops the table (bits may be NULL).  Completes calls in flight first.  ke_node_delete and a later
+ * upsert leave a node's bits alone. */
+int ke_node_sets_load(ke_ctx* ctx, int32_t n_sets, int32_t words_per_set, const uint64_t* bits);
+/* One node's membership in every loaded set: member[s-1] != 0 (a node that joins or is relabelled).  n_sets must
+ * equal the loaded count, node < 64*words_per_set.  Completes calls in flight first. */
+int ke_node_set_bits(ke_ctx* ctx, int32_t node, int32_t n_sets, const uint8_t* member);
+/* Set id per pod for the NEXT ke_eval / ke_schedule / ke_schedule_submit of exactly n_pods pods; 0 = every node.
+ * Consumed by that call whether it succeeds or not (as ke_pod_reservations' lists).  An id outside 0..n_sets is
+ * KE_ERR_INVALID here; a following call with a different n_pods is KE_ERR_INVALID (and the ids are gone).  Does
+ * not wait for calls in flight. */
+int ke_pod_node_sets(ke_ctx* ctx, int32_t n_pods, const int32_t* set_ids);
+
 /* NodeInfo.Requested / NonZeroRequested (MilliCPU, Memory) of `node` as the plugins see it for a pod that
  * matches no reservation (after the restore above and the Reserves of past ke_schedule calls). */
 int ke_node_info_requested(ke_ctx* ctx, int32_t node, int64_t* requested /*[2]*/, int64_t* non_zero /*[2]*/);

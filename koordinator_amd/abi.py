@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 ABSENT = -1
 
 OK = 0
@@ -69,6 +69,8 @@ REASON_RSV_AFFINITY = 52  # the Reservation Filter of a reservation-affinity pod
 REASON_RSV_INSUFFICIENT_NUMA = 53  # an affinity pod's reservations cannot allocate on the NUMA affinity
 REASON_FIT_TOO_MANY_PODS, REASON_FIT_INSUFFICIENT_CPU, REASON_FIT_INSUFFICIENT_MEMORY = 64, 65, 66
 REASON_FIT_INSUFFICIENT_SCALAR = 67
+REASON_NODE_SET = 96  # the node is outside the pod's node eligibility set (ke_pod_node_sets)
+MAX_NODE_SETS = 4096
 # ke_pod.gpu_required_topology_scope (apiext.DeviceTopologyScope -> level)
 SCOPE_NONE, SCOPE_NODE, SCOPE_NUMA, SCOPE_PCIE, SCOPE_DEVICE, SCOPE_UNKNOWN = range(6)
 SCOPES = {"": SCOPE_NONE, "Node": SCOPE_NODE, "NUMANode": SCOPE_NUMA, "PCIe": SCOPE_PCIE, "Device": SCOPE_DEVICE}
@@ -556,6 +558,9 @@ EXPORTS = {
     "ke_reservation_allocs_get": (C.c_int, [C.c_void_p, i32, C.c_void_p]),
     "ke_reservations_get": (C.c_int, [C.c_void_p, i32, C.c_void_p]),
     "ke_pod_reservations": (C.c_int, [C.c_void_p, i32, C.c_void_p, C.c_void_p]),
+    "ke_node_sets_load": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
+    "ke_node_set_bits": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
+    "ke_pod_node_sets": (C.c_int, [C.c_void_p, i32, C.c_void_p]),
     "ke_node_info_requested": (C.c_int, [C.c_void_p, i32, C.POINTER(i64), C.POINTER(i64)]),
     "ke_decode_pod_device_hints": (C.c_int, [C.c_char_p, i64, C.POINTER(PodDeviceHints), C.POINTER(i32)]),
     "ke_decode_device_flags": (C.c_int, [C.c_char_p, i64, C.c_char_p, i64, C.POINTER(i32), C.POINTER(i32)]),

@@ -608,6 +608,89 @@ int ke_pod_reservations(ke_ctx* ctx, int32_t n_pods, const int32_t* offsets, con
   return KE_OK;
 }
 
+// ---- per-pod node eligibility sets (include/koord_eval.h) ----
+int ke_node_sets_load(ke_ctx* ctx, int32_t n_sets, int32_t words_per_set, const uint64_t* bits) {
+  if (ctx) async_drain(ctx);
+  if (!ctx || n_sets < 0 || words_per_set < 0) return fail(KE_ERR_INVALID, "ke_node_sets_load arguments");
+  if (n_sets > KE_MAX_NODE_SETS) return fail(KE_ERR_INVALID, "ke_node_sets_load: more than KE_MAX_NODE_SETS sets");
+  if (words_per_set > (1 << 20)) return fail(KE_ERR_INVALID, "ke_node_sets_load: words_per_set");
+  if (n_sets > 0 && !bits) return fail(KE_ERR_INVALID, "ke_node_sets_load: bits");
+  Context& c = ctx->c;
+  c.ns_n = n_sets;
+  c.ns_wps = n_sets > 0 ? words_per_set : 0;
+  c.ns_bits.assign(bits, bits + (n_sets > 0 ? (size_t)n_sets * (size_t)words_per_set : 0));
+  c.ns_dirty = true;
+  c.ns_dirty_words.clear();
+  return KE_OK;
+}
+
+int ke_node_set_bits(ke_ctx* ctx, int32_t node, int32_t n_sets, const uint8_t* member) {
+  if (ctx) async_drain(ctx);
+  if (!ctx || (n_sets > 0 && !member)) return fail(KE_ERR_INVALID, "ke_node_set_bits arguments");
+  Context& c = ctx->c;
+  if (n_sets != c.ns_n) return fail(KE_ERR_INVALID, "ke_node_set_bits: n_sets differs from the loaded table's");
+  if (node < 0 || (int64_t)node >= 64 * (int64_t)c.ns_wps)
+    return fail(KE_ERR_NOT_FOUND, "ke_node_set_bits: node index beyond the table's words_per_set");
+  const uint64_t bit = 1ull << (node & 63);
+  for (int32_t s = 0; s < n_sets; s++) {
+    uint64_t& w = c.ns_bits[(size_t)s * (size_t)c.ns_wps + (size_t)(node >> 6)];
+    w = member[s] ? (w | bit) : (w & ~bit);
+  }
+  if (!c.ns_dirty) c.ns_dirty_words.push_back(node >> 6);  // (the next call with a non-zero id uploads the column)
+  return KE_OK;
+}
+
+int ke_pod_node_sets(ke_ctx* ctx, int32_t n_pods, const int32_t* set_ids) {
+  if (!ctx || n_pods < 0 || (n_pods > 0 && !set_ids)) return fail(KE_ERR_INVALID, "ke_pod_node_sets arguments");
+  Context& c = ctx->c;
+  for (int32_t p = 0; p < n_pods; p++)
+    if (set_ids[p] < 0 || set_ids[p] > c.ns_n) return fail(KE_ERR_INVALID, "ke_pod_node_sets: set id outside 0..n_sets");
+  c.ns_staged.assign(set_ids, set_ids + n_pods);
+  c.ns_staged_on = true;
+  return KE_OK;
+}
+
+// The ke_pod_node_sets ids of this call, consumed whether it goes on or not; Context::ns_call = the ids when any is
+// non-zero (the device entry points then run the node-set kernels).  Such a call is refused here, before any state
+// changes, where the sets are not built: node-sharded contexts, and for ke_schedule (`sched`) anything but a plain
+// queue (ke_schedule_submit's sense, with device_async_ok's conditions).
+static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool sched) {
+  Context& c = ctx->c;
+  c.ns_call = nullptr;
+  if (!c.ns_staged_on) return KE_OK;
+  c.ns_staged_on = false;
+  c.ns_call_ids.swap(c.ns_staged);
+  c.ns_staged.clear();
+  if ((int32_t)c.ns_call_ids.size() != n_pods)
+    return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_node_sets ids'");
+  bool any = false;
+  for (int32_t id : c.ns_call_ids) {
+    if (id < 0 || id > c.ns_n) return fail(KE_ERR_INVALID, "a staged node set id is outside the table loaded since");
+    any = any || id != 0;
+  }
+  if (!any) return KE_OK;
+  int rc = check_pods(pods, n_pods, &c, sched);
+  if (rc) return rc;
+  auto no = [](const char* what) { return fail(KE_ERR_UNSUPPORTED, std::string("node sets: ") + what); };
+  if (c.cfg.global_node_offset != 0 || (c.dev && device_sharded(&c))) return no("a node-sharded context");
+  if (sched) {
+    if (!c.match_off.empty()) return no("a call with staged ke_pod_reservations lists");
+    if (!c.quotas.empty()) return no("a context with an ElasticQuota tree");
+    if (c.numa_enabled) return no("a context with NUMA topology policy state");
+    if (c.n_bind_nodes > 0) return no("a context with CPU bind policy nodes");
+    for (int32_t p = 0; p < n_pods; p++) {
+      if (pods[p].reservation_matched != KE_RSV_NONE) return no("a reservation-matched / ignored / affinity pod in ke_schedule");
+      if (pods[p].numa_topology_policy != KE_NUMA_POLICY_NONE) return no("a NUMA-policy pod in ke_schedule");
+      if (pods[p].quota != 0) return no("an ElasticQuota pod in ke_schedule");
+      const uint32_t f = make_dev_pod(c.cfg, pods[p], pod_hints(c, pods[p]), &c.tmpl).flags;
+      if (f & (PF_DS | PF_DS_HINT)) return no("a DeviceShare pod in ke_schedule");
+      if (f & PF_CPUSET) return no("a cpuset pod in ke_schedule");
+    }
+  }
+  c.ns_call = c.ns_call_ids.data();
+  return KE_OK;
+}
+
 int ke_node_info_requested(ke_ctx* ctx, int32_t node, int64_t* requested, int64_t* non_zero) {
   if (ctx) async_drain(ctx);
   int rc = check_node(ctx, node);
@@ -895,7 +978,9 @@ int ke_eval(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns, uin
   if (ctx) async_drain(ctx);
   if (!ctx) return fail(KE_ERR_INVALID, "null context");
   if (ctx) flush_mirror(ctx->c);
-  int rc = check_pods(pods, n_pods, &ctx->c);
+  int rc = take_node_sets(ctx, n_pods, pods, false);
+  if (rc) return rc;
+  rc = check_pods(pods, n_pods, &ctx->c);
   if (rc) return rc;
   rc = check_numa_deviceshare(ctx, pods, n_pods);
   if (rc) return rc;
@@ -1227,6 +1312,14 @@ static int schedule_sync(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_
 
 int ke_schedule(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns, int32_t* chosen, int32_t* score) {
   if (ctx) async_drain(ctx);
+  if (ctx) {
+    const int rc = take_node_sets(ctx, n_pods, pods, true);
+    if (rc) {  // (the staged ke_pod_reservations lists belong to this call too)
+      ctx->c.match_off.clear();
+      ctx->c.match_ids.clear();
+      return rc;
+    }
+  }
   return schedule_sync(ctx, n_pods, pods, now_ns, chosen, score);
 }
 
@@ -1234,6 +1327,14 @@ int ke_schedule_submit(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t 
   if (!ctx || n_pods < 0 || (n_pods > 0 && !pods) || !ticket) return fail(KE_ERR_INVALID, "ke_schedule_submit arguments");
   using clk = std::chrono::steady_clock;
   Context& c = ctx->c;
+  {
+    const int rc = take_node_sets(ctx, n_pods, pods, true);
+    if (rc) {
+      c.match_off.clear();
+      c.match_ids.clear();
+      return rc;
+    }
+  }
   int in_flight = 0;
   for (const AsyncCall& a : ctx->async) in_flight += a.fin != nullptr;
   // at most one call in flight behind which this one is enqueued (two sets of call buffers)

@@ -217,6 +217,19 @@ struct Context {
   std::vector<std::vector<int32_t>> resv_by_node;  // reservation indices per node
   // ke_pod_reservations staging for the next ke_schedule: CSR over its pods
   std::vector<int32_t> match_off, match_ids;
+  // Per-pod node eligibility sets (ke_node_sets_load): the host mirror of the table (ns_n rows of
+  // ns_wps words, set s = row s - 1; bit i & 63 of word i >> 6 = node i), what of the device copy is stale (all of
+  // it, or the word columns ke_node_set_bits patched: the next call with a non-zero id uploads them), the
+  // ke_pod_node_sets staging for the next call (ns_staged_on: staged, also when every id is 0), and the ids of the
+  // call in progress (nullptr: no non-zero id, the call runs the set-free kernels)
+  int32_t ns_n = 0, ns_wps = 0;
+  std::vector<uint64_t> ns_bits;
+  bool ns_dirty = false;
+  std::vector<int32_t> ns_dirty_words;
+  std::vector<int32_t> ns_staged;
+  bool ns_staged_on = false;
+  std::vector<int32_t> ns_call_ids;
+  const int32_t* ns_call = nullptr;
   // the KE_RSV_MATCHED pod of the current segment: its nodes with matched reservations, their
   // (node, ScoreReservation of the nominated one, smallest order) for the device pick, the nominated index
   std::vector<int32_t> rsv_nodes;

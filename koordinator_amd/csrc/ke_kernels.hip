@@ -84,7 +84,25 @@ struct SoA {
   // a KE_RSV_MATCHED segment's allocate-from-reservation decisions (RsvOvr) for its NF_RSV_CS nodes
   const RsvOvr* rovr;
   int32_t n_rovr;
+  // per-pod node eligibility sets: ns_wps words a row covering the node capacity, row 0 all ones
+  // (set id 0 = every node), row s = set s; the current call's set id per pod, parallel to its DevPod array.
+  // Read only by the NS instantiations, which the host launches for a call that carries a non-zero id.
+  int32_t ns_wps;
+  const uint64_t* ns_tbl;
+  const int32_t* ns_ids;
 };
+// node `node` is in set `sid` (NS instantiations; every node < 64 * ns_wps is in bounds, sid checked by the host)
+template <bool NS>
+__device__ __forceinline__ bool ns_ok(const SoA& s, int sid, int node) {
+  if constexpr (!NS) return true;
+  else return (s.ns_tbl[(int64_t)sid * s.ns_wps + (node >> 6)] >> (node & 63)) & 1ull;
+}
+// a fresh key of (pod with set `sid`, node): 0 (filtered) outside the set
+template <bool NS>
+__device__ __forceinline__ uint32_t ns_key(const SoA& s, int sid, int node, uint32_t key) {
+  if constexpr (!NS) return key;
+  else return ns_ok<true>(s, sid, node) ? key : 0u;
+}
 __device__ __forceinline__ const RsvOvr* rsv_ovr_of(const SoA& s, int64_t node) {
   for (int q = 0; q < s.n_rovr; q++)
     if (s.rovr[q].node == node) return &s.rovr[q];
@@ -3151,7 +3169,9 @@ __device__ __forceinline__ void defer_push(bool want, uint64_t item, uint64_t* _
 // parity mode: full status / score matrices [pod][node]; `total` holds the LoadAware + NUMA part
 // until k_parity_finalize adds the normalized DeviceShare score.  dsmax[p] = 1 + max raw DeviceShare
 // score over the pod's feasible nodes (DefaultNormalizeScore's maxCount).
-template <bool NUMA, bool CPU>
+// NS: pods with a node set (SoA::ns_ids): a pair outside the set is KE_REASON_NODE_SET ahead of every other
+// filter -- scores 0, total -1, never deferred, and not part of the pod's DeviceShare normalisation max.
+template <bool NUMA, bool CPU, bool NS = false>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, int n_nodes, const DevPod* __restrict__ pods,
                                                             int n_pods, int pods_per_block, KArgs k,
                                                             uint8_t* status, uint8_t* reason, int16_t* la,
@@ -3173,7 +3193,15 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, int n_nodes, 
   for (int p = p0; p < p1; p++) {
     uint32_t m = 0;
     bool deferred = false;
-    if (live) {
+    if (NS && live && !ns_ok<NS>(s, s.ns_ids[p], i)) {  // (one table word a wave: the lanes' addresses are equal)
+      const int64_t o_idx = (int64_t)p * n_nodes + i;
+      status[o_idx] = KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE;
+      reason[o_idx] = KE_REASON_NODE_SET;
+      la[o_idx] = 0;
+      numa[o_idx] = 0;
+      ds[o_idx] = 0;
+      total[o_idx] = -1;
+    } else if (live) {
       const EvalOut o = eval_pair<true, NUMA, NUMA, false, CPU, true>(n, expired, pods[p], k, s, i, nv);
       deferred = NUMA && o.status == STATUS_DEFERRED;
       const int64_t o_idx = (int64_t)p * n_nodes + i;
@@ -3221,7 +3249,8 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_parity_finalize(int n_nodes, KAr
 // (always alone in its batch) also dsraw[node] = raw DeviceShare score + 1 (0 when filtered out).
 // Nodes [lo, hi) of the SoA (this rank's shard); scores stay indexed by the global node index.
 // DS: the batch's pod is a DeviceShare pod (the DeviceShare path stays out of plain batches' code).
-template <bool DS, bool NUMA, bool CPU, bool EXT = false, bool H = false>
+// NS (plain batches only): a node outside the pod's node set (SoA::ns_ids) is filtered (score 0).
+template <bool DS, bool NUMA, bool CPU, bool EXT = false, bool H = false, bool NS = false>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_batch(SoA s, int lo, int hi, const DevPod* __restrict__ pods,
                                                            const int32_t* __restrict__ batch_base, int batch_pods,
                                                            int pods_per_block, KArgs k, uint16_t* __restrict__ scores,
@@ -3254,6 +3283,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_batch(SoA s, int lo, int hi
       int32_t tot = lite_total(n, expired, pod, k);
       if (EXT && tot >= 0 && (k.flags & AF_FIT_FILTER) && fit_filter_row(s, i, n, pod, k)) tot = -1;
       if (EXT && tot >= 0) tot += ext_score(s, i, pod, k);  // FitPlus / SRA / Fit: its own variant
+      if (NS && !ns_ok<NS>(s, s.ns_ids[base + p], i)) tot = -1;  // (wave-uniform word address)
       scores[(int64_t)p * score_stride + i] = (uint16_t)(tot + 1);
       continue;
     }
@@ -3283,7 +3313,9 @@ constexpr int EVAL_PPB = 8;  // pods per block (eval_grid's pod groups)
 // double work per pair, the record read once per 8 pods); 1-2 pods stream the 148-B SoA rows
 // (k_eval_batch), the smaller read when the pass is bandwidth-bound.
 __host__ __device__ constexpr bool use_record_eval(int pods) { return pods > 2; }
-template <bool EXT>
+// NS: the pods' node sets (SoA::ns_ids) -- the block's table words (one a wave and pod, the tile starts at a
+// multiple of 64: lo = 0, set calls are unsharded) are staged in LDS with the pods, a node outside is filtered.
+template <bool EXT, bool NS = false>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi, const DevPod* __restrict__ pods,
                                                            const int32_t* __restrict__ batch_base, int batch_pods,
                                                            KArgs k, uint16_t* __restrict__ scores, int64_t score_stride,
@@ -3308,9 +3340,15 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
   __shared__ double s_pd[EVAL_PPB][4];
   __shared__ int64_t s_pi[EVAL_PPB][3];
   __shared__ uint32_t s_pf[EVAL_PPB];
+  __shared__ uint64_t s_ns[NS ? EVAL_PPB : 1][EVAL_BLOCK / 64];
   if ((int)threadIdx.x < 4 * np) {
     const int q = threadIdx.x >> 2, c = threadIdx.x & 3;
     const DevPod& pp = pods[base + p0 + q];
+    if constexpr (NS) {  // wave c's word of pod q's set (past the table: no node of the tile is live there)
+      static_assert(EVAL_BLOCK / 64 == 4, "one table word per wave of the block");
+      const int w = ((lo + tile * (int)blockDim.x) >> 6) + c;
+      s_ns[q][c] = w < s.ns_wps ? s.ns_tbl[(int64_t)s.ns_ids[base + p0 + q] * s.ns_wps + w] : 0ull;
+    }
     s_pd[q][c] = (double)(c < 2 ? pp.est[c] : pp.req[c - 2]);
     if (!EXT && c < 3) s_pi[q][c] = c < 2 ? pp.est[c] : pp.req[0];
     if (!EXT && c == 3) s_pf[q] = pp.flags;
@@ -3335,6 +3373,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
       pl.req[0] = s_pi[q][2];
       t = fast_total<false>(f, pl, ed, rd, k);
     }
+    if (NS && !((s_ns[q][threadIdx.x >> 6] >> (threadIdx.x & 63)) & 1ull)) t = -1;
     out[(int64_t)q * score_stride] = (uint16_t)(t + 1);
   }
 }
@@ -3343,7 +3382,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
 // b's eval waited only for batch b-3's done flag; once done[b-2] is published (a k_handoff ahead of this kernel)
 // lane t of workgroup j re-evaluates node t of batch b-2's changed list (written with its rows, drained before
 // the flag) for pod j from its record, as k_eval_plain does -- the lists then see every Reserve of batches <= b-2.
-template <bool EXT>
+template <bool EXT, bool NS = false>
 __global__ __launch_bounds__(64) void k_patch(SoA s, const DevPod* __restrict__ pods, const int32_t* __restrict__ batch_base,
                                               KArgs k, const int32_t* __restrict__ tlist, uint16_t* __restrict__ scores,
                                               int64_t score_stride, const int32_t* __restrict__ done_wait,
@@ -3364,7 +3403,9 @@ __global__ __launch_bounds__(64) void k_patch(SoA s, const DevPod* __restrict__ 
   fast_adopt(f, k);
   const DevPod pod = pods[*batch_base + j];
   const double ed[2] = {(double)pod.est[0], (double)pod.est[1]}, rd[2] = {(double)pod.req[0], (double)pod.req[1]};
-  scores[(int64_t)j * score_stride + node] = (uint16_t)(fast_total<EXT>(f, pod, ed, rd, k) + 1);
+  int32_t tot = fast_total<EXT>(f, pod, ed, rd, k);
+  if (NS && !ns_ok<NS>(s, s.ns_ids[*batch_base + j], node)) tot = -1;  // outside the pod's node set
+  scores[(int64_t)j * score_stride + node] = (uint16_t)(tot + 1);
 }
 
 // selectHost for a singleton batch: the best packed key over nodes [lo, hi) (ties to the lowest node
@@ -4396,7 +4437,7 @@ constexpr int FIX_BLOCK = KSTALE + KMAX;  // stale keys, then fresh keys of the 
 // The touched nodes come as the Reserve kernel's compact list of the rows batch b-1 changed (distinct
 // nodes, the node index in Row.pad), so no row gather depends on a node id read after the wait.
 
-template <bool EXT>
+template <bool EXT, bool NS = false>
 __global__ __launch_bounds__(FIX_BLOCK) void k_fixup(SoA s, const DevPod* __restrict__ pods,
                                                      const int32_t* __restrict__ batch_base, KArgs k,
                                                      const uint32_t* __restrict__ stale,
@@ -4442,7 +4483,7 @@ __global__ __launch_bounds__(FIX_BLOCK) void k_fixup(SoA s, const DevPod* __rest
   } else if (node >= 0) {
     fast_adopt(n, k);
     const double estd[2] = {(double)pod.est[0], (double)pod.est[1]}, reqd[2] = {(double)pod.req[0], (double)pod.req[1]};
-    key = make_key(fast_total<EXT>(n, pod, estd, reqd, k), node);
+    key = ns_key<NS>(s, NS ? s.ns_ids[*batch_base + j] : 0, node, make_key(fast_total<EXT>(n, pod, estd, reqd, k), node));
   }
   reinterpret_cast<uint32_t*>(s_k)[t] = key;
   const int nz = __syncthreads_count(key != 0u);
@@ -4479,7 +4520,7 @@ __global__ __launch_bounds__(FIX_BLOCK) void k_fixup(SoA s, const DevPod* __rest
 constexpr int FIXL_BLOCK = KSTALE2 + KMAX;
 constexpr int FIXL_PARTS_BLOCK = 1024;
 static_assert((1024 / KSTALE2) * KSTALE2 <= FIXL_PARTS_BLOCK, "every part of a select-ahead split fits a workgroup");
-template <bool EXT, bool PARTS = false>
+template <bool EXT, bool PARTS = false, bool NS = false>
 __global__ __launch_bounds__(PARTS ? FIXL_PARTS_BLOCK : FIXL_BLOCK) void k_fixlist(
     SoA s, const DevPod* __restrict__ pods, const int32_t* __restrict__ batch_base, KArgs k,
     const uint32_t* __restrict__ pre, const int32_t* __restrict__ pre_cnt, const int32_t* __restrict__ tlist,
@@ -4552,7 +4593,7 @@ __global__ __launch_bounds__(PARTS ? FIXL_PARTS_BLOCK : FIXL_BLOCK) void k_fixli
   } else if (node >= 0) {
     fast_adopt(n, k);
     const double estd[2] = {(double)pod.est[0], (double)pod.est[1]}, reqd[2] = {(double)pod.req[0], (double)pod.req[1]};
-    key = make_key(fast_total<EXT>(n, pod, estd, reqd, k), node);
+    key = ns_key<NS>(s, NS ? s.ns_ids[*batch_base + j] : 0, node, make_key(fast_total<EXT>(n, pod, estd, reqd, k), node));
   }
   if (t < FIXL_BLOCK) reinterpret_cast<uint32_t*>(s_k)[t] = key;
   const int nz = __syncthreads_count(key != 0u);
@@ -4800,7 +4841,8 @@ struct ResLdsCore {
 // SIMDs of their own instead of queueing behind a concurrent eval's FP64 instructions (pipelined schedule).
 constexpr int CU_LDS_BYTES = 163840;
 struct ResLds : ResLdsCore {
-  uint8_t cu_fill[CU_LDS_BYTES - 64 - sizeof(ResLdsCore)];
+  int32_t nsid[MAX_BATCH];  // the pods' node set ids (NS instantiations; behind the core, whose offsets stay)
+  uint8_t cu_fill[CU_LDS_BYTES - 64 - sizeof(ResLdsCore) - sizeof(int32_t) * MAX_BATCH];
 };
 static_assert(sizeof(ResLds) == CU_LDS_BYTES - 64, "ResLds fills the CU's LDS");
 
@@ -4970,7 +5012,13 @@ __device__ __forceinline__ void spec_predict_lean(ResLds& L, const ChgSet& C, in
 // j's best such node in its stale list); S evaluates every pod against all of T besides its own slots c < j; a
 // pod whose best current key is a T node takes it in V (Reserve on the T slot).  The batch's changed nodes --
 // its own slots and the T slots it reserved -- are written back and become the next batch's T.
-template <bool EXT>
+// NS: a fresh key of a node outside the pod's node set (L.nsid) is 0, as its snapshot key was
+template <bool NS>
+__device__ __forceinline__ int nsid_of(const ResLds& L, int j) {
+  if constexpr (NS) return L.nsid[j];
+  else return 0;
+}
+template <bool EXT, bool NS = false>
 __device__ __forceinline__ void replay_spec(ResLds& L, const ChgSet& C, const SoA& s, const int base, const int B,
                                             const KArgs& k, int32_t* __restrict__ chosen,
                                             int32_t* __restrict__ chosen_score, int32_t global_offset,
@@ -5016,7 +5064,7 @@ __device__ __forceinline__ void replay_spec(ResLds& L, const ChgSet& C, const So
     if (L.sp.tver[j] == tres) return;
     const DevPod p = L.pod[j];
     const double ed[2] = {L.pd[j][0], L.pd[j][1]}, rd[2] = {L.pd[j][2], L.pd[j][3]};
-    uint32_t tk = tv ? make_key(fast_total<EXT>(tslot, p, ed, rd, k), tnode) : 0u;
+    uint32_t tk = tv ? ns_key<NS>(s, nsid_of<NS>(L, j), tnode, make_key(fast_total<EXT>(tslot, p, ed, rd, k), tnode)) : 0u;
     tk = wave_max_u32(tk);
     if (lane == 0) L.sp.tmx[j] = tk, L.sp.tver[j] = tres;
   };
@@ -5036,8 +5084,8 @@ __device__ __forceinline__ void replay_spec(ResLds& L, const ChgSet& C, const So
     const double ed1[2] = {L.pd[j1][0], L.pd[j1][1]}, rd1[2] = {L.pd[j1][2], L.pd[j1][3]};
     uint32_t tk = 0, tk1 = 0;
     if (tv) {
-      tk = make_key(fast_total<EXT>(tslot, p, ed, rd, k), tnode);
-      tk1 = make_key(fast_total<EXT>(tslot, p1, ed1, rd1, k), tnode);
+      tk = ns_key<NS>(s, nsid_of<NS>(L, j), tnode, make_key(fast_total<EXT>(tslot, p, ed, rd, k), tnode));
+      tk1 = ns_key<NS>(s, nsid_of<NS>(L, j1), tnode, make_key(fast_total<EXT>(tslot, p1, ed1, rd1, k), tnode));
     }
     tk = wave_max_u32(tk);
     tk1 = wave_max_u32(tk1);
@@ -5166,13 +5214,13 @@ __device__ __forceinline__ void replay_spec(ResLds& L, const ChgSet& C, const So
         for (int j = c + 1 + g; pv && j < end; j += RS * GW) {
           const DevPod p = L.pod[j];
           const double ed[2] = {L.pd[j][0], L.pd[j][1]}, rd[2] = {L.pd[j][2], L.pd[j][3]};
-          const uint32_t kc = make_key(fast_total<EXT>(pslot, p, ed, rd, k), pnode);
+          const uint32_t kc = ns_key<NS>(s, nsid_of<NS>(L, j), pnode, make_key(fast_total<EXT>(pslot, p, ed, rd, k), pnode));
           uint32_t kc1 = 0u;
           const int j1 = j + GW;
           if (RS == 2 && j1 < end) {
             const DevPod p1 = L.pod[j1];
             const double ed1[2] = {L.pd[j1][0], L.pd[j1][1]}, rd1[2] = {L.pd[j1][2], L.pd[j1][3]};
-            kc1 = make_key(fast_total<EXT>(pslot, p1, ed1, rd1, k), pnode);
+            kc1 = ns_key<NS>(s, nsid_of<NS>(L, j1), pnode, make_key(fast_total<EXT>(pslot, p1, ed1, rd1, k), pnode));
           }
           if (kc) atomicMax(&L.sp.mrow[j], kc);
           if (kc1) atomicMax(&L.sp.mrow[j1], kc1);
@@ -5225,10 +5273,10 @@ __device__ __forceinline__ void replay_spec(ResLds& L, const ChgSet& C, const So
         if (has1) {
           const DevPod p1 = L.pod[j1];
           const double ed1[2] = {L.pd[j1][0], L.pd[j1][1]}, rd1[2] = {L.pd[j1][2], L.pd[j1][3]};
-          if (sv && lane < j) kc = make_key(fast_total<EXT>(slot, p, ed, rd, k), snode);
-          if (sv && lane < j1) kc1 = make_key(fast_total<EXT>(slot, p1, ed1, rd1, k), snode);
+          if (sv && lane < j) kc = ns_key<NS>(s, nsid_of<NS>(L, j), snode, make_key(fast_total<EXT>(slot, p, ed, rd, k), snode));
+          if (sv && lane < j1) kc1 = ns_key<NS>(s, nsid_of<NS>(L, j1), snode, make_key(fast_total<EXT>(slot, p1, ed1, rd1, k), snode));
         } else if (sv && lane < j) {
-          kc = make_key(fast_total<EXT>(slot, p, ed, rd, k), snode);
+          kc = ns_key<NS>(s, nsid_of<NS>(L, j), snode, make_key(fast_total<EXT>(slot, p, ed, rd, k), snode));
         }
         uint32_t tk = 0, tk1 = 0;
         if (tin) {  // T changes only when a pod of the batch reserves on it: pod j's T max is cached meanwhile
@@ -5359,7 +5407,7 @@ __device__ __forceinline__ ChgSet chg_init(ResLds& L, uint32_t* glb, int n_nodes
   return ChgSet{L.chg, glb};
 }
 
-template <bool DS, bool NUMA, bool QUOTA, bool EXT>
+template <bool DS, bool NUMA, bool QUOTA, bool EXT, bool NS>
 __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const SoA& s, const int base, const int B,
                                              const KArgs& k, int32_t* __restrict__ chosen,
                                              int32_t* __restrict__ chosen_score, int32_t global_offset,
@@ -5370,7 +5418,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
 
 // One batch: prologue on every thread of the workgroup (the batch's pods and exact candidate lists
 // into LDS), replay on wave 0 (the other waves skip it).
-template <bool DS, bool NUMA, bool QUOTA, bool EXT = true>
+template <bool DS, bool NUMA, bool QUOTA, bool EXT = true, bool NS = false>
 __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const SoA& s, const DevPod* __restrict__ pods,
                                               const int base, const int B, const KArgs& k,
                                               const uint32_t* __restrict__ cand, const int32_t* __restrict__ cand_cnt,
@@ -5413,6 +5461,7 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
     L.pd[tid][1] = (double)pd.est[1];
     L.pd[tid][2] = (double)pd.req[0];
     L.pd[tid][3] = (double)pd.req[1];
+    if constexpr (NS) L.nsid[tid] = s.ns_ids[base + tid];
     if (DS) {  // written by this batch's eval / select, earlier on the same stream
       L.dsm[tid] = s.dsb[DSB_MAX + tid];
       L.dsc[tid] = (int32_t)s.dsb[DSB_CNT + tid];
@@ -5447,7 +5496,7 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
   }
   if constexpr (!DS && !NUMA && !QUOTA) {  // plain batch: the speculative replay on every wave
     __builtin_amdgcn_s_setprio(3);
-    replay_spec<EXT>(L, C, s, base, B, k, chosen, chosen_score, global_offset, stamps, batch_index, dev_alloc,
+    replay_spec<EXT, NS>(L, C, s, base, B, k, chosen, chosen_score, global_offset, stamps, batch_index, dev_alloc,
                      touched_out, touched_cnt, pstamps + PST * batch_index, has_t, keep, LS, sorted, th);
     __builtin_amdgcn_s_setprio(0);
     return;
@@ -5455,7 +5504,7 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
   if (tid >= 64) return;  // the replay is one wavefront: wave-level ordering only from here on
   // the next batch's eval waves may share this SIMD (pipelined schedule): the replay issues first
   __builtin_amdgcn_s_setprio(3);
-  replay_batch<DS, NUMA, QUOTA, EXT>(L, C, s, base, B, k, chosen, chosen_score, global_offset, stamps, batch_index,
+  replay_batch<DS, NUMA, QUOTA, EXT, NS>(L, C, s, base, B, k, chosen, chosen_score, global_offset, stamps, batch_index,
                                 dev_alloc, numa_alloc, touched_out, touched_cnt, pstamps + PST * batch_index);
   __builtin_amdgcn_s_setprio(0);
 }
@@ -5469,7 +5518,7 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
 //   fetched from the SoA by the next free lane at the start of the pod, into spare registers, so its
 //   latency hides under the re-evaluation; it becomes that lane's row if bu wins.  Pod j+1's record
 //   and candidates are read during pod j, its changed flags right after pod j's Reserve.
-template <bool DS, bool NUMA, bool QUOTA, bool EXT>
+template <bool DS, bool NUMA, bool QUOTA, bool EXT, bool NS>
 __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const SoA& s, const int base, const int B,
                                              const KArgs& k, int32_t* __restrict__ chosen,
                                              int32_t* __restrict__ chosen_score, int32_t global_offset,
@@ -5477,6 +5526,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
                                              uint64_t* __restrict__ dev_alloc, int64_t* __restrict__ numa_alloc,
                                              int64_t* __restrict__ touched_out, int32_t* __restrict__ touched_cnt,
                                              uint64_t* __restrict__ pst) {
+  static_assert(!NS || (!DS && !NUMA), "node sets: plain batches only");
   const uint32_t* const s_cand = L.cand;
   const DevPod* const s_pod = L.pod;
   const int lane = threadIdx.x & 63;
@@ -5545,7 +5595,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
       } else {
         tot = fast_total<EXT>(fast, pod, estd, reqd, k);
       }
-      kc = make_key(tot, my_node);
+      kc = ns_key<NS>(s, nsid_of<NS>(L, j), my_node, make_key(tot, my_node));
     }
     RPROF(2)
     const uint32_t bc = wave_max_u32(kc);
@@ -5727,7 +5777,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
   drain_stores();  // every hand-off store is performed before the workgroup publishes the batch
 }
 
-template <bool DS, bool NUMA, bool QUOTA>
+template <bool DS, bool NUMA, bool QUOTA, bool NS = false>
 __global__ __launch_bounds__(res_threads<NUMA>()) void k_resolve(SoA s, const DevPod* __restrict__ pods, const int32_t* __restrict__ batch_base,
                                                 int batch_pods, KArgs k, const uint32_t* __restrict__ cand,
                                                 const int32_t* __restrict__ cand_cnt, int32_t* __restrict__ chosen,
@@ -5738,7 +5788,7 @@ __global__ __launch_bounds__(res_threads<NUMA>()) void k_resolve(SoA s, const De
                                                 int n_nodes, int sorted) {
   __shared__ ResLds L;
   const ChgSet C = chg_init(L, chg_glb, n_nodes);
-  resolve_batch<DS, NUMA, QUOTA>(L, C, s, pods, *batch_base, batch_pods, k, cand, cand_cnt, chosen, chosen_score,
+  resolve_batch<DS, NUMA, QUOTA, true, NS>(L, C, s, pods, *batch_base, batch_pods, k, cand, cand_cnt, chosen, chosen_score,
                                  global_offset, stamps, pstamps, batch_index, dev_alloc, numa_alloc, nullptr, nullptr,
                                  false, false, KMAX, sorted != 0);
 }
@@ -5750,7 +5800,7 @@ __global__ __launch_bounds__(res_threads<NUMA>()) void k_resolve(SoA s, const De
 // one relaxed add on tready[b] per helper.  A batch the Reserve workgroup has already finished (done[b]) is
 // skipped; the Reserve workgroup falls back to its own rows for any batch whose maxima arrive late, so no
 // wait of the run depends on a helper being resident.
-template <bool EXT>
+template <bool EXT, bool NS = false>
 __device__ __noinline__ void t_helper(ResLds& L, const SoA& s, const DevPod* __restrict__ pods,
                                       const int32_t* __restrict__ bases, int b0, int nb, const KArgs& k,
                                       const int32_t* __restrict__ done, int32_t* __restrict__ err, const THelp th,
@@ -5767,6 +5817,7 @@ __device__ __noinline__ void t_helper(ResLds& L, const SoA& s, const DevPod* __r
       L.pd[threadIdx.x][1] = (double)pd.est[1];
       L.pd[threadIdx.x][2] = (double)pd.req[0];
       L.pd[threadIdx.x][3] = (double)pd.req[1];
+      if constexpr (NS) L.nsid[threadIdx.x] = s.ns_ids[base + threadIdx.x];
     }
     if (threadIdx.x == 0) {
       int go = -1;
@@ -5804,11 +5855,12 @@ __device__ __noinline__ void t_helper(ResLds& L, const SoA& s, const DevPod* __r
         const bool has1 = j1 < B;
         const DevPod p = L.pod[j];
         const double ed[2] = {L.pd[j][0], L.pd[j][1]}, rd[2] = {L.pd[j][2], L.pd[j][3]};
-        uint32_t tk = tv ? make_key(fast_total<EXT>(tslot, p, ed, rd, k), tnode) : 0u, tk1 = 0u;
+        uint32_t tk = tv ? ns_key<NS>(s, nsid_of<NS>(L, j), tnode, make_key(fast_total<EXT>(tslot, p, ed, rd, k), tnode)) : 0u;
+        uint32_t tk1 = 0u;
         if (has1) {
           const DevPod p1 = L.pod[j1];
           const double ed1[2] = {L.pd[j1][0], L.pd[j1][1]}, rd1[2] = {L.pd[j1][2], L.pd[j1][3]};
-          tk1 = tv ? make_key(fast_total<EXT>(tslot, p1, ed1, rd1, k), tnode) : 0u;
+          tk1 = tv ? ns_key<NS>(s, nsid_of<NS>(L, j1), tnode, make_key(fast_total<EXT>(tslot, p1, ed1, rd1, k), tnode)) : 0u;
         }
         tk = wave_max_u32(tk);
         tk1 = wave_max_u32(tk1);
@@ -5833,7 +5885,7 @@ __device__ __noinline__ void t_helper(ResLds& L, const SoA& s, const DevPod* __r
 //   else: the stale top-(k_j + KMAX) lists of the double buffer `stale` (stride KSTALE) go straight to the
 //   speculative replay, with the previous batch's changed rows (touched_out, this workgroup wrote them) as
 //   its T slots -- no fixup kernel and no hand-off back to the eval stream on the critical path.
-template <bool QUOTA, bool EXT>
+template <bool QUOTA, bool EXT, bool NS = false>
 __global__ __launch_bounds__(res_threads<false>()) void k_resolve_run(SoA s, const DevPod* __restrict__ pods,
                                                                       const int32_t* __restrict__ bases, int b0, int nb,
                                                                       KArgs k, const uint32_t* __restrict__ cand,
@@ -5856,7 +5908,7 @@ __global__ __launch_bounds__(res_threads<false>()) void k_resolve_run(SoA s, con
   const bool nofix = !QUOTA && stale != nullptr;
   if (blockIdx.x == 0 && threadIdx.x == 0 && th.resident) st_sc1(th.resident, 1);
   if (blockIdx.x > 0) {  // a T-row helper
-    if (nofix) t_helper<EXT>(L, s, pods, bases, b0, nb, k, done, err, th, (int)blockIdx.x - 1, &s_ok);
+    if (nofix) t_helper<EXT, NS>(L, s, pods, bases, b0, nb, k, done, err, th, (int)blockIdx.x - 1, &s_ok);
     return;
   }
   if (!nofix) th.H = 0, th.tlist = nullptr;
@@ -5871,7 +5923,7 @@ __global__ __launch_bounds__(res_threads<false>()) void k_resolve_run(SoA s, con
     const int par = b & 1;
     const bool has_t = nofix && b > b0;       // the previous batch's changed nodes (L.trec)
     const bool keep = nofix && b + 1 < b0 + nb;  // this batch's are the next one's T
-    resolve_batch<false, false, QUOTA, EXT>(L, C, s, pods, base, B, k, nofix ? stale + (int64_t)par * MAX_BATCH * KSTALE : cand,
+    resolve_batch<false, false, QUOTA, EXT, NS>(L, C, s, pods, base, B, k, nofix ? stale + (int64_t)par * MAX_BATCH * KSTALE : cand,
                                        nofix ? stale_cnt + par * MAX_BATCH : cand_cnt, chosen, chosen_score, global_offset,
                                        stamps, pstamps, b, dev_alloc, nullptr, touched_out, touched_cnt, has_t, keep,
                                        nofix ? KSTALE : KMAX, !nofix || sorted != 0,  // (k_fixup's lists: by rank)
@@ -6865,6 +6917,11 @@ struct DeviceState {
   int64_t pods_cap = 0;
   DevPodHint* d_ph = nullptr;  // the hinted pods' records of the current call
   int64_t ph_cap = 0;
+  // node eligibility sets: rows 0 .. ns_n of capacity / 64 words (row 0 all ones); a call's set ids
+  // lie behind its DevPod records in d_pods (one per buffer set), staged page-locked in host_ns
+  uint64_t* d_ns_tbl = nullptr;
+  int64_t ns_tbl_cap = 0;
+  PinnedVec<int32_t> host_ns;
   int8_t* d_vfo = nullptr;     // [n_pods][2][DS_MINORS] VF ranks of the Reserves
   int64_t vfo_cap = 0;
   // batch buffers
@@ -6945,6 +7002,7 @@ struct DeviceState {
   // the other call's buffers of two in flight (ke_schedule_submit): swapped with the fields of the same name
   struct CallBufs {
     PinnedVec<DevPod> host_pods;
+    PinnedVec<int32_t> host_ns;
     DevPod* d_pods = nullptr;
     int64_t pods_cap = 0;
     int32_t *d_chosen = nullptr, *d_chosen_score = nullptr;
@@ -7221,7 +7279,7 @@ void device_destroy(Context* ctx) {
                   d->d_cpurows, d->d_cpusets, d->d_aff, d->soa.qt, d->soa.qm, d->d_sched, d->d_stale,
                   d->d_stale_cnt, d->d_pre, d->d_trows, d->d_tcnt, d->d_parts_done, d->d_scores2, d->d_split2, d->d_chg, d->soa.rec, d->soa.pt, d->soa.kerr,
                   d->soa.xf, d->soa.xm, d->d_xrows, d->soa.dsx, d->d_ph, d->d_vfo, d->d_rsv, d->d_rsv_out, d->d_rsv_st,
-                  d->d_rsv_views, d->d_ds_views, d->d_numa_views, d->d_rovr, d->d_rsv_gate};
+                  d->d_rsv_views, d->d_ds_views, d->d_numa_views, d->d_rovr, d->d_rsv_gate, d->d_ns_tbl};
   if (d->estream) (void)hipStreamSynchronize(d->estream);
   if (d->estream2) (void)hipStreamSynchronize(d->estream2);
   for (void* p : ptrs)
@@ -7725,6 +7783,46 @@ int device_refresh_flush(Context* ctx, const int32_t* gate) {
   return KE_OK;
 }
 
+// The device copy of the node-set table brought up to date for a call that carries set ids: rows
+// 0 .. ns_n of capacity / 64 words -- row 0 all ones (id 0: every node), row s the words of set s below the node
+// capacity, zero beyond words_per_set -- so a kernel's lookup of any (id, node < capacity) is in bounds without a
+// branch.  A reload uploads the table, ke_node_set_bits' patches their word columns.  The table only changes with
+// no call in flight (the entry points that change it complete them first).
+static int node_sets_sync(Context* ctx) {
+  DeviceState* d = ctx->dev;
+  const int64_t W = d->capacity / 64, wps = ctx->ns_wps, cw = std::min<int64_t>(W, wps);
+  const int64_t rows = (int64_t)ctx->ns_n + 1;
+  if (ctx->ns_dirty || !d->d_ns_tbl) {
+    std::vector<uint64_t> t((size_t)(rows * W), 0ull);
+    std::fill(t.begin(), t.begin() + W, ~0ull);
+    for (int64_t r = 0; r + 1 < rows; r++)
+      std::copy(ctx->ns_bits.begin() + r * wps, ctx->ns_bits.begin() + r * wps + cw, t.begin() + (r + 1) * W);
+    const int rc = ensure((void**)&d->d_ns_tbl, &d->ns_tbl_cap, (int64_t)sizeof(uint64_t) * rows * W);
+    if (rc) return rc;
+    HIP_OK(hipMemcpyAsync(d->d_ns_tbl, t.data(), sizeof(uint64_t) * t.size(), hipMemcpyHostToDevice, d->stream));
+    HIP_OK(hipStreamSynchronize(d->stream));
+  } else if (!ctx->ns_dirty_words.empty() && rows > 1) {
+    std::vector<int32_t>& dw = ctx->ns_dirty_words;
+    std::sort(dw.begin(), dw.end());
+    dw.erase(std::unique(dw.begin(), dw.end()), dw.end());
+    std::vector<uint64_t> col((size_t)(rows - 1) * dw.size());
+    size_t q = 0;
+    for (int32_t w : dw) {
+      if (w >= cw) continue;
+      uint64_t* cq = col.data() + (q++) * (size_t)(rows - 1);
+      for (int64_t r = 0; r + 1 < rows; r++) cq[r] = ctx->ns_bits[(size_t)(r * wps + w)];
+      HIP_OK(hipMemcpy2DAsync(d->d_ns_tbl + W + w, sizeof(uint64_t) * W, cq, sizeof(uint64_t), sizeof(uint64_t),
+                              (size_t)(rows - 1), hipMemcpyHostToDevice, d->stream));
+    }
+    HIP_OK(hipStreamSynchronize(d->stream));
+  }
+  ctx->ns_dirty = false;
+  ctx->ns_dirty_words.clear();
+  d->soa.ns_tbl = d->d_ns_tbl;
+  d->soa.ns_wps = (int32_t)W;
+  return KE_OK;
+}
+
 static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, hipStream_t ustream = nullptr) {
   DeviceState* d = ctx->dev;
   if (!ustream) ustream = d->stream;
@@ -7746,9 +7844,19 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, hipStre
       dp[p].ring_bw = (int64_t)ph.size() - 1;
     }
   }
-  int rc = ensure((void**)&d->d_pods, &d->pods_cap, sizeof(DevPod) * (int64_t)std::max(n_pods, 1));
+  const int32_t* ns = ctx->ns_call;  // the call's node set ids (a non-zero one among them): behind the records
+  int rc = ensure((void**)&d->d_pods, &d->pods_cap,
+                  sizeof(DevPod) * (int64_t)std::max(n_pods, 1) + (ns ? sizeof(int32_t) * (int64_t)n_pods : 0));
   if (rc) return rc;
   HIP_OK(hipMemcpyAsync(d->d_pods, dp.data(), sizeof(DevPod) * n_pods, hipMemcpyHostToDevice, ustream));
+  d->soa.ns_ids = nullptr;
+  if (ns) {
+    if (!d->host_ns.resize((size_t)n_pods)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the node set id staging buffer");
+    std::copy(ns, ns + n_pods, d->host_ns.data());
+    int32_t* d_ids = reinterpret_cast<int32_t*>(d->d_pods + n_pods);
+    HIP_OK(hipMemcpyAsync(d_ids, d->host_ns.data(), sizeof(int32_t) * n_pods, hipMemcpyHostToDevice, ustream));
+    d->soa.ns_ids = d_ids;
+  }
   if (!ph.empty()) {
     rc = ensure((void**)&d->d_ph, &d->ph_cap, sizeof(DevPodHint) * (int64_t)ph.size());
     if (rc) return rc;
@@ -7767,6 +7875,11 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
   int rc = device_refresh(ctx, now);
   if (rc) return rc;
   if (n_pods == 0) return KE_OK;
+  const bool ns = ctx->ns_call != nullptr;  // pods with node sets: the NS instantiations
+  if (ns) {
+    rc = node_sets_sync(ctx);
+    if (rc) return rc;
+  }
   rc = upload_pods(ctx, n_pods, pods);
   if (rc) return rc;
   const int64_t N = ctx->n_nodes, P = n_pods, M = N * P;
@@ -7797,7 +7910,8 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
       rc = ensure((void**)&d->d_defer_cnt, &d->defer_cnt_cap, sizeof(uint32_t));
       if (rc) return rc;
       HIP_OK(hipMemsetAsync(d->d_defer_cnt, 0, sizeof(uint32_t), d->stream));
-      hipLaunchKernelGGL((cpu ? k_eval_parity<true, true> : k_eval_parity<true, false>), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->d_pods, (int)P,
+      hipLaunchKernelGGL((ns ? (cpu ? k_eval_parity<true, true, true> : k_eval_parity<true, false, true>)
+                             : (cpu ? k_eval_parity<true, true> : k_eval_parity<true, false>)), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->d_pods, (int)P,
                          ppb, k, d_status, d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, d->d_defer, d->d_defer_cnt);
       HIP_OK(hipGetLastError());
       uint32_t* fb = reinterpret_cast<uint32_t*>(d->d_defer + M);
@@ -7810,7 +7924,8 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
                          d->d_batch_base, k, d->d_defer, d->d_defer_cnt, d->d_scores, d->capacity, (int)N, d_status,
                          d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, nullptr, nullptr, fb);
     } else {
-      hipLaunchKernelGGL((cpu ? k_eval_parity<false, true> : k_eval_parity<false, false>), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->d_pods, (int)P,
+      hipLaunchKernelGGL((ns ? (cpu ? k_eval_parity<false, true, true> : k_eval_parity<false, false, true>)
+                             : (cpu ? k_eval_parity<false, true> : k_eval_parity<false, false>)), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->d_pods, (int)P,
                          ppb, k, d_status, d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, nullptr, nullptr);
     }
     HIP_OK(hipGetLastError());
@@ -7846,6 +7961,7 @@ void device_swap_call_buffers(Context* ctx) {
   DeviceState* d = ctx->dev;
   DeviceState::CallBufs& a = d->alt;
   d->host_pods.swap(a.host_pods);
+  d->host_ns.swap(a.host_ns);
   std::swap(d->d_pods, a.d_pods);
   std::swap(d->pods_cap, a.pods_cap);
   std::swap(d->d_chosen, a.d_chosen);
@@ -7918,6 +8034,14 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
   if (n_pods == 0) return KE_OK;
   tp = clk::now();
   hipStream_t const cs = d->cstream ? d->cstream : d->stream;  // the call's staging stream
+  // a call with node set ids (a plain queue, ke_capi.cpp take_node_sets): the NS instantiations of every kernel that
+  // turns a (pod, node) pair into a score or key
+  const bool ns = ctx->ns_call != nullptr;
+  if (ns) {
+    if ((int64_t)ctx->ns_call_ids.size() != n_pods) return fail(KE_ERR_DEVICE, "internal: node set ids of another call");
+    rc = node_sets_sync(ctx);
+    if (rc) return rc;
+  }
   rc = upload_pods(ctx, n_pods, pods, cs);
   if (rc) return rc;
   ctx->host_ms[2] = ms_since(tp);
@@ -8171,11 +8295,14 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
                               : (numa ? k_eval_batch<false, true, true> : k_eval_batch<false, false, true>))
                         : ds ? (numa ? k_eval_batch<true, true, false> : k_eval_batch<true, false, false>)
                              : (numa ? k_eval_batch<false, true, false>
-                                     : ((k.flags & AF_EXT) ? k_eval_batch<false, false, false, true>
-                                                           : k_eval_batch<false, false, false>));
+                                     : ns ? ((k.flags & AF_EXT) ? k_eval_batch<false, false, false, true, false, true>
+                                                                : k_eval_batch<false, false, false, false, false, true>)
+                                          : ((k.flags & AF_EXT) ? k_eval_batch<false, false, false, true>
+                                                                : k_eval_batch<false, false, false>));
         uint32_t* dcnt = numa ? d->d_defer_cnt + b : nullptr;
         if (plain_rec)  // plain batch: the record-based evaluation
-          hipLaunchKernelGGL(((k.flags & AF_EXT) ? k_eval_plain<true> : k_eval_plain<false>), grid, dim3(eb), 0, es, d->soa,
+          hipLaunchKernelGGL((ns ? ((k.flags & AF_EXT) ? k_eval_plain<true, true> : k_eval_plain<false, true>)
+                                 : ((k.flags & AF_EXT) ? k_eval_plain<true> : k_eval_plain<false>)), grid, dim3(eb), 0, es, d->soa,
                              lo, hi, d->d_pods, bbase, bp, k, scores, d->capacity, fold_begin ? estamps + b : nullptr,
                              wait_kernel ? nullptr : dwait, d_err);
         else
@@ -8203,7 +8330,8 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
       // the nodes batch b-2 changed, once it is done (k_patch waits for the flag; folding it into the split select
       // was measured slower: 256 select workgroups spinning on the flag)
       if (pwait)
-        hipLaunchKernelGGL(((k.flags & AF_EXT) ? k_patch<true> : k_patch<false>), dim3((unsigned)bp), dim3(64), d->excl_lds, es,
+        hipLaunchKernelGGL((ns ? ((k.flags & AF_EXT) ? k_patch<true, true> : k_patch<false, true>)
+                               : ((k.flags & AF_EXT) ? k_patch<true> : k_patch<false>)), dim3((unsigned)bp), dim3(64), d->excl_lds, es,
                            d->soa, d->d_pods, bbase, k, ptl, scores, d->capacity, pwait, d_err);
       if (ds && sharded && !d->loopback) {  // DefaultNormalizeScore's max over the feasible nodes of all ranks
         const int crc = coll_all_reduce(d, d->d_dsmax, 1, KE_COLL_U32, KE_COLL_MAX, es);
@@ -8319,6 +8447,7 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
       const bool two_es = !fixup && d->estream2 != nullptr && !sharded;
       const bool ahead = two_es && d->eval_patch && d->select_ahead;  // (k_fixlist's lists: descending)
       hipLaunchKernelGGL((quota ? (ext ? k_resolve_run<true, true> : k_resolve_run<true, false>)
+                          : ns  ? (ext ? k_resolve_run<false, true, true> : k_resolve_run<false, false, true>)
                                 : (ext ? k_resolve_run<false, true> : k_resolve_run<false, false>)), dim3(1 + th.H), dim3(res_threads<false>()), 0,
                          d->stream, d->soa, d->d_pods, d_bases, r0, e - r0, k, d->d_cand, d->d_cand_cnt, d->d_chosen,
                          d->d_chosen_score, ctx->cfg.global_node_offset, d->d_stamps, d->d_stamps + (n_pods + 2),
@@ -8342,14 +8471,16 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
             const int32_t* pre_cnt = reinterpret_cast<const int32_t*>(d->d_pre + (size_t)2 * MAX_BATCH * KSTALE2) + (q & 1) * MAX_BATCH;
             const int sp = N > 0 && !batches[q].ds ? select_parts(N, batches[q].pods, KSTALE2) : 1;
             if (d->fix_merge && sp > 1)  // the select left its parts unmerged in the split buffer: the fix merges them
-              hipLaunchKernelGGL((ext ? k_fixlist<true, true> : k_fixlist<false, true>), dim3((unsigned)batches[q].pods),
+              hipLaunchKernelGGL((ns ? (ext ? k_fixlist<true, true, true> : k_fixlist<false, true, true>)
+                                     : (ext ? k_fixlist<true, true> : k_fixlist<false, true>)), dim3((unsigned)batches[q].pods),
                                  dim3(FIXL_PARTS_BLOCK), 0, es, d->soa, d->d_pods, d_bases + q, k,
                                  alt ? d->d_split2 : d->d_split, nullptr, d_tlist + ((q - 2) & 1) * (1 + MAX_BATCH),
                                  q - 2 >= r0 ? d_done + (q - 2) : nullptr,
                                  d->d_stale + (size_t)(q & 1) * MAX_BATCH * KSTALE, d->d_stale_cnt + (q & 1) * MAX_BATCH,
                                  d_ready + q, d_err, (int64_t)gath_words(KSTALE2), sp);
             else
-              hipLaunchKernelGGL((ext ? k_fixlist<true> : k_fixlist<false>), dim3((unsigned)batches[q].pods), dim3(FIXL_BLOCK),
+              hipLaunchKernelGGL((ns ? (ext ? k_fixlist<true, false, true> : k_fixlist<false, false, true>)
+                                     : (ext ? k_fixlist<true> : k_fixlist<false>)), dim3((unsigned)batches[q].pods), dim3(FIXL_BLOCK),
                                  0, es, d->soa, d->d_pods, d_bases + q, k, pre, pre_cnt,
                                  d_tlist + ((q - 2) & 1) * (1 + MAX_BATCH), q - 2 >= r0 ? d_done + (q - 2) : nullptr,
                                  d->d_stale + (size_t)(q & 1) * MAX_BATCH * KSTALE, d->d_stale_cnt + (q & 1) * MAX_BATCH,
@@ -8375,7 +8506,8 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
         }
         rc = eval_select(q, true, d->estream);
         if (rc) return rc;
-        hipLaunchKernelGGL((ext ? k_fixup<true> : k_fixup<false>), dim3((unsigned)batches[q].pods), dim3(FIX_BLOCK), 0, d->estream, d->soa, d->d_pods,
+        hipLaunchKernelGGL((ns ? (ext ? k_fixup<true, true> : k_fixup<false, true>) : (ext ? k_fixup<true> : k_fixup<false>)),
+                           dim3((unsigned)batches[q].pods), dim3(FIX_BLOCK), 0, d->estream, d->soa, d->d_pods,
                            d_bases + q, k, d->d_stale + (size_t)(q & 1) * MAX_BATCH * KSTALE,
                            d->d_stale_cnt + (q & 1) * MAX_BATCH, d->d_trows, d->d_tcnt, d->d_cand, d->d_cand_cnt,
                            d_done, first ? -1 : q - 1, d_ready + q, d_err, d_fst + 2 * q);
@@ -8426,7 +8558,8 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
       auto resolve = quota ? (ds ? (numa ? k_resolve<true, true, true> : k_resolve<true, false, true>)
                                  : (numa ? k_resolve<false, true, true> : k_resolve<false, false, true>))
                            : (ds ? (numa ? k_resolve<true, true, false> : k_resolve<true, false, false>)
-                                 : (numa ? k_resolve<false, true, false> : k_resolve<false, false, false>));
+                                 : (numa ? k_resolve<false, true, false>
+                                         : ns ? k_resolve<false, false, false, true> : k_resolve<false, false, false>));
       hipLaunchKernelGGL(resolve, dim3(1), dim3(numa ? res_threads<true>() : res_threads<false>()), 0, d->stream, d->soa, d->d_pods, bbase, bp, k,
                          d->d_cand, d->d_cand_cnt, d->d_chosen, d->d_chosen_score, ctx->cfg.global_node_offset,
                          d->d_stamps, d->d_stamps + (n_pods + 2), b, d->d_devalloc, d->d_numaalloc, d->d_chg, N,

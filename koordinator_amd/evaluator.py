@@ -18,6 +18,36 @@ class KoordEvalError(RuntimeError):
         self.code = code
 
 
+def pack_node_sets(sets, n_nodes=None):
+    """Node sets -> (n_sets, words_per_set, uint64 words) for ke_node_sets_load: `sets` is a bool [n_sets, N] matrix
+    or a list of node index arrays (then N = n_nodes, default 1 + the highest index).  Bit i & 63 of word i >> 6 of a
+    set's row = node i; the tail bits of the last word are zero."""
+    if isinstance(sets, np.ndarray) and sets.ndim == 2:
+        m = np.ascontiguousarray(sets, dtype=bool)
+    else:
+        idx = [np.asarray(x, np.int64).reshape(-1) for x in sets]
+        if n_nodes is None:
+            n_nodes = max([int(x.max()) + 1 for x in idx if len(x)], default=0)
+        m = np.zeros((len(idx), n_nodes), bool)
+        for r, x in enumerate(idx):
+            if len(x) and (x.min() < 0 or x.max() >= n_nodes):
+                raise ValueError("node index outside 0..n_nodes")
+            m[r, x] = True
+    n_sets, n = m.shape
+    wps = (n + 63) // 64
+    padded = np.zeros((n_sets, wps * 64), np.uint8)
+    padded[:, :n] = m
+    words = np.packbits(padded, axis=1, bitorder="little").view("<u8").reshape(n_sets, wps)
+    return n_sets, wps, np.ascontiguousarray(words, np.uint64)
+
+
+def unpack_node_sets(words, n_nodes):
+    """The bool [n_sets, n_nodes] matrix of pack_node_sets' words."""
+    w = np.ascontiguousarray(words, "<u8")
+    bits = np.unpackbits(w.view(np.uint8).reshape(w.shape[0], -1), axis=1, bitorder="little")
+    return bits[:, :n_nodes].astype(bool)
+
+
 def as_pod_array(pods):
     """list[abi.Pod] | np.ndarray(POD_DTYPE) -> contiguous np.ndarray(POD_DTYPE)."""
     if isinstance(pods, np.ndarray):
@@ -188,6 +218,22 @@ class Evaluator:
                                    else np.zeros(0, np.int32), np.int32)
         self._check(self.lib.ke_pod_reservations(self.h, len(matches), abi.ptr(off), abi.ptr(ids)))
 
+    def node_sets_load(self, sets, n_nodes=None):
+        """ke_node_sets_load: replace the node eligibility sets (pack_node_sets' inputs); set ids are 1 + the row.
+        An empty list drops the table."""
+        n_sets, wps, words = pack_node_sets(sets, n_nodes)
+        self._check(self.lib.ke_node_sets_load(self.h, n_sets, wps, abi.ptr(words) if n_sets else None))
+
+    def node_set_bits(self, node, member):
+        """ke_node_set_bits: node `node`'s membership in every loaded set (member[s - 1] for set id s)."""
+        m = np.ascontiguousarray(np.asarray(member).astype(bool), np.uint8)
+        self._check(self.lib.ke_node_set_bits(self.h, int(node), len(m), abi.ptr(m)))
+
+    def pod_node_sets(self, set_ids):
+        """ke_pod_node_sets: the set id (0 = every node) per pod of the next eval / schedule / submit."""
+        ids = np.ascontiguousarray(set_ids, np.int32)
+        self._check(self.lib.ke_pod_node_sets(self.h, len(ids), abi.ptr(ids)))
+
     def node_info_requested(self, i):
         """ke_node_info_requested: NodeInfo Requested / NonZeroRequested (MilliCPU, Memory) after the restore."""
         req, nz = (C.c_int64 * 2)(), (C.c_int64 * 2)()
@@ -271,8 +317,11 @@ class Evaluator:
         return lo.value, hi.value
 
     # ---- evaluation -------------------------------------------------------------------------
-    def eval(self, pods, now_ns):
+    def eval(self, pods, now_ns, node_sets=None):
+        """ke_eval; `node_sets` (optional): the node set id per pod (0 = every node)."""
         pods = as_pod_array(pods)
+        if node_sets is not None:
+            self.pod_node_sets(node_sets)
         P, N = len(pods), self.num_nodes
         out = {
             "status": np.zeros((P, N), np.uint8),
@@ -288,21 +337,26 @@ class Evaluator:
                                      abi.ptr(out["ds"]), abi.ptr(out["total"]), abi.ptr(out["best"])))
         return out
 
-    def schedule(self, pods, now_ns, matches=None):
-        """ke_schedule; `matches` (optional): per pod the reservation indices it matches (KE_RSV_MATCHED pods)."""
+    def schedule(self, pods, now_ns, matches=None, node_sets=None):
+        """ke_schedule; `matches` (optional): per pod the reservation indices it matches (KE_RSV_MATCHED pods);
+        `node_sets` (optional): the node set id per pod (0 = every node)."""
         pods = as_pod_array(pods)
         if matches is not None:
             self.pod_reservations(matches)
+        if node_sets is not None:
+            self.pod_node_sets(node_sets)
         chosen = np.zeros(len(pods), np.int32)
         score = np.zeros(len(pods), np.int32)
         self._check(self.lib.ke_schedule(self.h, len(pods), abi.ptr(pods), int(now_ns), abi.ptr(chosen), abi.ptr(score)))
         self._last_n, self._last_out = len(pods), {}  # the per-pod allocations are read on first access
         return chosen, score
 
-    def submit(self, pods, now_ns):
+    def submit(self, pods, now_ns, node_sets=None):
         """ke_schedule_submit: enqueue a queue slice behind the calls in flight; returns its ticket (wait() collects
-        it).  The pod array is kept alive here until then."""
+        it).  The pod array is kept alive here until then.  `node_sets` as for schedule()."""
         pods = as_pod_array(pods)
+        if node_sets is not None:
+            self.pod_node_sets(node_sets)
         t = C.c_int64()
         self._check(self.lib.ke_schedule_submit(self.h, len(pods), abi.ptr(pods), int(now_ns), C.byref(t)))
         self._inflight[t.value] = pods
