@@ -1266,6 +1266,14 @@ int ke_debug_kernel_phases(ke_ctx* ctx, int32_t kernel, double* cyc8);
 /* Speculative replay of plain batches: rounds per batch of the last ke_schedule that ended at a
  * failed prediction (0 = every pod of the batch took its best candidate not taken before). */
 int ke_debug_spec_failed(ke_ctx* ctx, double* per_batch);
+/* The boundary between the last completed device call and the call before it.  out4[0]: batches
+ * whose eval was enqueued ahead of the previous call's end (always 0 today: every call starts behind the previous
+ * one's last Reserve); out4[1] / out4[2]: copies / fills the call enqueued on the Reserve stream between its pod
+ * upload and its read-back, counted on the host (a plain call: 3 and 0; a row refresh's uploads are not counted);
+ * out4[3]: nanoseconds from the previous call's last batch end to this call's first Reserve prologue, both
+ * stamped on the device; 0 unless ke_schedule_submit enqueued the call behind one still in flight.
+ * Additive: KE_ABI_VERSION stays 14, no struct or existing entry point changes. */
+int ke_debug_call_boundary(ke_ctx* ctx, int64_t* out4);
 /* Number of nodes whose replay record (the Reserve replay's row-major copy of the node-only terms)
  * differs from one derived from the node's current device row (0 = consistent). */
 int ke_debug_check_records(ke_ctx* ctx, int64_t now_ns, int64_t* mismatched_nodes);

@@ -593,6 +593,7 @@ EXPORTS = {
     "ke_debug_ds_cuts": (C.c_int, [C.c_void_p, C.POINTER(i32)]),
     "ke_debug_rsv_fused": (C.c_int, [C.c_void_p, C.POINTER(i64)]),
     "ke_debug_spec_failed": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "ke_debug_call_boundary": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ke_bench_eval_kernel": (C.c_int, [C.c_void_p, i32, C.c_void_p, i64, i32, C.POINTER(C.c_double)]),
     "ke_row_bytes": (C.c_int, []),
     "ke_pod_record_bytes": (C.c_int, []),

@@ -1366,6 +1366,7 @@ int ke_schedule_submit(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t 
       a.pods = pods;
       a.now = now_ns;
       a.device = true;
+      c.call_behind = in_flight > 0;
       rc = device_schedule_enqueue(&c, n_pods, pods, now_ns, true, &a.fin);
       if (rc) {
         // the call in flight keeps the buffers its completion captured: swap back, and let no partly enqueued
@@ -1575,6 +1576,12 @@ int ke_debug_kernel_phases(ke_ctx* ctx, int32_t kernel, double* cyc8) {
 int ke_debug_spec_failed(ke_ctx* ctx, double* per_batch) {
   if (!ctx || !per_batch) return fail(KE_ERR_INVALID, "ke_debug_spec_failed arguments");
   *per_batch = ctx->c.kstat_spec_failed;
+  return KE_OK;
+}
+
+int ke_debug_call_boundary(ke_ctx* ctx, int64_t* out4) {
+  if (!ctx || !out4) return fail(KE_ERR_INVALID, "ke_debug_call_boundary arguments");
+  for (int i = 0; i < 4; i++) out4[i] = ctx->c.call_boundary[i];
   return KE_OK;
 }
 

@@ -157,6 +157,11 @@ struct Context {
   std::vector<double> last_batch_ms;
   double kstat_eval_ms = 0, kstat_select_ms = 0, kstat_resolve_ms = 0, kstat_fixup_ms = 0, kstat_handoff_ms = 0;
   int32_t last_pipelined = 0;
+  // ke_debug_call_boundary of the last completed device call; call_behind: the call being enqueued follows one
+  // still in flight (ke_schedule_submit sets it); prev_end_tick: the last completed call's final batch end stamp
+  int64_t call_boundary[4] = {0, 0, 0, 0};
+  bool call_behind = false;
+  uint64_t prev_end_tick = 0;
   int32_t last_ds_cuts = 0;  // DeviceShare batches of the last ke_schedule that stopped early (re-run remainders)
   double kstat_spec_failed = 0;  // per batch: speculative-replay rounds that ended at a failed prediction
   double kstat_rows_fetched = 0, kstat_rows_changed = 0;  // per batch: replay records fetched (best unchanged candidates), rows changed

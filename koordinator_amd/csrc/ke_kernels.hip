@@ -6842,7 +6842,17 @@ __global__ __launch_bounds__(64) void k_cpuset_reserve(SoA s, const DevPod* __re
   }
 }
 
-__global__ void k_stamp(uint64_t* stamps) { stamps[0] = __builtin_amdgcn_s_memrealtime(); }
+// Start of a ke_schedule call on the Reserve stream, one launch for what were fills: zeroes the call's
+// hand-off words (a), its error word and fixup stamps (b) and, in a call with a cpuset pod, the cpuset table
+// (c, else nc == 0), and writes the call's start stamp.  The grid covers the longest of the three.
+__global__ void k_call_begin(uint32_t* __restrict__ a, int64_t na, uint32_t* __restrict__ b, int64_t nb,
+                             uint32_t* __restrict__ c, int64_t nc, uint64_t* __restrict__ stamps) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < na) a[i] = 0;
+  if (i < nb) b[i] = 0;
+  if (i < nc) c[i] = 0;
+  if (i == 0) stamps[0] = __builtin_amdgcn_s_memrealtime();
+}
 // start of a batch on its eval stream: the eval-start stamp, and the zeroed atomicMax targets of a
 // DeviceShare batch (NormalizeScore's max) and of a one-pod argmax (one launch instead of three)
 __global__ void k_batch_begin(uint64_t* stamp, uint32_t* dsb, uint32_t* argmax) {  // 64 threads
@@ -6872,17 +6882,19 @@ struct PinnedVec {
   ~PinnedVec() {
     if (p) (void)hipHostFree(p);
   }
-  bool resize(size_t m) {  // contents not kept when it grows
-    if (m > cap) {
+  // contents not kept when it grows; tail_bytes: room behind the m elements (not part of size())
+  bool resize(size_t m, size_t tail_bytes = 0) {
+    const size_t need = m + (tail_bytes + sizeof(T) - 1) / sizeof(T);
+    if (need > cap) {
       if (p) (void)hipHostFree(p);
       p = nullptr;
       cap = 0;
-      if (hipHostMalloc((void**)&p, sizeof(T) * std::max<size_t>(m, 1), hipHostMallocDefault) != hipSuccess) {
+      if (hipHostMalloc((void**)&p, sizeof(T) * std::max<size_t>(need, 1), hipHostMallocDefault) != hipSuccess) {
         p = nullptr;
         n = 0;
         return false;
       }
-      cap = m;
+      cap = need;
     }
     n = m;
     return true;
@@ -6918,10 +6930,9 @@ struct DeviceState {
   DevPodHint* d_ph = nullptr;  // the hinted pods' records of the current call
   int64_t ph_cap = 0;
   // node eligibility sets: rows 0 .. ns_n of capacity / 64 words (row 0 all ones); a call's set ids
-  // lie behind its DevPod records in d_pods (one per buffer set), staged page-locked in host_ns
+  // lie behind its DevPod records in d_pods (one per buffer set), staged alike behind host_pods (upload_pods)
   uint64_t* d_ns_tbl = nullptr;
   int64_t ns_tbl_cap = 0;
-  PinnedVec<int32_t> host_ns;
   int8_t* d_vfo = nullptr;     // [n_pods][2][DS_MINORS] VF ranks of the Reserves
   int64_t vfo_cap = 0;
   // batch buffers
@@ -6929,12 +6940,12 @@ struct DeviceState {
   uint32_t* d_cand = nullptr;    // [MAX_BATCH][KMAX]
   int32_t* d_cand_cnt = nullptr;
   int32_t* d_batch_base = nullptr;  // a zero word (batch base of the parity / bench launches)
-  int32_t* d_sched = nullptr;       // ke_schedule bookkeeping: batch bases, hand-off flags, fixup stamps
+  int32_t* d_sched = nullptr;       // ke_schedule bookkeeping: hand-off flags, the T helpers' lists
   int64_t sched_cap = 0;            // bytes
-  int32_t* d_chosen = nullptr;
-  int32_t* d_chosen_score = nullptr;
-  uint64_t* d_stamps = nullptr;
-  int64_t out_cap = 0;
+  // ke_schedule's read-back block (OutLayout): scores, placements, the call's error word, fixup stamps and the
+  // batch stamps, contiguous in the order the completion reads them, so one copy brings them to h_out
+  uint8_t* d_out = nullptr;
+  int64_t out_cap = 0;              // pods (d_out, d_devalloc, d_numaalloc)
   // parity outputs
   void* d_parity = nullptr;
   int64_t parity_cap = 0;
@@ -7002,11 +7013,9 @@ struct DeviceState {
   // the other call's buffers of two in flight (ke_schedule_submit): swapped with the fields of the same name
   struct CallBufs {
     PinnedVec<DevPod> host_pods;
-    PinnedVec<int32_t> host_ns;
     DevPod* d_pods = nullptr;
     int64_t pods_cap = 0;
-    int32_t *d_chosen = nullptr, *d_chosen_score = nullptr;
-    uint64_t* d_stamps = nullptr;
+    uint8_t* d_out = nullptr;
     uint64_t* d_devalloc = nullptr;
     int64_t* d_numaalloc = nullptr;
     int64_t out_cap = 0;
@@ -7272,8 +7281,8 @@ void device_destroy(Context* ctx) {
   if (d->stream) (void)hipStreamSynchronize(d->stream);
   if (d->comm) (void)ncclCommDestroy(d->comm);
   void* ptrs[] = {d->soa.f,     d->soa.flags, d->d_rows,      d->d_idx,          d->d_pods,   d->d_scores,
-                  d->d_cand,    d->d_cand_cnt, d->d_batch_base, d->d_chosen,     d->d_chosen_score,
-                  d->d_stamps,  d->d_parity, d->d_best,       d->d_gath,    d->d_split,         d->soa.ds,   d->soa.dsm,
+                  d->d_cand,    d->d_cand_cnt, d->d_batch_base, d->d_out,
+                  d->d_parity, d->d_best,      d->d_gath,    d->d_split,         d->soa.ds,   d->soa.dsm,
                   d->d_dsraw,   d->d_dsmax,  d->d_devalloc,   d->d_dsrows,       d->soa.nf,   d->soa.nm,
                   d->d_numaalloc, d->d_numarows, d->d_defer, d->d_defer_cnt, d->soa.cs, d->soa.cpu,
                   d->d_cpurows, d->d_cpusets, d->d_aff, d->soa.qt, d->soa.qm, d->d_sched, d->d_stale,
@@ -7299,8 +7308,7 @@ void device_destroy(Context* ctx) {
   if (d->ev_sel2) (void)hipEventDestroy(d->ev_sel2);
   for (auto& e : d->tev) (void)hipEventDestroy(e);
   for (auto& e : d->alt.tev) (void)hipEventDestroy(e);
-  for (void* p : {(void*)d->alt.d_pods, (void*)d->alt.d_chosen, (void*)d->alt.d_chosen_score, (void*)d->alt.d_stamps,
-                  (void*)d->alt.d_devalloc, (void*)d->alt.d_numaalloc, (void*)d->alt.d_cpusets, (void*)d->alt.d_sched})
+  for (void* p : {(void*)d->alt.d_pods, (void*)d->alt.d_out, (void*)d->alt.d_devalloc, (void*)d->alt.d_numaalloc, (void*)d->alt.d_cpusets, (void*)d->alt.d_sched})
     if (p) (void)hipFree(p);
   if (d->stream) (void)hipStreamDestroy(d->stream);
   delete d;
@@ -7823,11 +7831,20 @@ static int node_sets_sync(Context* ctx) {
   return KE_OK;
 }
 
-static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, hipStream_t ustream = nullptr) {
+// The call's upload block: the DevPod records, the node set ids when present (int32 each) and room for
+// tail_words more int32 words, laid out alike in the page-locked host_pods and in d_pods, so one copy carries
+// it.  Without `tail` the block is copied here; with it the caller fills *tail (ke_schedule's batch bases) and
+// copies *block_bytes itself.  *copies counts the copies enqueued on ustream.
+static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, hipStream_t ustream = nullptr,
+                       int64_t tail_words = 0, int32_t** tail = nullptr, int64_t* block_bytes = nullptr,
+                       int* copies = nullptr) {
   DeviceState* d = ctx->dev;
   if (!ustream) ustream = d->stream;
   PinnedVec<DevPod>& dp = d->host_pods;
-  if (!dp.resize((size_t)n_pods)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the pod staging buffer");
+  const int32_t* ns = ctx->ns_call;  // the call's node set ids (a non-zero one among them): behind the records
+  const int64_t ns_words = ns ? (int64_t)n_pods : 0;
+  if (!dp.resize((size_t)n_pods, sizeof(int32_t) * (size_t)(ns_words + tail_words)))
+    return fail(KE_ERR_DEVICE, "hipHostMalloc of the pod staging buffer");
   std::vector<DevPodHint>& ph = d->host_ph;  // the hinted pods' records; DevPod::ring_bw = slot
   ph.clear();
   // the argument checks of this call staged the records (check_cpuset); pods may be a segment of them
@@ -7844,23 +7861,26 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, hipStre
       dp[p].ring_bw = (int64_t)ph.size() - 1;
     }
   }
-  const int32_t* ns = ctx->ns_call;  // the call's node set ids (a non-zero one among them): behind the records
-  int rc = ensure((void**)&d->d_pods, &d->pods_cap,
-                  sizeof(DevPod) * (int64_t)std::max(n_pods, 1) + (ns ? sizeof(int32_t) * (int64_t)n_pods : 0));
+  const int64_t bytes = sizeof(DevPod) * (int64_t)n_pods + sizeof(int32_t) * (ns_words + tail_words);
+  int rc = ensure((void**)&d->d_pods, &d->pods_cap, std::max<int64_t>(bytes, (int64_t)sizeof(DevPod)));
   if (rc) return rc;
-  HIP_OK(hipMemcpyAsync(d->d_pods, dp.data(), sizeof(DevPod) * n_pods, hipMemcpyHostToDevice, ustream));
+  int32_t* const h_words = reinterpret_cast<int32_t*>(dp.data() + n_pods);
   d->soa.ns_ids = nullptr;
   if (ns) {
-    if (!d->host_ns.resize((size_t)n_pods)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the node set id staging buffer");
-    std::copy(ns, ns + n_pods, d->host_ns.data());
-    int32_t* d_ids = reinterpret_cast<int32_t*>(d->d_pods + n_pods);
-    HIP_OK(hipMemcpyAsync(d_ids, d->host_ns.data(), sizeof(int32_t) * n_pods, hipMemcpyHostToDevice, ustream));
-    d->soa.ns_ids = d_ids;
+    std::copy(ns, ns + n_pods, h_words);
+    d->soa.ns_ids = reinterpret_cast<int32_t*>(d->d_pods + n_pods);
+  }
+  if (tail) *tail = h_words + ns_words;
+  if (block_bytes) *block_bytes = bytes;
+  if (!tail && bytes) {
+    HIP_OK(hipMemcpyAsync(d->d_pods, dp.data(), (size_t)bytes, hipMemcpyHostToDevice, ustream));
+    if (copies) ++*copies;
   }
   if (!ph.empty()) {
     rc = ensure((void**)&d->d_ph, &d->ph_cap, sizeof(DevPodHint) * (int64_t)ph.size());
     if (rc) return rc;
     HIP_OK(hipMemcpyAsync(d->d_ph, ph.data(), sizeof(DevPodHint) * ph.size(), hipMemcpyHostToDevice, ustream));
+    if (copies) ++*copies;
   }
   d->soa.ph = d->d_ph;
   // no host wait: the kernels run on d->stream after the copies, and the eval stream waits for ev_start,
@@ -7961,12 +7981,9 @@ void device_swap_call_buffers(Context* ctx) {
   DeviceState* d = ctx->dev;
   DeviceState::CallBufs& a = d->alt;
   d->host_pods.swap(a.host_pods);
-  d->host_ns.swap(a.host_ns);
   std::swap(d->d_pods, a.d_pods);
   std::swap(d->pods_cap, a.pods_cap);
-  std::swap(d->d_chosen, a.d_chosen);
-  std::swap(d->d_chosen_score, a.d_chosen_score);
-  std::swap(d->d_stamps, a.d_stamps);
+  std::swap(d->d_out, a.d_out);
   std::swap(d->d_devalloc, a.d_devalloc);
   std::swap(d->d_numaalloc, a.d_numaalloc);
   std::swap(d->out_cap, a.out_cap);
@@ -8011,6 +8028,7 @@ bool device_async_ok(const Context* ctx, int32_t n_pods) {
 
 int device_schedule(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, int32_t* chosen, int32_t* score) {
   DevFinish fin;
+  ctx->call_behind = false;  // (every earlier call has completed)
   const int rc = device_schedule_enqueue(ctx, n_pods, pods, now, score != nullptr, &fin);
   if (rc || !fin) return rc;
   return fin(chosen, score);
@@ -8042,8 +8060,24 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
     rc = node_sets_sync(ctx);
     if (rc) return rc;
   }
-  rc = upload_pods(ctx, n_pods, pods, cs);
+  // host-counted copies / fills this call enqueues on the Reserve stream (ke_debug_call_boundary)
+  int n_copies = 0, n_fills = 0;
+  auto copy_async = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    n_copies += s == d->stream;
+    return hipMemcpyAsync(dst, src, bytes, kind, s);
+  };
+  auto fill_async = [&](void* dst, int v, size_t bytes, hipStream_t s) {
+    n_fills += s == d->stream;
+    return hipMemsetAsync(dst, v, bytes, s);
+  };
+  // the upload block: records, node set ids, then the batch bases (at most one batch per pod, and the end);
+  // copied once the bases are known
+  int32_t* h_bases = nullptr;
+  int64_t upload_bytes = 0;
+  int ph_copies = 0;
+  rc = upload_pods(ctx, n_pods, pods, cs, (int64_t)n_pods + 1, &h_bases, &upload_bytes, &ph_copies);
   if (rc) return rc;
+  n_copies += cs == d->stream ? ph_copies : 0;
   ctx->host_ms[2] = ms_since(tp);
   tp = clk::now();
   // Batches: runs of up to B pods without DeviceShare requests (exact speculative batching, DESIGN.md
@@ -8089,29 +8123,54 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
   if (any_cpu && !d->cpu_alloc) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
   const int n_batches = (int)batches.size();
   const int64_t out_bytes = sizeof(int32_t) * (int64_t)n_pods;
+  // The read-back block, device and h_out alike (16-byte aligned parts): scores, placements, the call's error
+  // word, the fixup stamps [2 nb], the batch end stamps [nb + 1] (st[0]: the call's start), the replay stamps
+  // [PST nb], the eval start stamps [nb] -- and, not read back, one more eval stamp (a re-run remainder's)
+  struct OutLayout {
+    size_t score, chosen, err, fst, st, pst, est, end, total;
+    OutLayout(size_t np, size_t nb) {
+      size_t off = 0;
+      auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off = (off + bytes + 15) & ~(size_t)15;
+        return o;
+      };
+      score = take(4 * np), chosen = take(4 * np), err = take(8), fst = take(16 * nb), st = take(8 * (nb + 1));
+      pst = take(8 * PST * nb), est = take(8 * nb);
+      end = est + 8 * nb;
+      total = est + 8 * (nb + 1);
+    }
+  };
   if (d->out_cap < n_pods) {
-    if (d->d_chosen) HIP_OK(hipFree(d->d_chosen));
-    if (d->d_chosen_score) HIP_OK(hipFree(d->d_chosen_score));
-    if (d->d_stamps) HIP_OK(hipFree(d->d_stamps));
+    if (d->d_out) HIP_OK(hipFree(d->d_out));
     if (d->d_devalloc) HIP_OK(hipFree(d->d_devalloc));
     if (d->d_numaalloc) HIP_OK(hipFree(d->d_numaalloc));
+    d->d_out = nullptr;
+    d->d_devalloc = nullptr;
     d->d_numaalloc = nullptr;
-    HIP_OK(hipMalloc(&d->d_chosen, out_bytes));
-    HIP_OK(hipMalloc(&d->d_chosen_score, out_bytes));
-    HIP_OK(hipMalloc(&d->d_stamps, sizeof(uint64_t) * (PST + 2) * ((int64_t)n_pods + 2)));
+    d->out_cap = 0;
+    HIP_OK(hipMalloc(&d->d_out, OutLayout((size_t)n_pods, (size_t)n_pods).total));  // (n_batches <= n_pods)
     HIP_OK(hipMalloc(&d->d_devalloc, sizeof(uint64_t) * n_pods));
     d->out_cap = n_pods;
   }
+  const OutLayout ol((size_t)n_pods, (size_t)n_batches);
+  int32_t* const d_chosen = reinterpret_cast<int32_t*>(d->d_out + ol.chosen);
+  int32_t* const d_chosen_score = reinterpret_cast<int32_t*>(d->d_out + ol.score);
+  int32_t* const d_err = reinterpret_cast<int32_t*>(d->d_out + ol.err);
+  uint64_t* const d_fst = reinterpret_cast<uint64_t*>(d->d_out + ol.fst);
+  uint64_t* const d_st = reinterpret_cast<uint64_t*>(d->d_out + ol.st);
+  uint64_t* const d_pst = reinterpret_cast<uint64_t*>(d->d_out + ol.pst);
+  // (every singleton batch's k_cpuset_reserve writes its pod's entry; the table is read back, and so zeroed by
+  // k_call_begin, only in a call with a cpuset pod)
   rc = ensure((void**)&d->d_cpusets, &d->cpusets_cap, sizeof(uint64_t) * 4 * (int64_t)n_pods);
   if (rc) return rc;
-  HIP_OK(hipMemsetAsync(d->d_cpusets, 0, sizeof(uint64_t) * 4 * n_pods, cs));
   bool any_hint = false;
   for (const DevPod& q : d->host_pods) any_hint = any_hint || (q.flags & PF_DS_HINT);
   d->soa.vfo = nullptr;
   if (any_hint) {  // the VF ranks the hinted pods' Reserves take
     rc = ensure((void**)&d->d_vfo, &d->vfo_cap, 2 * DS_MINORS * (int64_t)n_pods);
     if (rc) return rc;
-    HIP_OK(hipMemsetAsync(d->d_vfo, 0xFF, 2 * DS_MINORS * (size_t)n_pods, d->stream));
+    HIP_OK(fill_async(d->d_vfo, 0xFF, 2 * DS_MINORS * (size_t)n_pods, d->stream));
     d->soa.vfo = d->d_vfo;
   }
   const bool numa = d->numa_alloc;
@@ -8121,7 +8180,7 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
     if (rc) return rc;
     rc = ensure((void**)&d->d_defer_cnt, &d->defer_cnt_cap, sizeof(uint32_t) * n_batches);
     if (rc) return rc;
-    HIP_OK(hipMemsetAsync(d->d_defer_cnt, 0, sizeof(uint32_t) * n_batches, d->stream));
+    HIP_OK(fill_async(d->d_defer_cnt, 0, sizeof(uint32_t) * n_batches, d->stream));
   }
   KArgs k = make_kargs(ctx, now);
   if (ctx->rsv_affinity) k.flags |= AF_RSV_ONLY;  // the Reservation Filter: RsvOvr.rfilter of the pod's nodes
@@ -8146,16 +8205,16 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
   if (!ctx->rsv_pairs.empty() || ctx->rsv_affinity) {
     if (rsv_bytes) {
       std::memcpy(d->h_rsv.data(), ctx->rsv_pairs.data(), rsv_bytes);
-      HIP_OK(hipMemcpyAsync(d->d_rsv, d->h_rsv.data(), rsv_bytes, hipMemcpyHostToDevice, d->stream));
+      HIP_OK(copy_async(d->d_rsv, d->h_rsv.data(), rsv_bytes, hipMemcpyHostToDevice, d->stream));
     }
-    HIP_OK(hipMemsetAsync(d->d_rsv_out, 0xFF, sizeof(int32_t) * 4, d->stream));
+    HIP_OK(fill_async(d->d_rsv_out, 0xFF, sizeof(int32_t) * 4, d->stream));
   }
   d->soa.n_rovr = 0;  // a matched pod's allocate-from-reservation decisions (NF_RSV_CS rows read them)
   if (!ctx->rsv_ovr.empty()) {
     rc = ensure((void**)&d->d_rovr, &d->rovr_cap, (int64_t)sizeof(RsvOvr) * (int64_t)ctx->rsv_ovr.size());
     if (rc) return rc;
     std::memcpy(d->h_rsv.data() + rsv_bytes, ctx->rsv_ovr.data(), ovr_bytes);
-    HIP_OK(hipMemcpyAsync(d->d_rovr, d->h_rsv.data() + rsv_bytes, ovr_bytes, hipMemcpyHostToDevice, d->stream));
+    HIP_OK(copy_async(d->d_rovr, d->h_rsv.data() + rsv_bytes, ovr_bytes, hipMemcpyHostToDevice, d->stream));
     d->soa.rovr = d->d_rovr;
     d->soa.n_rovr = (int32_t)ctx->rsv_ovr.size();
   }
@@ -8192,28 +8251,27 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
     if (e - b >= 2) run_end[b] = e;
     b = e;
   }
-  // device: bases [n+1], ready [n], done [n], error word, T-helper counts [n], select-started counts [n], the
-  // Reserve kernels' residency flags [n] (by run start); fixup stamps [2n]; the T helpers' lists and maxima (THelp)
-  const int64_t sched_words = 6 * ((int64_t)n_batches + 1) + 1;
+  // d_sched: ready [n], done [n], T-helper counts [n], select-started counts [n], the Reserve kernels' residency
+  // flags [n] (by run start), each with a spare word; the T helpers' lists and maxima (THelp).  The batch bases
+  // [n+1] lie in the upload block behind the records (and node set ids); the error word and the fixup stamps in
+  // the read-back block.
+  const int64_t sched_words = (5 * ((int64_t)n_batches + 1) + 1) & ~1LL;  // (the lists behind stay 8-byte aligned)
   constexpr int64_t THELP_WORDS = 2 * (1 + MAX_BATCH) + 2 * MAX_BATCH;
-  rc = ensure((void**)&d->d_sched, &d->sched_cap,
-              sizeof(int32_t) * sched_words + sizeof(uint64_t) * 2 * n_batches + 8 + sizeof(int32_t) * THELP_WORDS);
+  rc = ensure((void**)&d->d_sched, &d->sched_cap, sizeof(int32_t) * (sched_words + THELP_WORDS));
   if (rc) return rc;
-  int32_t* d_bases = d->d_sched;
-  int32_t* d_ready = d_bases + n_batches + 1;
+  int32_t* d_bases = reinterpret_cast<int32_t*>(d->d_pods + n_pods) + (ns ? n_pods : 0);
+  int32_t* d_ready = d->d_sched;
   int32_t* d_done = d_ready + n_batches + 1;
-  int32_t* d_err = d_done + n_batches + 1;
-  int32_t* d_tready = d_err + 1;
+  int32_t* d_tready = d_done + n_batches + 1;
   int32_t* d_sstart = d_tready + n_batches + 1;
   int32_t* d_rres = d_sstart + n_batches + 1;
-  uint64_t* d_fst = reinterpret_cast<uint64_t*>(d->d_sched + ((sched_words + 1) & ~1LL));
-  int32_t* d_tlist = reinterpret_cast<int32_t*>(d_fst + 2 * n_batches);
+  int32_t* d_tlist = d->d_sched + sched_words;
   uint32_t* d_tmx = reinterpret_cast<uint32_t*>(d_tlist + 2 * (1 + MAX_BATCH));
-  // (the call's own words, on its staging stream; the error word and the split selects' counters stay zero
-  // between calls -- an aborted call resets them)
-  HIP_OK(hipMemcpyAsync(d_bases, bases.data(), sizeof(int32_t) * (n_batches + 1), hipMemcpyHostToDevice, cs));
-  HIP_OK(hipMemsetAsync(d_ready, 0, sizeof(int32_t) * (sched_words - n_batches - 1), cs));
-  HIP_OK(hipMemsetAsync(d_fst, 0, sizeof(uint64_t) * 2 * n_batches, cs));
+  const bool sharded = d->world > 1 || d->comm || d->host_fn;
+  // one copy for everything the call uploads (on its staging stream)
+  std::copy(bases.begin(), bases.end(), h_bases);
+  HIP_OK(copy_async(d->d_pods, d->host_pods.data(), (size_t)(upload_bytes - (int64_t)sizeof(int32_t) * (n_pods - n_batches)),
+                    hipMemcpyHostToDevice, cs));
   HIP_OK(hipEventRecord(d->ev_setup, cs));
   // sampled per-kernel HIP event pairs (ke_set_profiling) on the eval stream: eval, select
   constexpr int PE = 4;  // eval start, eval end, select end, select start (after k_patch and its wait)
@@ -8231,11 +8289,19 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
   std::vector<hipEvent_t> ev(d->tev.begin() + 5, d->tev.begin() + (long)n_tev);
   HIP_OK(hipStreamWaitEvent(d->stream, d->ev_setup, 0));
   HIP_OK(hipEventRecord(e0, d->stream));
-  hipLaunchKernelGGL(k_stamp, dim3(1), dim3(1), 0, d->stream, d->d_stamps);
+  {
+    // the call's own words start at zero: the hand-off words, the error word and the fixup stamps (adjacent in
+    // the read-back block), the cpuset table when a pod may bind CPUs; and the call's start stamp.  (The split
+    // selects' counters stay zero between calls -- an aborted call resets them.)
+    const int64_t nw_out = (int64_t)(ol.st - ol.err) / 4, nw_cs = any_cpu ? 8 * (int64_t)n_pods : 0;
+    const int64_t nw = std::max(std::max(sched_words, nw_out), nw_cs);
+    hipLaunchKernelGGL(k_call_begin, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, d->stream,
+                       reinterpret_cast<uint32_t*>(d->d_sched), sched_words, reinterpret_cast<uint32_t*>(d_err), nw_out,
+                       reinterpret_cast<uint32_t*>(d->d_cpusets), nw_cs, d_st);
+  }
   HIP_OK(hipEventRecord(d->ev_start, d->stream));
   HIP_OK(hipStreamWaitEvent(d->estream, d->ev_start, 0));
-  const bool sharded = d->world > 1 || d->comm || d->host_fn;
-  uint64_t* estamps = d->d_stamps + (PST + 1) * ((int64_t)n_pods + 2);  // eval start of each batch
+  uint64_t* estamps = reinterpret_cast<uint64_t*>(d->d_out + ol.est);  // eval start of each batch
   constexpr int R = DeviceState::EV_RING;
   int n_pipelined = 0;
   // Batch b's eval + candidate lists on stream `es`.  pipe: stale top-(k_j + KMAX) lists into the run's
@@ -8268,7 +8334,7 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
     // stamp (latency counts from there)
     const bool fold_begin = !ds && !argmax1 && !rerun && hi > lo;
     if (!fold_begin)
-      hipLaunchKernelGGL(k_batch_begin, dim3(1), dim3(MAX_BATCH), 0, es, estamps + (rerun ? n_pods + 1 : b), ds ? d->d_dsmax : nullptr,
+      hipLaunchKernelGGL(k_batch_begin, dim3(1), dim3(MAX_BATCH), 0, es, estamps + (rerun ? n_batches : b), ds ? d->d_dsmax : nullptr,
                          argmax1 ? d->d_cand : nullptr);
     // (with two eval streams the wait is a one-wave kernel ahead of the eval, outside its timing: an eval grid
     // spinning on the flag would hold the CUs the other stream's select needs)
@@ -8353,7 +8419,7 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
           hipLaunchKernelGGL(k_rsv_pick, dim3(1), dim3(64), 0, es, scores, d->d_rsv, (int)ctx->rsv_pairs.size(),
                              (int64_t)ctx->cfg.weight_reservation, (int)ctx->rsv_affinity, d->d_cand, d->d_rsv_out,
                              ds ? d->d_dsraw : nullptr, d->d_dsmax, k.wp_ds);
-          HIP_OK(hipMemcpyAsync(d->h_rsv_out.data(), d->d_rsv_out, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, es));
+          HIP_OK(copy_async(d->h_rsv_out.data(), d->d_rsv_out, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, es));
         }
       } else if (!sharded && parts > 1) {
         const int gw = gath_words(L);
@@ -8406,13 +8472,13 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
           hipLaunchKernelGGL(k_rsv_stage<4>, dim3(1), dim3(64), 0, es, scores, d->d_rsv, K, rlo, rhi, wr, aff, lists, st, d->d_rsv_out, rds, d->d_dsmax, k.wp_ds);
           if (coll && (crc = coll_all_reduce(d, &st->wt, 2, KE_COLL_I32, KE_COLL_MAX, es))) return crc;  // wt, nw
           hipLaunchKernelGGL(k_rsv_stage<5>, dim3(1), dim3(64), 0, es, scores, d->d_rsv, K, rlo, rhi, wr, aff, lists, st, d->d_rsv_out, rds, d->d_dsmax, k.wp_ds);
-          HIP_OK(hipMemcpyAsync(d->h_rsv_out.data(), d->d_rsv_out, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, es));
+          HIP_OK(copy_async(d->h_rsv_out.data(), d->d_rsv_out, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, es));
         }
       }
     } else {
       if (prof) HIP_OK(hipEventRecord(pe[1], es));
       if (prof) HIP_OK(hipEventRecord(pe[3], es));
-      HIP_OK(hipMemsetAsync(lists_cnt, 0, sizeof(int32_t) * MAX_BATCH, es));
+      HIP_OK(fill_async(lists_cnt, 0, sizeof(int32_t) * MAX_BATCH, es));
     }
     if (prof) HIP_OK(hipEventRecord(pe[2], es));
     return KE_OK;
@@ -8449,8 +8515,8 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
       hipLaunchKernelGGL((quota ? (ext ? k_resolve_run<true, true> : k_resolve_run<true, false>)
                           : ns  ? (ext ? k_resolve_run<false, true, true> : k_resolve_run<false, false, true>)
                                 : (ext ? k_resolve_run<false, true> : k_resolve_run<false, false>)), dim3(1 + th.H), dim3(res_threads<false>()), 0,
-                         d->stream, d->soa, d->d_pods, d_bases, r0, e - r0, k, d->d_cand, d->d_cand_cnt, d->d_chosen,
-                         d->d_chosen_score, ctx->cfg.global_node_offset, d->d_stamps, d->d_stamps + (n_pods + 2),
+                         d->stream, d->soa, d->d_pods, d_bases, r0, e - r0, k, d->d_cand, d->d_cand_cnt, d_chosen,
+                         d_chosen_score, ctx->cfg.global_node_offset, d_st, d_pst,
                          d->d_devalloc, d_ready, d_done, d_err, d->d_trows, d->d_tcnt, d->d_chg, N,
                          fixup ? nullptr : d->d_stale, fixup ? nullptr : d->d_stale_cnt, (int)(ahead || run_sorted(r0, e)), th);
       if (r0 > 0) HIP_OK(hipStreamWaitEvent(d->estream, d->ev_res[(r0 - 1) % R], 0));
@@ -8529,7 +8595,7 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
     const int32_t* bbase = d_bases + b;
     const bool fused_b = fused && b == n_batches - 1;
     if (fused_b) {  // the fused matched pod: the speculation check, then its rows (gated) before its eval
-      hipLaunchKernelGGL(k_rsv_check, dim3(1), dim3(256), 0, d->stream, d->d_chosen, bases[b], d->d_rsv,
+      hipLaunchKernelGGL(k_rsv_check, dim3(1), dim3(256), 0, d->stream, d_chosen, bases[b], d->d_rsv,
                          (int)ctx->rsv_pairs.size(), ctx->cfg.global_node_offset, d->d_rsv_gate);
       rc = device_refresh_flush(ctx, d->d_rsv_gate);
       if (rc) return rc;
@@ -8539,7 +8605,7 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
     if (rc) return rc;
     if (fused_b) {
       hipLaunchKernelGGL(k_rsv_gate_apply, dim3(1), dim3(64), 0, d->stream, d->d_rsv_gate, d->d_cand_cnt);
-      HIP_OK(hipMemcpyAsync(d->h_rsv_out.data() + 4, d->d_rsv_gate, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+      HIP_OK(copy_async(d->h_rsv_out.data() + 4, d->d_rsv_gate, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
     }
     if (bp == 1) {  // one pod: the single-node Reserve (cpuset accumulator when it binds)
       int elo = 0, ehi = 0;  // nodes whose affinities this batch's eval stored in d_aff (binding batches)
@@ -8550,8 +8616,8 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
       hipLaunchKernelGGL((ds ? (numa ? k_cpuset_reserve<true, true> : k_cpuset_reserve<true, false>)
                              : (numa ? k_cpuset_reserve<false, true> : k_cpuset_reserve<false, false>)),
                          dim3(1), dim3(64), 0, d->stream, d->soa,
-                         d->d_pods, bbase, k, d->d_cand, d->d_cand_cnt, d->d_chosen, d->d_chosen_score,
-                         ctx->cfg.global_node_offset, d->d_stamps, d->d_stamps + (n_pods + 2), b, d->d_devalloc,
+                         d->d_pods, bbase, k, d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score,
+                         ctx->cfg.global_node_offset, d_st, d_pst, b, d->d_devalloc,
                          numa ? d->d_numaalloc : nullptr, d->d_cpusets,
                          d->d_aff, elo, ehi);
     } else {
@@ -8561,12 +8627,12 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
                                  : (numa ? k_resolve<false, true, false>
                                          : ns ? k_resolve<false, false, false, true> : k_resolve<false, false, false>));
       hipLaunchKernelGGL(resolve, dim3(1), dim3(numa ? res_threads<true>() : res_threads<false>()), 0, d->stream, d->soa, d->d_pods, bbase, bp, k,
-                         d->d_cand, d->d_cand_cnt, d->d_chosen, d->d_chosen_score, ctx->cfg.global_node_offset,
-                         d->d_stamps, d->d_stamps + (n_pods + 2), b, d->d_devalloc, d->d_numaalloc, d->d_chg, N,
+                         d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score, ctx->cfg.global_node_offset,
+                         d_st, d_pst, b, d->d_devalloc, d->d_numaalloc, d->d_chg, N,
                          (int)run_sorted(b, b + 1));
       if (batches[b].cut) {  // a DeviceShare batch may stop early: re-run its remaining pods as batch b
         if (!d->h_cut.resize(1)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the cut word");
-        HIP_OK(hipMemcpyAsync(d->h_cut.data(), d->d_dsmax + DSB_CUT, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+        HIP_OK(copy_async(d->h_cut.data(), d->d_dsmax + DSB_CUT, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
         // the next serial batch's eval + select go in behind the read-back, so the device keeps working while the
         // host waits for the cut (without one they stand; with one the re-run batch overwrites what they wrote)
         if (b + 1 < n_batches && run_end[b + 1] == 0 && !(fused && b + 1 == n_batches - 1)) {
@@ -8584,7 +8650,7 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
           if (cut <= bases[b] || cut >= bases[b] + bp) return fail(KE_ERR_DEVICE, "DeviceShare batch cut out of range");
           batches[b].pods = bases[b] + bp - cut;
           bases[b] = cut;
-          HIP_OK(hipMemcpyAsync(d_bases + b, &bases[b], sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
+          HIP_OK(copy_async(d_bases + b, &bases[b], sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
           ctx->last_ds_cuts++;
           rerun = true;
           continue;
@@ -8611,35 +8677,34 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
   for (const Batch& bt : batches) any_ds = any_ds || bt.ds || bt.hint;
   const bool vf_out = d->soa.vfo != nullptr;
   const size_t np = (size_t)n_pods, nb = (size_t)n_batches;
-  size_t off = 0;
+  // h_out: the read-back block from its first wanted part (the scores lead it, so a call without them starts at
+  // the placements), then the context's error word and what only some calls have
+  const size_t blk0 = want_score ? ol.score : ol.chosen;
+  size_t off = (ol.end - blk0 + 15) & ~(size_t)15;
   auto take = [&](size_t bytes) {
     const size_t o = off;
     off = (off + bytes + 15) & ~(size_t)15;
     return o;
   };
-  const size_t o_chosen = take((size_t)out_bytes), o_score = take(want_score ? (size_t)out_bytes : 0),
+  const size_t o_chosen = ol.chosen - blk0, o_score = ol.score - blk0, o_err = ol.err - blk0, o_fst = ol.fst - blk0,
+               o_st = ol.st - blk0, o_pst = ol.pst - blk0, o_est = ol.est - blk0, o_kerr = take(4),
                o_dev = take(any_ds ? 8 * np : 0), o_cs = take(any_cpu ? 32 * np : 0),
-               o_vf = take(vf_out ? 2 * DS_MINORS * np : 0), o_numa = take(numa ? 8 * 16 * np : 0), o_err = take(8),
-               o_fst = take(16 * nb), o_dcnt = take(numa ? 4 * nb : 0), o_st = take(8 * (nb + 1)),
-               o_pst = take(8 * PST * nb), o_est = take(8 * nb);
+               o_vf = take(vf_out ? 2 * DS_MINORS * np : 0), o_numa = take(numa ? 8 * 16 * np : 0),
+               o_dcnt = take(numa ? 4 * nb : 0);
   if (!d->h_out.resize(off)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the readback staging buffer");
   uint8_t* const h = d->h_out.data();
   auto d2h = [&](size_t o, const void* src, size_t bytes) -> int {
-    if (bytes) HIP_OK(hipMemcpyAsync(h + o, src, bytes, hipMemcpyDeviceToHost, cs));
+    if (bytes) HIP_OK(copy_async(h + o, src, bytes, hipMemcpyDeviceToHost, cs));
     return KE_OK;
   };
-  if ((rc = d2h(o_chosen, d->d_chosen, (size_t)out_bytes))) return rc;
-  if (want_score && (rc = d2h(o_score, d->d_chosen_score, (size_t)out_bytes))) return rc;
+  if ((rc = d2h(0, d->d_out + blk0, ol.end - blk0)) || (rc = d2h(o_kerr, d->soa.kerr, 4))) return rc;
   if (any_ds && (rc = d2h(o_dev, d->d_devalloc, 8 * np))) return rc;
   if (any_cpu && (rc = d2h(o_cs, d->d_cpusets, 32 * np))) return rc;
   if (vf_out && (rc = d2h(o_vf, d->d_vfo, 2 * DS_MINORS * np))) return rc;
   if (numa && (rc = d2h(o_numa, d->d_numaalloc, 8 * 16 * np))) return rc;
-  if ((rc = d2h(o_err, d_err, 4)) || (rc = d2h(o_err + 4, d->soa.kerr, 4))) return rc;
-  if ((rc = d2h(o_fst, d_fst, 16 * nb))) return rc;
   if (numa && (rc = d2h(o_dcnt, d->d_defer_cnt, 4 * nb))) return rc;
-  if ((rc = d2h(o_st, d->d_stamps, 8 * (nb + 1))) || (rc = d2h(o_pst, d->d_stamps + (n_pods + 2), 8 * PST * nb)) ||
-      (rc = d2h(o_est, estamps, 8 * nb)))
-    return rc;
+  const int64_t cb_copies = n_copies, cb_fills = n_fills;
+  const bool behind = ctx->call_behind;  // (ke_schedule_submit: enqueued behind a call in flight)
   // the call's end on every stream: its completion waits for these events, not for the streams (a submission
   // behind it may already be queued on them)
   HIP_OK(hipEventRecord(done_ev[0], cs));
@@ -8691,7 +8756,9 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
     std::memcpy(dcnt.data(), h + o_dcnt, 4 * nb);
   }
   std::memcpy(&herr, h + o_err, 4);
-  std::memcpy(&kerr, h + o_err + 4, 4);
+  std::memcpy(&kerr, h + o_kerr, 4);
+  const uint64_t prev_end = ctx->prev_end_tick;  // (a failed call leaves none behind)
+  ctx->prev_end_tick = 0;
   std::memcpy(fst.data(), h + o_fst, 16 * nb);
   std::memcpy(st.data(), h + o_st, 8 * (nb + 1));
   std::memcpy(pst.data(), h + o_pst, 8 * PST * nb);
@@ -8715,6 +8782,13 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
   // s_memrealtime ticks -> ms, calibrated against the event-timed span of the whole queue
   const double span = (double)(st[n_batches] - st[0]);
   const double ms_per_tick = span > 0 ? ms / span : 1e-5;
+  // ke_debug_call_boundary: the device time between the previous call's last batch end and this call's first
+  // Reserve prologue (a call enqueued behind one in flight; the completions run in submission order)
+  ctx->call_boundary[0] = 0;  // (no batch's eval is enqueued ahead of the previous call's end)
+  ctx->call_boundary[1] = cb_copies;
+  ctx->call_boundary[2] = cb_fills;
+  ctx->call_boundary[3] = behind && prev_end && pst[0] > prev_end ? (int64_t)((double)(pst[0] - prev_end) * ms_per_tick * 1e6) : 0;
+  ctx->prev_end_tick = st[n_batches];
   // a batch's device service time: from its eval start to the end of its Reserve
   ctx->last_batch_ms.resize(n_batches);
   for (int b = 0; b < n_batches; b++) {

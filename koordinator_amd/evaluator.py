@@ -506,6 +506,12 @@ class Evaluator:
                                               ph.tolist() + sub.tolist())),
                 "resolve_wave1_ms": dict(zip(["wait", "reserve", "rows", "end"], w1.tolist()))}
 
+    def call_boundary(self):
+        """The last completed device call's boundary with the call before it (ke_debug_call_boundary)."""
+        out = np.zeros(4, np.int64)
+        self._check(self.lib.ke_debug_call_boundary(self.h, abi.ptr(out)))
+        return dict(zip(("primed_batches", "reserve_stream_copies", "reserve_stream_fills", "boundary_ns"), out.tolist()))
+
     def bench_eval_kernel(self, pods, now_ns, iters):
         pods = as_pod_array(pods)
         ms = C.c_double()
