@@ -917,6 +917,37 @@ int ke_node_set_bits(ke_ctx* ctx, int32_t node, int32_t n_sets, const uint8_t* m
  * KE_ERR_INVALID here; a following call with a different n_pods is KE_ERR_INVALID (and the ids are gone).  Does
  * not wait for calls in flight. */
 int ke_pod_node_sets(ke_ctx* ctx, int32_t n_pods, const int32_t* set_ids);
+/* ---- per-pod node score offsets (additive: KE_ABI_VERSION stays 14) ---------------------------------
+ * The Score half of the node sets: a profile's other Score plugins (ImageLocality, NodeAffinity's preferred terms,
+ * TaintToleration's PreferNoSchedule, site plugins) add to the sum selectHost maximises.  The caller computes
+ * Σ weight * score of those plugins once per distinct pod signature into a table of one uint16 per node
+ * (INTEGRATION.md §11), loads the tables and gives every pod of a call its table id.  For a pod with table id
+ * t > 0 and a node that passes every Filter and is in the pod's node set,
+ *   total = Σ weight * score of the evaluator's plugins (DeviceShare's normalised) + scores[t-1][node];
+ * a filtered pair stays at total -1.  A node at or beyond n_nodes has offset 0.
+ *  - ke_eval: total[] and best[] include the offset; the per-plugin outputs, status and reason do not change.
+ *  - ke_schedule / ke_schedule_submit / ke_schedule_wait: selection is over the sum, score[p] includes the
+ *    offset, ties go to the lowest node index; bit-exact with one pod at a time for every pod_batch, pipelined or
+ *    not, submitted ahead or not.  A call with a non-zero table id must be a plain queue exactly as one with a
+ *    non-zero set id (above); anything else is KE_ERR_UNSUPPORTED before any state changes ("node scores: ...",
+ *    or the node sets' message when a set id of the call is non-zero too).  ke_eval takes table ids wherever it
+ *    takes set ids (DeviceShare pods too, not node-sharded contexts).
+ * Set ids and table ids may both be staged for one call.  Without a table, or with every id 0, every call
+ * behaves as before. */
+#define KE_MAX_NODE_SCORE_TABLES 1024
+/* Replace the whole table: table t (1..n_tables) is n_nodes uint16 at scores + (t-1)*n_nodes.  The packed key
+ * holds total + 1 in 10 bits, so an entry above 1022 - 100 * (sum of the context's Score plugin weights) is
+ * KE_ERR_UNSUPPORTED (the message names the cap) and leaves the earlier table in place.  n_tables = 0 drops the
+ * table (scores may be NULL).  Completes calls in flight first. */
+int ke_node_scores_load(ke_ctx* ctx, int32_t n_tables, int32_t n_nodes, const uint16_t* scores);
+/* One node's entry in every loaded table: column[t-1] (a node event that changes its scores).  n_tables must equal
+ * the loaded count, node < n_nodes, every value within the cap.  Completes calls in flight first. */
+int ke_node_scores_set(ke_ctx* ctx, int32_t node, int32_t n_tables, const uint16_t* column);
+/* Table id per pod for the NEXT ke_eval / ke_schedule / ke_schedule_submit of exactly n_pods pods; 0 = no offset.
+ * Consumed by that call whether it succeeds or not.  An id outside 0..n_tables is KE_ERR_INVALID here; a following
+ * call with a different n_pods, or after the table was replaced by a smaller one, is KE_ERR_INVALID.  Does not
+ * wait for calls in flight. */
+int ke_pod_node_scores(ke_ctx* ctx, int32_t n_pods, const int32_t* table_ids);
 
 /* NodeInfo.Requested / NonZeroRequested (MilliCPU, Memory) of `node` as the plugins see it for a pod that
  * matches no reservation (after the restore above and the Reserves of past ke_schedule calls). */

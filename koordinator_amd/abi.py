@@ -71,6 +71,7 @@ REASON_FIT_TOO_MANY_PODS, REASON_FIT_INSUFFICIENT_CPU, REASON_FIT_INSUFFICIENT_M
 REASON_FIT_INSUFFICIENT_SCALAR = 67
 REASON_NODE_SET = 96  # the node is outside the pod's node eligibility set (ke_pod_node_sets)
 MAX_NODE_SETS = 4096
+MAX_NODE_SCORE_TABLES = 1024  # ke_node_scores_load's tables (per-pod node score offsets)
 # ke_pod.gpu_required_topology_scope (apiext.DeviceTopologyScope -> level)
 SCOPE_NONE, SCOPE_NODE, SCOPE_NUMA, SCOPE_PCIE, SCOPE_DEVICE, SCOPE_UNKNOWN = range(6)
 SCOPES = {"": SCOPE_NONE, "Node": SCOPE_NODE, "NUMANode": SCOPE_NUMA, "PCIe": SCOPE_PCIE, "Device": SCOPE_DEVICE}
@@ -561,6 +562,9 @@ EXPORTS = {
     "ke_node_sets_load": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
     "ke_node_set_bits": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
     "ke_pod_node_sets": (C.c_int, [C.c_void_p, i32, C.c_void_p]),
+    "ke_node_scores_load": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
+    "ke_node_scores_set": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
+    "ke_pod_node_scores": (C.c_int, [C.c_void_p, i32, C.c_void_p]),
     "ke_node_info_requested": (C.c_int, [C.c_void_p, i32, C.POINTER(i64), C.POINTER(i64)]),
     "ke_decode_pod_device_hints": (C.c_int, [C.c_char_p, i64, C.POINTER(PodDeviceHints), C.POINTER(i32)]),
     "ke_decode_device_flags": (C.c_int, [C.c_char_p, i64, C.c_char_p, i64, C.POINTER(i32), C.POINTER(i32)]),

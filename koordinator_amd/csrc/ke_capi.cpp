@@ -650,28 +650,100 @@ int ke_pod_node_sets(ke_ctx* ctx, int32_t n_pods, const int32_t* set_ids) {
   return KE_OK;
 }
 
-// The ke_pod_node_sets ids of this call, consumed whether it goes on or not; Context::ns_call = the ids when any is
-// non-zero (the device entry points then run the node-set kernels).  Such a call is refused here, before any state
-// changes, where the sets are not built: node-sharded contexts, and for ke_schedule (`sched`) anything but a plain
-// queue (ke_schedule_submit's sense, with device_async_ok's conditions).
+// ---- per-pod node score offsets (include/koord_eval.h): the node sets' lifecycle ----
+// The highest table entry the packed key's 10-bit score field leaves room for: total + 1 <= 1023 with every
+// Score plugin of the context at 100 (validate_config's sum).
+static int32_t node_score_cap(const ke_config& cfg) {
+  return MAX_TOTAL_SCORE - 100 * (cfg.weight_loadaware + cfg.weight_numa + cfg.weight_deviceshare + cfg.ext.weight_fitplus +
+                                  cfg.ext.weight_sra + cfg.fit.weight);
+}
+static int node_score_above_cap(const char* fn, int32_t cap) {
+  return fail(KE_ERR_UNSUPPORTED, std::string(fn) + ": an entry above " + std::to_string(cap) +
+                                      " = 1022 - 100 * (sum of the Score plugin weights): total + 1 must fit the key's 10 bits");
+}
+
+int ke_node_scores_load(ke_ctx* ctx, int32_t n_tables, int32_t n_nodes, const uint16_t* scores) {
+  if (ctx) async_drain(ctx);
+  if (!ctx || n_tables < 0 || n_nodes < 0) return fail(KE_ERR_INVALID, "ke_node_scores_load arguments");
+  if (n_tables > KE_MAX_NODE_SCORE_TABLES)
+    return fail(KE_ERR_INVALID, "ke_node_scores_load: more than KE_MAX_NODE_SCORE_TABLES tables");
+  if (n_nodes > MAX_SHARD_NODES) return fail(KE_ERR_INVALID, "ke_node_scores_load: n_nodes");
+  if (n_tables > 0 && !scores) return fail(KE_ERR_INVALID, "ke_node_scores_load: scores");
+  Context& c = ctx->c;
+  const size_t n = n_tables > 0 ? (size_t)n_tables * (size_t)n_nodes : 0;
+  const int32_t cap = node_score_cap(c.cfg);
+  for (size_t q = 0; q < n; q++)
+    if ((int32_t)scores[q] > cap) return node_score_above_cap("ke_node_scores_load", cap);
+  c.nsc_n = n_tables;
+  c.nsc_nodes = n_tables > 0 ? n_nodes : 0;
+  c.nsc_vals.assign(scores, scores + n);
+  c.nsc_dirty = true;
+  c.nsc_dirty_nodes.clear();
+  return KE_OK;
+}
+
+int ke_node_scores_set(ke_ctx* ctx, int32_t node, int32_t n_tables, const uint16_t* column) {
+  if (ctx) async_drain(ctx);
+  if (!ctx || (n_tables > 0 && !column)) return fail(KE_ERR_INVALID, "ke_node_scores_set arguments");
+  Context& c = ctx->c;
+  if (n_tables != c.nsc_n) return fail(KE_ERR_INVALID, "ke_node_scores_set: n_tables differs from the loaded table's");
+  if (node < 0 || node >= c.nsc_nodes) return fail(KE_ERR_NOT_FOUND, "ke_node_scores_set: node index beyond the table's n_nodes");
+  const int32_t cap = node_score_cap(c.cfg);
+  for (int32_t t = 0; t < n_tables; t++)
+    if ((int32_t)column[t] > cap) return node_score_above_cap("ke_node_scores_set", cap);
+  for (int32_t t = 0; t < n_tables; t++) c.nsc_vals[(size_t)t * (size_t)c.nsc_nodes + (size_t)node] = column[t];
+  if (!c.nsc_dirty) c.nsc_dirty_nodes.push_back(node);  // (the next call with a non-zero id uploads the column)
+  return KE_OK;
+}
+
+int ke_pod_node_scores(ke_ctx* ctx, int32_t n_pods, const int32_t* table_ids) {
+  if (!ctx || n_pods < 0 || (n_pods > 0 && !table_ids)) return fail(KE_ERR_INVALID, "ke_pod_node_scores arguments");
+  Context& c = ctx->c;
+  for (int32_t p = 0; p < n_pods; p++)
+    if (table_ids[p] < 0 || table_ids[p] > c.nsc_n)
+      return fail(KE_ERR_INVALID, "ke_pod_node_scores: table id outside 0..n_tables");
+  c.nsc_staged.assign(table_ids, table_ids + n_pods);
+  c.nsc_staged_on = true;
+  return KE_OK;
+}
+
+// The ke_pod_node_sets and ke_pod_node_scores ids of this call, both consumed whether it goes on or not;
+// Context::ns_call / nsc_call = the ids of a kind when any of them is non-zero (the device entry points then run the
+// node-set / score-offset kernels).  Such a call is refused here, before any state changes, where those kernels are
+// not built: node-sharded contexts, and for ke_schedule (`sched`) anything but a plain queue (ke_schedule_submit's
+// sense, with device_async_ok's conditions).  The message names the sets when a set id is non-zero, else the scores.
 static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool sched) {
   Context& c = ctx->c;
   c.ns_call = nullptr;
-  if (!c.ns_staged_on) return KE_OK;
-  c.ns_staged_on = false;
-  c.ns_call_ids.swap(c.ns_staged);
+  c.nsc_call = nullptr;
+  const bool sets_on = c.ns_staged_on, scores_on = c.nsc_staged_on;
+  if (!sets_on && !scores_on) return KE_OK;
+  c.ns_staged_on = c.nsc_staged_on = false;
+  c.ns_call_ids.clear();
+  c.nsc_call_ids.clear();
+  if (sets_on) c.ns_call_ids.swap(c.ns_staged);
+  if (scores_on) c.nsc_call_ids.swap(c.nsc_staged);
   c.ns_staged.clear();
-  if ((int32_t)c.ns_call_ids.size() != n_pods)
+  c.nsc_staged.clear();
+  if (sets_on && (int32_t)c.ns_call_ids.size() != n_pods)
     return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_node_sets ids'");
-  bool any = false;
+  if (scores_on && (int32_t)c.nsc_call_ids.size() != n_pods)
+    return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_node_scores ids'");
+  bool any = false, any_sc = false;
   for (int32_t id : c.ns_call_ids) {
     if (id < 0 || id > c.ns_n) return fail(KE_ERR_INVALID, "a staged node set id is outside the table loaded since");
     any = any || id != 0;
   }
-  if (!any) return KE_OK;
+  for (int32_t id : c.nsc_call_ids) {
+    if (id < 0 || id > c.nsc_n) return fail(KE_ERR_INVALID, "a staged node score table id is outside the table loaded since");
+    any_sc = any_sc || id != 0;
+  }
+  if (!any && !any_sc) return KE_OK;
   int rc = check_pods(pods, n_pods, &c, sched);
   if (rc) return rc;
-  auto no = [](const char* what) { return fail(KE_ERR_UNSUPPORTED, std::string("node sets: ") + what); };
+  auto no = [any](const char* what) {
+    return fail(KE_ERR_UNSUPPORTED, std::string(any ? "node sets: " : "node scores: ") + what);
+  };
   if (c.cfg.global_node_offset != 0 || (c.dev && device_sharded(&c))) return no("a node-sharded context");
   if (sched) {
     if (!c.match_off.empty()) return no("a call with staged ke_pod_reservations lists");
@@ -687,7 +759,8 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
       if (f & PF_CPUSET) return no("a cpuset pod in ke_schedule");
     }
   }
-  c.ns_call = c.ns_call_ids.data();
+  if (any) c.ns_call = c.ns_call_ids.data();
+  if (any_sc) c.nsc_call = c.nsc_call_ids.data();
   return KE_OK;
 }
 

@@ -235,6 +235,18 @@ struct Context {
   bool ns_staged_on = false;
   std::vector<int32_t> ns_call_ids;
   const int32_t* ns_call = nullptr;
+  // Per-pod node score offsets (ke_node_scores_load), with the node sets' lifecycle: the host mirror
+  // of the table (nsc_n rows of nsc_nodes entries, table t = row t - 1), what of the device copy is stale (all of
+  // it, or the node columns ke_node_scores_set patched), the ke_pod_node_scores staging for the next call, and the
+  // table ids of the call in progress (nullptr: no non-zero id, the call runs the kernels it ran without them)
+  int32_t nsc_n = 0, nsc_nodes = 0;
+  std::vector<uint16_t> nsc_vals;
+  bool nsc_dirty = false;
+  std::vector<int32_t> nsc_dirty_nodes;
+  std::vector<int32_t> nsc_staged;
+  bool nsc_staged_on = false;
+  std::vector<int32_t> nsc_call_ids;
+  const int32_t* nsc_call = nullptr;
   // the KE_RSV_MATCHED pod of the current segment: its nodes with matched reservations, their
   // (node, ScoreReservation of the nominated one, smallest order) for the device pick, the nominated index
   std::vector<int32_t> rsv_nodes;

@@ -90,18 +90,46 @@ struct SoA {
   int32_t ns_wps;
   const uint64_t* ns_tbl;
   const int32_t* ns_ids;
+  // per-pod node score offsets: rows 0 .. n_tables of nsc_stride (= the node capacity, a multiple
+  // of 64) uint16 entries, row 0 all zero (table id 0 = no offset), row t = table t.  A call that carries a non-zero
+  // table id packs (table id << 16) | set id into its ns_ids words and runs the NS == NS_SCORES instantiations.
+  int32_t nsc_stride;
+  const uint16_t* nsc_tbl;
 };
-// node `node` is in set `sid` (NS instantiations; every node < 64 * ns_wps is in bounds, sid checked by the host)
-template <bool NS>
-__device__ __forceinline__ bool ns_ok(const SoA& s, int sid, int node) {
+// NS, the template mode of every kernel that makes a score or key: 0 = the call has no per-pod ids, NS_SETS = its
+// ns_ids words are node set ids, NS_SCORES = they are (score table id << 16) | node set id
+constexpr int NS_SETS = 1, NS_SCORES = 2;
+// node `node` is in the set of id word `idw` (NS instantiations; every node < 64 * ns_wps is in bounds, the ids
+// checked by the host)
+template <int NS>
+__device__ __forceinline__ bool ns_ok(const SoA& s, int idw, int node) {
   if constexpr (!NS) return true;
-  else return (s.ns_tbl[(int64_t)sid * s.ns_wps + (node >> 6)] >> (node & 63)) & 1ull;
+  else return (s.ns_tbl[(int64_t)(NS == NS_SCORES ? idw & 0xffff : idw) * s.ns_wps + (node >> 6)] >> (node & 63)) & 1ull;
 }
 // a fresh key of (pod with set `sid`, node): 0 (filtered) outside the set
-template <bool NS>
+template <int NS>
 __device__ __forceinline__ uint32_t ns_key(const SoA& s, int sid, int node, uint32_t key) {
   if constexpr (!NS) return key;
-  else return ns_ok<true>(s, sid, node) ? key : 0u;
+  else return ns_ok<NS_SETS>(s, sid, node) ? key : 0u;
+}
+// the score offset of (pod with id word `idw`, node): 0 unless NS_SCORES; node < nsc_stride
+template <int NS>
+__device__ __forceinline__ int32_t ns_off(const SoA& s, int idw, int node) {
+  if constexpr (NS != NS_SCORES) return 0;
+  else return s.nsc_tbl[(int64_t)((uint32_t)idw >> 16) * s.nsc_stride + node];
+}
+// a fresh key of (pod with id word `idw`, node) from the plugins' total: the offset goes into a feasible total
+// before the key is packed (both table reads are issued before either is used); 0 outside the set
+template <int NS>
+__device__ __forceinline__ uint32_t ns_mkkey(const SoA& s, int idw, int node, int32_t total) {
+  if constexpr (NS != NS_SCORES) {
+    const uint32_t key = make_key(total, node);
+    return ns_key<NS>(s, idw, node, key);
+  } else {
+    const int32_t off = ns_off<NS>(s, idw, node);
+    const bool ok = ns_ok<NS>(s, idw, node);
+    return ok && total >= 0 ? make_key(total + off, node) : 0u;
+  }
 }
 __device__ __forceinline__ const RsvOvr* rsv_ovr_of(const SoA& s, int64_t node) {
   for (int q = 0; q < s.n_rovr; q++)
@@ -3171,7 +3199,7 @@ __device__ __forceinline__ void defer_push(bool want, uint64_t item, uint64_t* _
 // score over the pod's feasible nodes (DefaultNormalizeScore's maxCount).
 // NS: pods with a node set (SoA::ns_ids): a pair outside the set is KE_REASON_NODE_SET ahead of every other
 // filter -- scores 0, total -1, never deferred, and not part of the pod's DeviceShare normalisation max.
-template <bool NUMA, bool CPU, bool NS = false>
+template <bool NUMA, bool CPU, int NS = 0>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, int n_nodes, const DevPod* __restrict__ pods,
                                                             int n_pods, int pods_per_block, KArgs k,
                                                             uint8_t* status, uint8_t* reason, int16_t* la,
@@ -3226,9 +3254,12 @@ __device__ __forceinline__ int32_t ds_norm(int32_t raw, uint32_t dsmax1) {
 }
 
 // normalized DeviceShare score into the weighted sum, then selectHost's packed-key max per pod
+// SC: the call carries score table ids (packed in ids[], SoA::nsc_tbl): a feasible pair's offset goes into its
+// total here, after the normalisation and for the pairs the NUMA deferral finished too, ahead of the key
+template <bool SC = false>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_parity_finalize(int n_nodes, KArgs k, const int16_t* ds,
                                                                 int16_t* total, const uint32_t* dsmax,
-                                                                uint32_t* best_key) {
+                                                                uint32_t* best_key, SoA s) {
   const int i = blockIdx.x * EVAL_BLOCK + threadIdx.x;
   const int p = blockIdx.y;
   uint32_t key = 0;
@@ -3237,6 +3268,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_parity_finalize(int n_nodes, KAr
     int32_t t = total[o];
     if (t >= 0) {
       t += k.wp_ds * ds_norm(ds[o], dsmax[p]);
+      if constexpr (SC) t += ns_off<NS_SCORES>(s, s.ns_ids[p], i);  // (i < n_nodes <= nsc_stride)
       total[o] = (int16_t)t;
     }
     key = make_key(t, i);
@@ -3249,8 +3281,9 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_parity_finalize(int n_nodes, KAr
 // (always alone in its batch) also dsraw[node] = raw DeviceShare score + 1 (0 when filtered out).
 // Nodes [lo, hi) of the SoA (this rank's shard); scores stay indexed by the global node index.
 // DS: the batch's pod is a DeviceShare pod (the DeviceShare path stays out of plain batches' code).
-// NS (plain batches only): a node outside the pod's node set (SoA::ns_ids) is filtered (score 0).
-template <bool DS, bool NUMA, bool CPU, bool EXT = false, bool H = false, bool NS = false>
+// NS (plain batches only): a node outside the pod's node set (SoA::ns_ids) is filtered (score 0); NS_SCORES: a
+// feasible total takes the pod's score offset of the node (SoA::nsc_tbl) before the store.
+template <bool DS, bool NUMA, bool CPU, bool EXT = false, bool H = false, int NS = 0>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_batch(SoA s, int lo, int hi, const DevPod* __restrict__ pods,
                                                            const int32_t* __restrict__ batch_base, int batch_pods,
                                                            int pods_per_block, KArgs k, uint16_t* __restrict__ scores,
@@ -3284,6 +3317,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_batch(SoA s, int lo, int hi
       if (EXT && tot >= 0 && (k.flags & AF_FIT_FILTER) && fit_filter_row(s, i, n, pod, k)) tot = -1;
       if (EXT && tot >= 0) tot += ext_score(s, i, pod, k);  // FitPlus / SRA / Fit: its own variant
       if (NS && !ns_ok<NS>(s, s.ns_ids[base + p], i)) tot = -1;  // (wave-uniform word address)
+      if constexpr (NS == NS_SCORES) tot = tot >= 0 ? tot + ns_off<NS>(s, s.ns_ids[base + p], i) : tot;
       scores[(int64_t)p * score_stride + i] = (uint16_t)(tot + 1);
       continue;
     }
@@ -3315,7 +3349,7 @@ constexpr int EVAL_PPB = 8;  // pods per block (eval_grid's pod groups)
 __host__ __device__ constexpr bool use_record_eval(int pods) { return pods > 2; }
 // NS: the pods' node sets (SoA::ns_ids) -- the block's table words (one a wave and pod, the tile starts at a
 // multiple of 64: lo = 0, set calls are unsharded) are staged in LDS with the pods, a node outside is filtered.
-template <bool EXT, bool NS = false>
+template <bool EXT, int NS = 0>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi, const DevPod* __restrict__ pods,
                                                            const int32_t* __restrict__ batch_base, int batch_pods,
                                                            KArgs k, uint16_t* __restrict__ scores, int64_t score_stride,
@@ -3341,13 +3375,26 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
   __shared__ int64_t s_pi[EVAL_PPB][3];
   __shared__ uint32_t s_pf[EVAL_PPB];
   __shared__ uint64_t s_ns[NS ? EVAL_PPB : 1][EVAL_BLOCK / 64];
+  // NS_SCORES: this lane's offsets of the group's pods, loaded ahead of the scoring loop (a wave reads 128
+  // aligned bytes of a wave-uniform row; the rows cover the node capacity, so i < hi is in bounds), four to a
+  // register pair so that the loop's wave-uniform q picks one without an indexed register file
+  uint64_t off[2] = {0ull, 0ull};
+  if constexpr (NS == NS_SCORES) {
+    static_assert(EVAL_PPB == 8, "two words of four offsets");
+#pragma unroll
+    for (int q = 0; q < EVAL_PPB; q++) {
+      const uint16_t v = q < np && i < hi ? s.nsc_tbl[(int64_t)((uint32_t)s.ns_ids[base + p0 + q] >> 16) * s.nsc_stride + i] : (uint16_t)0;
+      off[q >> 2] |= (uint64_t)v << ((q & 3) * 16);
+    }
+  }
   if ((int)threadIdx.x < 4 * np) {
     const int q = threadIdx.x >> 2, c = threadIdx.x & 3;
     const DevPod& pp = pods[base + p0 + q];
     if constexpr (NS) {  // wave c's word of pod q's set (past the table: no node of the tile is live there)
       static_assert(EVAL_BLOCK / 64 == 4, "one table word per wave of the block");
       const int w = ((lo + tile * (int)blockDim.x) >> 6) + c;
-      s_ns[q][c] = w < s.ns_wps ? s.ns_tbl[(int64_t)s.ns_ids[base + p0 + q] * s.ns_wps + w] : 0ull;
+      const int idw = s.ns_ids[base + p0 + q];
+      s_ns[q][c] = w < s.ns_wps ? s.ns_tbl[(int64_t)(NS == NS_SCORES ? idw & 0xffff : idw) * s.ns_wps + w] : 0ull;
     }
     s_pd[q][c] = (double)(c < 2 ? pp.est[c] : pp.req[c - 2]);
     if (!EXT && c < 3) s_pi[q][c] = c < 2 ? pp.est[c] : pp.req[0];
@@ -3373,6 +3420,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
       pl.req[0] = s_pi[q][2];
       t = fast_total<false>(f, pl, ed, rd, k);
     }
+    if constexpr (NS == NS_SCORES) t = t >= 0 ? t + (int32_t)((uint32_t)((q < 4 ? off[0] : off[1]) >> ((q & 3) * 16)) & 0xffffu) : t;
     if (NS && !((s_ns[q][threadIdx.x >> 6] >> (threadIdx.x & 63)) & 1ull)) t = -1;
     out[(int64_t)q * score_stride] = (uint16_t)(t + 1);
   }
@@ -3382,7 +3430,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
 // b's eval waited only for batch b-3's done flag; once done[b-2] is published (a k_handoff ahead of this kernel)
 // lane t of workgroup j re-evaluates node t of batch b-2's changed list (written with its rows, drained before
 // the flag) for pod j from its record, as k_eval_plain does -- the lists then see every Reserve of batches <= b-2.
-template <bool EXT, bool NS = false>
+template <bool EXT, int NS = 0>
 __global__ __launch_bounds__(64) void k_patch(SoA s, const DevPod* __restrict__ pods, const int32_t* __restrict__ batch_base,
                                               KArgs k, const int32_t* __restrict__ tlist, uint16_t* __restrict__ scores,
                                               int64_t score_stride, const int32_t* __restrict__ done_wait,
@@ -3405,6 +3453,7 @@ __global__ __launch_bounds__(64) void k_patch(SoA s, const DevPod* __restrict__ 
   const double ed[2] = {(double)pod.est[0], (double)pod.est[1]}, rd[2] = {(double)pod.req[0], (double)pod.req[1]};
   int32_t tot = fast_total<EXT>(f, pod, ed, rd, k);
   if (NS && !ns_ok<NS>(s, s.ns_ids[*batch_base + j], node)) tot = -1;  // outside the pod's node set
+  if constexpr (NS == NS_SCORES) tot = tot >= 0 ? tot + ns_off<NS>(s, s.ns_ids[*batch_base + j], node) : tot;
   scores[(int64_t)j * score_stride + node] = (uint16_t)(tot + 1);
 }
 
@@ -4437,7 +4486,7 @@ constexpr int FIX_BLOCK = KSTALE + KMAX;  // stale keys, then fresh keys of the 
 // The touched nodes come as the Reserve kernel's compact list of the rows batch b-1 changed (distinct
 // nodes, the node index in Row.pad), so no row gather depends on a node id read after the wait.
 
-template <bool EXT, bool NS = false>
+template <bool EXT, int NS = 0>
 __global__ __launch_bounds__(FIX_BLOCK) void k_fixup(SoA s, const DevPod* __restrict__ pods,
                                                      const int32_t* __restrict__ batch_base, KArgs k,
                                                      const uint32_t* __restrict__ stale,
@@ -4483,7 +4532,7 @@ __global__ __launch_bounds__(FIX_BLOCK) void k_fixup(SoA s, const DevPod* __rest
   } else if (node >= 0) {
     fast_adopt(n, k);
     const double estd[2] = {(double)pod.est[0], (double)pod.est[1]}, reqd[2] = {(double)pod.req[0], (double)pod.req[1]};
-    key = ns_key<NS>(s, NS ? s.ns_ids[*batch_base + j] : 0, node, make_key(fast_total<EXT>(n, pod, estd, reqd, k), node));
+    key = ns_mkkey<NS>(s, NS ? s.ns_ids[*batch_base + j] : 0, node, fast_total<EXT>(n, pod, estd, reqd, k));
   }
   reinterpret_cast<uint32_t*>(s_k)[t] = key;
   const int nz = __syncthreads_count(key != 0u);
@@ -4520,7 +4569,7 @@ __global__ __launch_bounds__(FIX_BLOCK) void k_fixup(SoA s, const DevPod* __rest
 constexpr int FIXL_BLOCK = KSTALE2 + KMAX;
 constexpr int FIXL_PARTS_BLOCK = 1024;
 static_assert((1024 / KSTALE2) * KSTALE2 <= FIXL_PARTS_BLOCK, "every part of a select-ahead split fits a workgroup");
-template <bool EXT, bool PARTS = false, bool NS = false>
+template <bool EXT, bool PARTS = false, int NS = 0>
 __global__ __launch_bounds__(PARTS ? FIXL_PARTS_BLOCK : FIXL_BLOCK) void k_fixlist(
     SoA s, const DevPod* __restrict__ pods, const int32_t* __restrict__ batch_base, KArgs k,
     const uint32_t* __restrict__ pre, const int32_t* __restrict__ pre_cnt, const int32_t* __restrict__ tlist,
@@ -4593,7 +4642,7 @@ __global__ __launch_bounds__(PARTS ? FIXL_PARTS_BLOCK : FIXL_BLOCK) void k_fixli
   } else if (node >= 0) {
     fast_adopt(n, k);
     const double estd[2] = {(double)pod.est[0], (double)pod.est[1]}, reqd[2] = {(double)pod.req[0], (double)pod.req[1]};
-    key = ns_key<NS>(s, NS ? s.ns_ids[*batch_base + j] : 0, node, make_key(fast_total<EXT>(n, pod, estd, reqd, k), node));
+    key = ns_mkkey<NS>(s, NS ? s.ns_ids[*batch_base + j] : 0, node, fast_total<EXT>(n, pod, estd, reqd, k));
   }
   if (t < FIXL_BLOCK) reinterpret_cast<uint32_t*>(s_k)[t] = key;
   const int nz = __syncthreads_count(key != 0u);
@@ -4841,7 +4890,9 @@ struct ResLdsCore {
 // SIMDs of their own instead of queueing behind a concurrent eval's FP64 instructions (pipelined schedule).
 constexpr int CU_LDS_BYTES = 163840;
 struct ResLds : ResLdsCore {
-  int32_t nsid[MAX_BATCH];  // the pods' node set ids (NS instantiations; behind the core, whose offsets stay)
+  // the pods' node set ids, or with NS_SCORES their (score table id << 16) | set id words (NS instantiations;
+  // behind the core, whose offsets stay)
+  int32_t nsid[MAX_BATCH];
   uint8_t cu_fill[CU_LDS_BYTES - 64 - sizeof(ResLdsCore) - sizeof(int32_t) * MAX_BATCH];
 };
 static_assert(sizeof(ResLds) == CU_LDS_BYTES - 64, "ResLds fills the CU's LDS");
@@ -5012,13 +5063,14 @@ __device__ __forceinline__ void spec_predict_lean(ResLds& L, const ChgSet& C, in
 // j's best such node in its stale list); S evaluates every pod against all of T besides its own slots c < j; a
 // pod whose best current key is a T node takes it in V (Reserve on the T slot).  The batch's changed nodes --
 // its own slots and the T slots it reserved -- are written back and become the next batch's T.
-// NS: a fresh key of a node outside the pod's node set (L.nsid) is 0, as its snapshot key was
-template <bool NS>
+// NS: a fresh key of a node outside the pod's node set (L.nsid) is 0, as its snapshot key was; with NS_SCORES a
+// fresh total takes the pod's score offset of the node before it is packed, as its snapshot score did (ns_mkkey)
+template <int NS>
 __device__ __forceinline__ int nsid_of(const ResLds& L, int j) {
   if constexpr (NS) return L.nsid[j];
   else return 0;
 }
-template <bool EXT, bool NS = false>
+template <bool EXT, int NS = 0>
 __device__ __forceinline__ void replay_spec(ResLds& L, const ChgSet& C, const SoA& s, const int base, const int B,
                                             const KArgs& k, int32_t* __restrict__ chosen,
                                             int32_t* __restrict__ chosen_score, int32_t global_offset,
@@ -5064,7 +5116,7 @@ __device__ __forceinline__ void replay_spec(ResLds& L, const ChgSet& C, const So
     if (L.sp.tver[j] == tres) return;
     const DevPod p = L.pod[j];
     const double ed[2] = {L.pd[j][0], L.pd[j][1]}, rd[2] = {L.pd[j][2], L.pd[j][3]};
-    uint32_t tk = tv ? ns_key<NS>(s, nsid_of<NS>(L, j), tnode, make_key(fast_total<EXT>(tslot, p, ed, rd, k), tnode)) : 0u;
+    uint32_t tk = tv ? ns_mkkey<NS>(s, nsid_of<NS>(L, j), tnode, fast_total<EXT>(tslot, p, ed, rd, k)) : 0u;
     tk = wave_max_u32(tk);
     if (lane == 0) L.sp.tmx[j] = tk, L.sp.tver[j] = tres;
   };
@@ -5084,8 +5136,8 @@ __device__ __forceinline__ void replay_spec(ResLds& L, const ChgSet& C, const So
     const double ed1[2] = {L.pd[j1][0], L.pd[j1][1]}, rd1[2] = {L.pd[j1][2], L.pd[j1][3]};
     uint32_t tk = 0, tk1 = 0;
     if (tv) {
-      tk = ns_key<NS>(s, nsid_of<NS>(L, j), tnode, make_key(fast_total<EXT>(tslot, p, ed, rd, k), tnode));
-      tk1 = ns_key<NS>(s, nsid_of<NS>(L, j1), tnode, make_key(fast_total<EXT>(tslot, p1, ed1, rd1, k), tnode));
+      tk = ns_mkkey<NS>(s, nsid_of<NS>(L, j), tnode, fast_total<EXT>(tslot, p, ed, rd, k));
+      tk1 = ns_mkkey<NS>(s, nsid_of<NS>(L, j1), tnode, fast_total<EXT>(tslot, p1, ed1, rd1, k));
     }
     tk = wave_max_u32(tk);
     tk1 = wave_max_u32(tk1);
@@ -5214,13 +5266,13 @@ __device__ __forceinline__ void replay_spec(ResLds& L, const ChgSet& C, const So
         for (int j = c + 1 + g; pv && j < end; j += RS * GW) {
           const DevPod p = L.pod[j];
           const double ed[2] = {L.pd[j][0], L.pd[j][1]}, rd[2] = {L.pd[j][2], L.pd[j][3]};
-          const uint32_t kc = ns_key<NS>(s, nsid_of<NS>(L, j), pnode, make_key(fast_total<EXT>(pslot, p, ed, rd, k), pnode));
+          const uint32_t kc = ns_mkkey<NS>(s, nsid_of<NS>(L, j), pnode, fast_total<EXT>(pslot, p, ed, rd, k));
           uint32_t kc1 = 0u;
           const int j1 = j + GW;
           if (RS == 2 && j1 < end) {
             const DevPod p1 = L.pod[j1];
             const double ed1[2] = {L.pd[j1][0], L.pd[j1][1]}, rd1[2] = {L.pd[j1][2], L.pd[j1][3]};
-            kc1 = ns_key<NS>(s, nsid_of<NS>(L, j1), pnode, make_key(fast_total<EXT>(pslot, p1, ed1, rd1, k), pnode));
+            kc1 = ns_mkkey<NS>(s, nsid_of<NS>(L, j1), pnode, fast_total<EXT>(pslot, p1, ed1, rd1, k));
           }
           if (kc) atomicMax(&L.sp.mrow[j], kc);
           if (kc1) atomicMax(&L.sp.mrow[j1], kc1);
@@ -5273,10 +5325,10 @@ __device__ __forceinline__ void replay_spec(ResLds& L, const ChgSet& C, const So
         if (has1) {
           const DevPod p1 = L.pod[j1];
           const double ed1[2] = {L.pd[j1][0], L.pd[j1][1]}, rd1[2] = {L.pd[j1][2], L.pd[j1][3]};
-          if (sv && lane < j) kc = ns_key<NS>(s, nsid_of<NS>(L, j), snode, make_key(fast_total<EXT>(slot, p, ed, rd, k), snode));
-          if (sv && lane < j1) kc1 = ns_key<NS>(s, nsid_of<NS>(L, j1), snode, make_key(fast_total<EXT>(slot, p1, ed1, rd1, k), snode));
+          if (sv && lane < j) kc = ns_mkkey<NS>(s, nsid_of<NS>(L, j), snode, fast_total<EXT>(slot, p, ed, rd, k));
+          if (sv && lane < j1) kc1 = ns_mkkey<NS>(s, nsid_of<NS>(L, j1), snode, fast_total<EXT>(slot, p1, ed1, rd1, k));
         } else if (sv && lane < j) {
-          kc = ns_key<NS>(s, nsid_of<NS>(L, j), snode, make_key(fast_total<EXT>(slot, p, ed, rd, k), snode));
+          kc = ns_mkkey<NS>(s, nsid_of<NS>(L, j), snode, fast_total<EXT>(slot, p, ed, rd, k));
         }
         uint32_t tk = 0, tk1 = 0;
         if (tin) {  // T changes only when a pod of the batch reserves on it: pod j's T max is cached meanwhile
@@ -5407,7 +5459,7 @@ __device__ __forceinline__ ChgSet chg_init(ResLds& L, uint32_t* glb, int n_nodes
   return ChgSet{L.chg, glb};
 }
 
-template <bool DS, bool NUMA, bool QUOTA, bool EXT, bool NS>
+template <bool DS, bool NUMA, bool QUOTA, bool EXT, int NS>
 __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const SoA& s, const int base, const int B,
                                              const KArgs& k, int32_t* __restrict__ chosen,
                                              int32_t* __restrict__ chosen_score, int32_t global_offset,
@@ -5418,7 +5470,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
 
 // One batch: prologue on every thread of the workgroup (the batch's pods and exact candidate lists
 // into LDS), replay on wave 0 (the other waves skip it).
-template <bool DS, bool NUMA, bool QUOTA, bool EXT = true, bool NS = false>
+template <bool DS, bool NUMA, bool QUOTA, bool EXT = true, int NS = 0>
 __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const SoA& s, const DevPod* __restrict__ pods,
                                               const int base, const int B, const KArgs& k,
                                               const uint32_t* __restrict__ cand, const int32_t* __restrict__ cand_cnt,
@@ -5518,7 +5570,7 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
 //   fetched from the SoA by the next free lane at the start of the pod, into spare registers, so its
 //   latency hides under the re-evaluation; it becomes that lane's row if bu wins.  Pod j+1's record
 //   and candidates are read during pod j, its changed flags right after pod j's Reserve.
-template <bool DS, bool NUMA, bool QUOTA, bool EXT, bool NS>
+template <bool DS, bool NUMA, bool QUOTA, bool EXT, int NS>
 __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const SoA& s, const int base, const int B,
                                              const KArgs& k, int32_t* __restrict__ chosen,
                                              int32_t* __restrict__ chosen_score, int32_t global_offset,
@@ -5595,7 +5647,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
       } else {
         tot = fast_total<EXT>(fast, pod, estd, reqd, k);
       }
-      kc = ns_key<NS>(s, nsid_of<NS>(L, j), my_node, make_key(tot, my_node));
+      kc = ns_mkkey<NS>(s, nsid_of<NS>(L, j), my_node, tot);
     }
     RPROF(2)
     const uint32_t bc = wave_max_u32(kc);
@@ -5777,7 +5829,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
   drain_stores();  // every hand-off store is performed before the workgroup publishes the batch
 }
 
-template <bool DS, bool NUMA, bool QUOTA, bool NS = false>
+template <bool DS, bool NUMA, bool QUOTA, int NS = 0>
 __global__ __launch_bounds__(res_threads<NUMA>()) void k_resolve(SoA s, const DevPod* __restrict__ pods, const int32_t* __restrict__ batch_base,
                                                 int batch_pods, KArgs k, const uint32_t* __restrict__ cand,
                                                 const int32_t* __restrict__ cand_cnt, int32_t* __restrict__ chosen,
@@ -5800,7 +5852,7 @@ __global__ __launch_bounds__(res_threads<NUMA>()) void k_resolve(SoA s, const De
 // one relaxed add on tready[b] per helper.  A batch the Reserve workgroup has already finished (done[b]) is
 // skipped; the Reserve workgroup falls back to its own rows for any batch whose maxima arrive late, so no
 // wait of the run depends on a helper being resident.
-template <bool EXT, bool NS = false>
+template <bool EXT, int NS = 0>
 __device__ __noinline__ void t_helper(ResLds& L, const SoA& s, const DevPod* __restrict__ pods,
                                       const int32_t* __restrict__ bases, int b0, int nb, const KArgs& k,
                                       const int32_t* __restrict__ done, int32_t* __restrict__ err, const THelp th,
@@ -5855,12 +5907,12 @@ __device__ __noinline__ void t_helper(ResLds& L, const SoA& s, const DevPod* __r
         const bool has1 = j1 < B;
         const DevPod p = L.pod[j];
         const double ed[2] = {L.pd[j][0], L.pd[j][1]}, rd[2] = {L.pd[j][2], L.pd[j][3]};
-        uint32_t tk = tv ? ns_key<NS>(s, nsid_of<NS>(L, j), tnode, make_key(fast_total<EXT>(tslot, p, ed, rd, k), tnode)) : 0u;
+        uint32_t tk = tv ? ns_mkkey<NS>(s, nsid_of<NS>(L, j), tnode, fast_total<EXT>(tslot, p, ed, rd, k)) : 0u;
         uint32_t tk1 = 0u;
         if (has1) {
           const DevPod p1 = L.pod[j1];
           const double ed1[2] = {L.pd[j1][0], L.pd[j1][1]}, rd1[2] = {L.pd[j1][2], L.pd[j1][3]};
-          tk1 = tv ? ns_key<NS>(s, nsid_of<NS>(L, j1), tnode, make_key(fast_total<EXT>(tslot, p1, ed1, rd1, k), tnode)) : 0u;
+          tk1 = tv ? ns_mkkey<NS>(s, nsid_of<NS>(L, j1), tnode, fast_total<EXT>(tslot, p1, ed1, rd1, k)) : 0u;
         }
         tk = wave_max_u32(tk);
         tk1 = wave_max_u32(tk1);
@@ -5885,7 +5937,7 @@ __device__ __noinline__ void t_helper(ResLds& L, const SoA& s, const DevPod* __r
 //   else: the stale top-(k_j + KMAX) lists of the double buffer `stale` (stride KSTALE) go straight to the
 //   speculative replay, with the previous batch's changed rows (touched_out, this workgroup wrote them) as
 //   its T slots -- no fixup kernel and no hand-off back to the eval stream on the critical path.
-template <bool QUOTA, bool EXT, bool NS = false>
+template <bool QUOTA, bool EXT, int NS = 0>
 __global__ __launch_bounds__(res_threads<false>()) void k_resolve_run(SoA s, const DevPod* __restrict__ pods,
                                                                       const int32_t* __restrict__ bases, int b0, int nb,
                                                                       KArgs k, const uint32_t* __restrict__ cand,
@@ -6933,6 +6985,9 @@ struct DeviceState {
   // lie behind its DevPod records in d_pods (one per buffer set), staged alike behind host_pods (upload_pods)
   uint64_t* d_ns_tbl = nullptr;
   int64_t ns_tbl_cap = 0;
+  // node score offsets: rows 0 .. nsc_n of `capacity` uint16 entries (row 0 all zero)
+  uint16_t* d_nsc_tbl = nullptr;
+  int64_t nsc_tbl_cap = 0;
   int8_t* d_vfo = nullptr;     // [n_pods][2][DS_MINORS] VF ranks of the Reserves
   int64_t vfo_cap = 0;
   // batch buffers
@@ -7288,7 +7343,7 @@ void device_destroy(Context* ctx) {
                   d->d_cpurows, d->d_cpusets, d->d_aff, d->soa.qt, d->soa.qm, d->d_sched, d->d_stale,
                   d->d_stale_cnt, d->d_pre, d->d_trows, d->d_tcnt, d->d_parts_done, d->d_scores2, d->d_split2, d->d_chg, d->soa.rec, d->soa.pt, d->soa.kerr,
                   d->soa.xf, d->soa.xm, d->d_xrows, d->soa.dsx, d->d_ph, d->d_vfo, d->d_rsv, d->d_rsv_out, d->d_rsv_st,
-                  d->d_rsv_views, d->d_ds_views, d->d_numa_views, d->d_rovr, d->d_rsv_gate, d->d_ns_tbl};
+                  d->d_rsv_views, d->d_ds_views, d->d_numa_views, d->d_rovr, d->d_rsv_gate, d->d_ns_tbl, d->d_nsc_tbl};
   if (d->estream) (void)hipStreamSynchronize(d->estream);
   if (d->estream2) (void)hipStreamSynchronize(d->estream2);
   for (void* p : ptrs)
@@ -7831,6 +7886,46 @@ static int node_sets_sync(Context* ctx) {
   return KE_OK;
 }
 
+// The device copy of the score offset table brought up to date for a call that carries table ids:
+// rows 0 .. nsc_n of `capacity` uint16 entries (a multiple of 256, so a wave's 64 entries are 128 aligned bytes) --
+// row 0 all zero (id 0: no offset), row t the entries of table t below the node capacity, zero at and beyond the
+// table's n_nodes -- so a lookup of any (id, node < capacity) is in bounds without a branch.  A reload uploads the
+// table, ke_node_scores_set's patches one strided column copy per node.  As the set table, it only changes with no
+// call in flight.
+static int node_scores_sync(Context* ctx) {
+  DeviceState* d = ctx->dev;
+  const int64_t S = d->capacity, nn = ctx->nsc_nodes, cn = std::min<int64_t>(S, nn);
+  const int64_t rows = (int64_t)ctx->nsc_n + 1;
+  if (ctx->nsc_dirty || !d->d_nsc_tbl) {
+    std::vector<uint16_t> t((size_t)(rows * S), (uint16_t)0);
+    for (int64_t r = 0; r + 1 < rows; r++)
+      std::copy(ctx->nsc_vals.begin() + r * nn, ctx->nsc_vals.begin() + r * nn + cn, t.begin() + (r + 1) * S);
+    const int rc = ensure((void**)&d->d_nsc_tbl, &d->nsc_tbl_cap, (int64_t)sizeof(uint16_t) * rows * S);
+    if (rc) return rc;
+    HIP_OK(hipMemcpyAsync(d->d_nsc_tbl, t.data(), sizeof(uint16_t) * t.size(), hipMemcpyHostToDevice, d->stream));
+    HIP_OK(hipStreamSynchronize(d->stream));
+  } else if (!ctx->nsc_dirty_nodes.empty() && rows > 1) {
+    std::vector<int32_t>& dn = ctx->nsc_dirty_nodes;
+    std::sort(dn.begin(), dn.end());
+    dn.erase(std::unique(dn.begin(), dn.end()), dn.end());
+    std::vector<uint16_t> col((size_t)(rows - 1) * dn.size());
+    size_t q = 0;
+    for (int32_t i : dn) {
+      if (i >= cn) continue;
+      uint16_t* cq = col.data() + (q++) * (size_t)(rows - 1);
+      for (int64_t r = 0; r + 1 < rows; r++) cq[r] = ctx->nsc_vals[(size_t)(r * nn + i)];
+      HIP_OK(hipMemcpy2DAsync(d->d_nsc_tbl + S + i, sizeof(uint16_t) * S, cq, sizeof(uint16_t), sizeof(uint16_t),
+                              (size_t)(rows - 1), hipMemcpyHostToDevice, d->stream));
+    }
+    HIP_OK(hipStreamSynchronize(d->stream));
+  }
+  ctx->nsc_dirty = false;
+  ctx->nsc_dirty_nodes.clear();
+  d->soa.nsc_tbl = d->d_nsc_tbl;
+  d->soa.nsc_stride = (int32_t)S;
+  return KE_OK;
+}
+
 // The call's upload block: the DevPod records, the node set ids when present (int32 each) and room for
 // tail_words more int32 words, laid out alike in the page-locked host_pods and in d_pods, so one copy carries
 // it.  Without `tail` the block is copied here; with it the caller fills *tail (ke_schedule's batch bases) and
@@ -7841,8 +7936,11 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, hipStre
   DeviceState* d = ctx->dev;
   if (!ustream) ustream = d->stream;
   PinnedVec<DevPod>& dp = d->host_pods;
-  const int32_t* ns = ctx->ns_call;  // the call's node set ids (a non-zero one among them): behind the records
-  const int64_t ns_words = ns ? (int64_t)n_pods : 0;
+  // the call's node set ids and score table ids (a non-zero one among either): one word per pod behind the
+  // records, the set id alone or -- in a call with table ids -- (table id << 16) | set id
+  const int32_t* ns = ctx->ns_call;
+  const int32_t* sc = ctx->nsc_call;
+  const int64_t ns_words = ns || sc ? (int64_t)n_pods : 0;
   if (!dp.resize((size_t)n_pods, sizeof(int32_t) * (size_t)(ns_words + tail_words)))
     return fail(KE_ERR_DEVICE, "hipHostMalloc of the pod staging buffer");
   std::vector<DevPodHint>& ph = d->host_ph;  // the hinted pods' records; DevPod::ring_bw = slot
@@ -7866,8 +7964,9 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, hipStre
   if (rc) return rc;
   int32_t* const h_words = reinterpret_cast<int32_t*>(dp.data() + n_pods);
   d->soa.ns_ids = nullptr;
-  if (ns) {
-    std::copy(ns, ns + n_pods, h_words);
+  if (ns || sc) {
+    static_assert(KE_MAX_NODE_SETS < (1 << 16) && KE_MAX_NODE_SCORE_TABLES < (1 << 15), "the packed id word");
+    for (int32_t p = 0; p < n_pods; p++) h_words[p] = (ns ? ns[p] : 0) | (sc ? sc[p] << 16 : 0);
     d->soa.ns_ids = reinterpret_cast<int32_t*>(d->d_pods + n_pods);
   }
   if (tail) *tail = h_words + ns_words;
@@ -7895,9 +7994,14 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
   int rc = device_refresh(ctx, now);
   if (rc) return rc;
   if (n_pods == 0) return KE_OK;
-  const bool ns = ctx->ns_call != nullptr;  // pods with node sets: the NS instantiations
+  // pods with node sets (NS_SETS) or score tables (NS_SCORES, which reads the set table too: id 0 = its row 0)
+  const int ns = ctx->nsc_call ? NS_SCORES : ctx->ns_call ? NS_SETS : 0;
   if (ns) {
     rc = node_sets_sync(ctx);
+    if (rc) return rc;
+  }
+  if (ns == NS_SCORES) {
+    rc = node_scores_sync(ctx);
     if (rc) return rc;
   }
   rc = upload_pods(ctx, n_pods, pods);
@@ -7930,7 +8034,8 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
       rc = ensure((void**)&d->d_defer_cnt, &d->defer_cnt_cap, sizeof(uint32_t));
       if (rc) return rc;
       HIP_OK(hipMemsetAsync(d->d_defer_cnt, 0, sizeof(uint32_t), d->stream));
-      hipLaunchKernelGGL((ns ? (cpu ? k_eval_parity<true, true, true> : k_eval_parity<true, false, true>)
+      hipLaunchKernelGGL((ns == NS_SCORES ? (cpu ? k_eval_parity<true, true, NS_SCORES> : k_eval_parity<true, false, NS_SCORES>)
+                          : ns ? (cpu ? k_eval_parity<true, true, NS_SETS> : k_eval_parity<true, false, NS_SETS>)
                              : (cpu ? k_eval_parity<true, true> : k_eval_parity<true, false>)), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->d_pods, (int)P,
                          ppb, k, d_status, d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, d->d_defer, d->d_defer_cnt);
       HIP_OK(hipGetLastError());
@@ -7944,14 +8049,15 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
                          d->d_batch_base, k, d->d_defer, d->d_defer_cnt, d->d_scores, d->capacity, (int)N, d_status,
                          d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, nullptr, nullptr, fb);
     } else {
-      hipLaunchKernelGGL((ns ? (cpu ? k_eval_parity<false, true, true> : k_eval_parity<false, false, true>)
+      hipLaunchKernelGGL((ns == NS_SCORES ? (cpu ? k_eval_parity<false, true, NS_SCORES> : k_eval_parity<false, false, NS_SCORES>)
+                          : ns ? (cpu ? k_eval_parity<false, true, NS_SETS> : k_eval_parity<false, false, NS_SETS>)
                              : (cpu ? k_eval_parity<false, true> : k_eval_parity<false, false>)), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->d_pods, (int)P,
                          ppb, k, d_status, d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, nullptr, nullptr);
     }
     HIP_OK(hipGetLastError());
     dim3 grid2((unsigned)((N + EVAL_BLOCK - 1) / EVAL_BLOCK), (unsigned)P);
-    hipLaunchKernelGGL(k_parity_finalize, grid2, dim3(EVAL_BLOCK), 0, d->stream, (int)N, k, d_ds, d_total, d_dsmax,
-                       d->d_best);
+    hipLaunchKernelGGL((ns == NS_SCORES ? k_parity_finalize<true> : k_parity_finalize<false>), grid2, dim3(EVAL_BLOCK), 0,
+                       d->stream, (int)N, k, d_ds, d_total, d_dsmax, d->d_best, d->soa);
     HIP_OK(hipGetLastError());
   }
   if (status) HIP_OK(hipMemcpyAsync(status, d_status, M, hipMemcpyDeviceToHost, d->stream));
@@ -8054,10 +8160,17 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
   hipStream_t const cs = d->cstream ? d->cstream : d->stream;  // the call's staging stream
   // a call with node set ids (a plain queue, ke_capi.cpp take_node_sets): the NS instantiations of every kernel that
   // turns a (pod, node) pair into a score or key
-  const bool ns = ctx->ns_call != nullptr;
+  // (NS_SETS), or with score table ids (NS_SCORES: these read the set table too, id 0 = its all-ones row 0)
+  const int ns = ctx->nsc_call ? NS_SCORES : ctx->ns_call ? NS_SETS : 0;
   if (ns) {
-    if ((int64_t)ctx->ns_call_ids.size() != n_pods) return fail(KE_ERR_DEVICE, "internal: node set ids of another call");
+    if ((ctx->ns_call && (int64_t)ctx->ns_call_ids.size() != n_pods) ||
+        (ctx->nsc_call && (int64_t)ctx->nsc_call_ids.size() != n_pods))
+      return fail(KE_ERR_DEVICE, "internal: node set / score table ids of another call");
     rc = node_sets_sync(ctx);
+    if (rc) return rc;
+  }
+  if (ns == NS_SCORES) {
+    rc = node_scores_sync(ctx);
     if (rc) return rc;
   }
   // host-counted copies / fills this call enqueues on the Reserve stream (ke_debug_call_boundary)
@@ -8361,13 +8474,17 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
                               : (numa ? k_eval_batch<false, true, true> : k_eval_batch<false, false, true>))
                         : ds ? (numa ? k_eval_batch<true, true, false> : k_eval_batch<true, false, false>)
                              : (numa ? k_eval_batch<false, true, false>
-                                     : ns ? ((k.flags & AF_EXT) ? k_eval_batch<false, false, false, true, false, true>
-                                                                : k_eval_batch<false, false, false, false, false, true>)
+                                     : ns == NS_SCORES
+                                         ? ((k.flags & AF_EXT) ? k_eval_batch<false, false, false, true, false, NS_SCORES>
+                                                               : k_eval_batch<false, false, false, false, false, NS_SCORES>)
+                                     : ns ? ((k.flags & AF_EXT) ? k_eval_batch<false, false, false, true, false, NS_SETS>
+                                                                : k_eval_batch<false, false, false, false, false, NS_SETS>)
                                           : ((k.flags & AF_EXT) ? k_eval_batch<false, false, false, true>
                                                                 : k_eval_batch<false, false, false>));
         uint32_t* dcnt = numa ? d->d_defer_cnt + b : nullptr;
         if (plain_rec)  // plain batch: the record-based evaluation
-          hipLaunchKernelGGL((ns ? ((k.flags & AF_EXT) ? k_eval_plain<true, true> : k_eval_plain<false, true>)
+          hipLaunchKernelGGL((ns == NS_SCORES ? ((k.flags & AF_EXT) ? k_eval_plain<true, NS_SCORES> : k_eval_plain<false, NS_SCORES>)
+                              : ns ? ((k.flags & AF_EXT) ? k_eval_plain<true, NS_SETS> : k_eval_plain<false, NS_SETS>)
                                  : ((k.flags & AF_EXT) ? k_eval_plain<true> : k_eval_plain<false>)), grid, dim3(eb), 0, es, d->soa,
                              lo, hi, d->d_pods, bbase, bp, k, scores, d->capacity, fold_begin ? estamps + b : nullptr,
                              wait_kernel ? nullptr : dwait, d_err);
@@ -8396,7 +8513,8 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
       // the nodes batch b-2 changed, once it is done (k_patch waits for the flag; folding it into the split select
       // was measured slower: 256 select workgroups spinning on the flag)
       if (pwait)
-        hipLaunchKernelGGL((ns ? ((k.flags & AF_EXT) ? k_patch<true, true> : k_patch<false, true>)
+        hipLaunchKernelGGL((ns == NS_SCORES ? ((k.flags & AF_EXT) ? k_patch<true, NS_SCORES> : k_patch<false, NS_SCORES>)
+                            : ns ? ((k.flags & AF_EXT) ? k_patch<true, NS_SETS> : k_patch<false, NS_SETS>)
                                : ((k.flags & AF_EXT) ? k_patch<true> : k_patch<false>)), dim3((unsigned)bp), dim3(64), d->excl_lds, es,
                            d->soa, d->d_pods, bbase, k, ptl, scores, d->capacity, pwait, d_err);
       if (ds && sharded && !d->loopback) {  // DefaultNormalizeScore's max over the feasible nodes of all ranks
@@ -8513,7 +8631,8 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
       const bool two_es = !fixup && d->estream2 != nullptr && !sharded;
       const bool ahead = two_es && d->eval_patch && d->select_ahead;  // (k_fixlist's lists: descending)
       hipLaunchKernelGGL((quota ? (ext ? k_resolve_run<true, true> : k_resolve_run<true, false>)
-                          : ns  ? (ext ? k_resolve_run<false, true, true> : k_resolve_run<false, false, true>)
+                          : ns == NS_SCORES ? (ext ? k_resolve_run<false, true, NS_SCORES> : k_resolve_run<false, false, NS_SCORES>)
+                          : ns  ? (ext ? k_resolve_run<false, true, NS_SETS> : k_resolve_run<false, false, NS_SETS>)
                                 : (ext ? k_resolve_run<false, true> : k_resolve_run<false, false>)), dim3(1 + th.H), dim3(res_threads<false>()), 0,
                          d->stream, d->soa, d->d_pods, d_bases, r0, e - r0, k, d->d_cand, d->d_cand_cnt, d_chosen,
                          d_chosen_score, ctx->cfg.global_node_offset, d_st, d_pst,
@@ -8537,7 +8656,8 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
             const int32_t* pre_cnt = reinterpret_cast<const int32_t*>(d->d_pre + (size_t)2 * MAX_BATCH * KSTALE2) + (q & 1) * MAX_BATCH;
             const int sp = N > 0 && !batches[q].ds ? select_parts(N, batches[q].pods, KSTALE2) : 1;
             if (d->fix_merge && sp > 1)  // the select left its parts unmerged in the split buffer: the fix merges them
-              hipLaunchKernelGGL((ns ? (ext ? k_fixlist<true, true, true> : k_fixlist<false, true, true>)
+              hipLaunchKernelGGL((ns == NS_SCORES ? (ext ? k_fixlist<true, true, NS_SCORES> : k_fixlist<false, true, NS_SCORES>)
+                                  : ns ? (ext ? k_fixlist<true, true, NS_SETS> : k_fixlist<false, true, NS_SETS>)
                                      : (ext ? k_fixlist<true, true> : k_fixlist<false, true>)), dim3((unsigned)batches[q].pods),
                                  dim3(FIXL_PARTS_BLOCK), 0, es, d->soa, d->d_pods, d_bases + q, k,
                                  alt ? d->d_split2 : d->d_split, nullptr, d_tlist + ((q - 2) & 1) * (1 + MAX_BATCH),
@@ -8545,7 +8665,8 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
                                  d->d_stale + (size_t)(q & 1) * MAX_BATCH * KSTALE, d->d_stale_cnt + (q & 1) * MAX_BATCH,
                                  d_ready + q, d_err, (int64_t)gath_words(KSTALE2), sp);
             else
-              hipLaunchKernelGGL((ns ? (ext ? k_fixlist<true, false, true> : k_fixlist<false, false, true>)
+              hipLaunchKernelGGL((ns == NS_SCORES ? (ext ? k_fixlist<true, false, NS_SCORES> : k_fixlist<false, false, NS_SCORES>)
+                                  : ns ? (ext ? k_fixlist<true, false, NS_SETS> : k_fixlist<false, false, NS_SETS>)
                                      : (ext ? k_fixlist<true> : k_fixlist<false>)), dim3((unsigned)batches[q].pods), dim3(FIXL_BLOCK),
                                  0, es, d->soa, d->d_pods, d_bases + q, k, pre, pre_cnt,
                                  d_tlist + ((q - 2) & 1) * (1 + MAX_BATCH), q - 2 >= r0 ? d_done + (q - 2) : nullptr,
@@ -8572,7 +8693,8 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
         }
         rc = eval_select(q, true, d->estream);
         if (rc) return rc;
-        hipLaunchKernelGGL((ns ? (ext ? k_fixup<true, true> : k_fixup<false, true>) : (ext ? k_fixup<true> : k_fixup<false>)),
+        hipLaunchKernelGGL((ns == NS_SCORES ? (ext ? k_fixup<true, NS_SCORES> : k_fixup<false, NS_SCORES>)
+                            : ns ? (ext ? k_fixup<true, NS_SETS> : k_fixup<false, NS_SETS>) : (ext ? k_fixup<true> : k_fixup<false>)),
                            dim3((unsigned)batches[q].pods), dim3(FIX_BLOCK), 0, d->estream, d->soa, d->d_pods,
                            d_bases + q, k, d->d_stale + (size_t)(q & 1) * MAX_BATCH * KSTALE,
                            d->d_stale_cnt + (q & 1) * MAX_BATCH, d->d_trows, d->d_tcnt, d->d_cand, d->d_cand_cnt,
@@ -8625,7 +8747,8 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
                                  : (numa ? k_resolve<false, true, true> : k_resolve<false, false, true>))
                            : (ds ? (numa ? k_resolve<true, true, false> : k_resolve<true, false, false>)
                                  : (numa ? k_resolve<false, true, false>
-                                         : ns ? k_resolve<false, false, false, true> : k_resolve<false, false, false>));
+                                         : ns == NS_SCORES ? k_resolve<false, false, false, NS_SCORES>
+                                         : ns ? k_resolve<false, false, false, NS_SETS> : k_resolve<false, false, false>));
       hipLaunchKernelGGL(resolve, dim3(1), dim3(numa ? res_threads<true>() : res_threads<false>()), 0, d->stream, d->soa, d->d_pods, bbase, bp, k,
                          d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score, ctx->cfg.global_node_offset,
                          d_st, d_pst, b, d->d_devalloc, d->d_numaalloc, d->d_chg, N,

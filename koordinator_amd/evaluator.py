@@ -234,6 +234,37 @@ class Evaluator:
         ids = np.ascontiguousarray(set_ids, np.int32)
         self._check(self.lib.ke_pod_node_sets(self.h, len(ids), abi.ptr(ids)))
 
+    def node_scores_load(self, tables, n_nodes=None):
+        """ke_node_scores_load: replace the node score offset tables -- `tables` a [n_tables, N] matrix (or a list of
+        rows) of uint16 values, zero-padded to n_nodes when that is larger; table ids are 1 + the row.  An empty
+        list drops the table."""
+        t = np.asarray(tables)
+        if t.size == 0:
+            self._check(self.lib.ke_node_scores_load(self.h, 0, 0, None))
+            return
+        t = np.atleast_2d(t)
+        if (t < 0).any() or (t > 0xFFFF).any():
+            raise ValueError("node score outside 0..65535")
+        n = t.shape[1] if n_nodes is None else int(n_nodes)
+        if n < t.shape[1]:
+            raise ValueError("n_nodes below the tables' width")
+        v = np.zeros((t.shape[0], n), np.uint16)
+        v[:, :t.shape[1]] = t
+        self._check(self.lib.ke_node_scores_load(self.h, v.shape[0], n, abi.ptr(v)))
+
+    def node_scores_set(self, node, column):
+        """ke_node_scores_set: node `node`'s entry in every loaded table (column[t - 1] for table id t)."""
+        c = np.asarray(column).reshape(-1)
+        if (c < 0).any() or (c > 0xFFFF).any():
+            raise ValueError("node score outside 0..65535")
+        c = np.ascontiguousarray(c, np.uint16)
+        self._check(self.lib.ke_node_scores_set(self.h, int(node), len(c), abi.ptr(c) if len(c) else None))
+
+    def pod_node_scores(self, table_ids):
+        """ke_pod_node_scores: the score table id (0 = no offset) per pod of the next eval / schedule / submit."""
+        ids = np.ascontiguousarray(table_ids, np.int32)
+        self._check(self.lib.ke_pod_node_scores(self.h, len(ids), abi.ptr(ids)))
+
     def node_info_requested(self, i):
         """ke_node_info_requested: NodeInfo Requested / NonZeroRequested (MilliCPU, Memory) after the restore."""
         req, nz = (C.c_int64 * 2)(), (C.c_int64 * 2)()
@@ -317,11 +348,14 @@ class Evaluator:
         return lo.value, hi.value
 
     # ---- evaluation -------------------------------------------------------------------------
-    def eval(self, pods, now_ns, node_sets=None):
-        """ke_eval; `node_sets` (optional): the node set id per pod (0 = every node)."""
+    def eval(self, pods, now_ns, node_sets=None, node_scores=None):
+        """ke_eval; `node_sets` (optional): the node set id per pod (0 = every node); `node_scores` (optional): the
+        score table id per pod (0 = no offset)."""
         pods = as_pod_array(pods)
         if node_sets is not None:
             self.pod_node_sets(node_sets)
+        if node_scores is not None:
+            self.pod_node_scores(node_scores)
         P, N = len(pods), self.num_nodes
         out = {
             "status": np.zeros((P, N), np.uint8),
@@ -337,26 +371,31 @@ class Evaluator:
                                      abi.ptr(out["ds"]), abi.ptr(out["total"]), abi.ptr(out["best"])))
         return out
 
-    def schedule(self, pods, now_ns, matches=None, node_sets=None):
+    def schedule(self, pods, now_ns, matches=None, node_sets=None, node_scores=None):
         """ke_schedule; `matches` (optional): per pod the reservation indices it matches (KE_RSV_MATCHED pods);
-        `node_sets` (optional): the node set id per pod (0 = every node)."""
+        `node_sets` (optional): the node set id per pod (0 = every node); `node_scores` (optional): the score table
+        id per pod (0 = no offset)."""
         pods = as_pod_array(pods)
         if matches is not None:
             self.pod_reservations(matches)
         if node_sets is not None:
             self.pod_node_sets(node_sets)
+        if node_scores is not None:
+            self.pod_node_scores(node_scores)
         chosen = np.zeros(len(pods), np.int32)
         score = np.zeros(len(pods), np.int32)
         self._check(self.lib.ke_schedule(self.h, len(pods), abi.ptr(pods), int(now_ns), abi.ptr(chosen), abi.ptr(score)))
         self._last_n, self._last_out = len(pods), {}  # the per-pod allocations are read on first access
         return chosen, score
 
-    def submit(self, pods, now_ns, node_sets=None):
+    def submit(self, pods, now_ns, node_sets=None, node_scores=None):
         """ke_schedule_submit: enqueue a queue slice behind the calls in flight; returns its ticket (wait() collects
-        it).  The pod array is kept alive here until then.  `node_sets` as for schedule()."""
+        it).  The pod array is kept alive here until then.  `node_sets` and `node_scores` as for schedule()."""
         pods = as_pod_array(pods)
         if node_sets is not None:
             self.pod_node_sets(node_sets)
+        if node_scores is not None:
+            self.pod_node_scores(node_scores)
         t = C.c_int64()
         self._check(self.lib.ke_schedule_submit(self.h, len(pods), abi.ptr(pods), int(now_ns), C.byref(t)))
         self._inflight[t.value] = pods
