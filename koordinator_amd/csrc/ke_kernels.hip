@@ -21,11 +21,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ke_cpuacc.h"
 #include "ke_merge.h"
 #include "ke_host.h"
+#include "ke_plan.h"
 #include "ke_types.h"
 
 namespace ke {
@@ -43,15 +46,11 @@ extern "C" __device__ int32_t __ockl_wfred_add_i32(int32_t);
   } while (0)
 
 constexpr int EVAL_BLOCK = 256;
-constexpr int PST = 16;  // replay stamps / counters per batch (ke_debug_resolve_phases)
 // k_eval_batch grid: node tiles padded to a multiple of the 8 XCDs (x) x pod groups (y)
 inline dim3 eval_grid(int n_nodes, int block, int pods, int ppb) {
   const int tiles = (n_nodes + block - 1) / block;
   return dim3((unsigned)((tiles + 7) / 8 * 8), (unsigned)((pods + ppb - 1) / ppb));
 }
-constexpr int SELECT_BLOCK = 1024;
-constexpr int SELECT_WAVES = SELECT_BLOCK / 64;
-constexpr int KMAX = MAX_BATCH;
 
 struct SoA {
   int64_t* f;       // NUM_I64_FIELDS arrays of `stride` int64
@@ -3342,11 +3341,6 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_batch(SoA s, int lo, int hi
 // dependent words are exact doubles, so no int64 -> double conversion or 64-bit subtraction is left per
 // (pod, node).  The pods' estimates / requests as doubles are converted once per block into LDS.
 // Records are written sc1 by the Reserve kernels, so a pipelined eval sees them like the SoA rows.
-constexpr int EVAL_PPB = 8;  // pods per block (eval_grid's pod groups)
-// A plain batch of more than 2 pods is evaluated from the 208-B replay records (k_eval_plain: no int64 ->
-// double work per pair, the record read once per 8 pods); 1-2 pods stream the 148-B SoA rows
-// (k_eval_batch), the smaller read when the pass is bandwidth-bound.
-__host__ __device__ constexpr bool use_record_eval(int pods) { return pods > 2; }
 // NS: the pods' node sets (SoA::ns_ids) -- the block's table words (one a wave and pod, the tile starts at a
 // multiple of 64: lo = 0, set calls are unsharded) are staged in LDS with the pods, a node outside is filtered.
 template <bool EXT, int NS = 0>
@@ -3992,24 +3986,9 @@ __device__ __forceinline__ void load8(const uint16_t* sc, int i, int end, uint32
 }
 
 constexpr int SEL_WINDOW = 64;  // histogram window below the pod's best score
-constexpr int SEL_RC = 8;       // register-resident select: up to SEL_RC * 512 nodes per wave (65,536 per pod)
 constexpr int SEL_COPIES = 8;   // histogram copies per wave (pass 2)
 
-// per-wave node segment of k_select over [lo, hi): a multiple of 512 (one 16-B load per lane per step)
-__host__ __device__ inline int select_seg(int lo, int hi) { return ((hi - lo + SELECT_WAVES - 1) / SELECT_WAVES + 511) & ~511; }
-// workgroups per pod of a plain batch's split k_select over n nodes: >= 256 workgroups in all, parts of
-// >= 4096 nodes, at most MAX_WORLD (k_merge's fan-in)
-// (parts of >= 24576 nodes: at C3's 50k nodes two parts per pod measured 93.5 G against 92.1 G with four and 91.1 G
-// with one -- profiles/r06/ab_select_parts.txt; the split's merge tail costs more than the per-part pass saves.
-// KOORDEVAL_SELECT_PARTS = P, an A/B knob: at most P parts of >= 4096 nodes.)
-inline int select_parts(int64_t n, int bp, int L = 2 * 64) {
-  const char* e = std::getenv("KOORDEVAL_SELECT_PARTS");
-  const int cap = e ? std::max(1, std::min(8, std::atoi(e))) : 8;
-  const int64_t per = e ? 4096 : 24576;
-  return std::max(1, std::min({cap, (255 + bp) / bp, (int)(n / per), 1024 / L}));  // (the merge: parts x L <= 1024)
-}
-// node part of one of `parts` workgroups of a split k_select (512-aligned, like the shard ranges)
-__host__ __device__ inline int select_part(int lo, int hi, int parts) { return ((hi - lo + parts - 1) / parts + 511) & ~511; }
+// (the select's geometry -- select_seg, select_part, select_parts -- is in ke_plan.h)
 
 // it = 0 .. iters-1 over a wave's 512-node steps; RC > 0: a constant trip count (registers indexed by it)
 template <int RC, typename F>
@@ -4062,12 +4041,7 @@ __device__ __forceinline__ uint32_t max_halves(uint32_t w) { return max(w & 0xFF
 // each, every part's top-k_j list in its own block of a gather buffer (`ystride` words apart) for k_merge --
 // the per-shard lists of the node-sharded path, on one GPU (a batch of 64 pods then fills every CU).
 // L = list length (KMAX, or KSTALE for the pipelined schedule's stale lists); outputs use stride L.
-constexpr int KSTALE = 2 * KMAX;  // stale-snapshot list length of the pipelined schedule
-constexpr int KSTALE2 = 3 * KMAX;  // select-ahead list length (k_fixlist: up to KMAX of them are batch b-2's nodes)
-constexpr int gath_words(int L) { return MAX_BATCH * L + MAX_BATCH; }
 constexpr int GATH_WORDS_MAX = MAX_BATCH * KSTALE + MAX_BATCH;
-constexpr int MAX_WORLD = 8;
-static_assert(MAX_WORLD == 8, "select_parts caps the parts at 8");
 constexpr int MERGE_BLOCK = MAX_WORLD * KSTALE;
 
 template <bool SC1, bool SORTED = false>
@@ -6967,6 +6941,35 @@ struct PinnedVec {
   const T* end() const { return p + n; }
 };
 
+// What each of two calls in flight (ke_schedule_submit) needs of its own: `call` is the set of the call being
+// enqueued, `alt` the other one's; device_swap_call_buffers swaps them whole.
+struct CallBufs {
+  PinnedVec<DevPod> host_pods;  // the uploaded queue (batch segmentation), page-locked
+  DevPod* d_pods = nullptr;     // ... on the device, the call's id words and batch bases behind the records
+  int64_t pods_cap = 0;
+  // ke_schedule's read-back block (OutLayout): scores, placements, the call's error word, fixup stamps and the
+  // batch stamps, contiguous in the order the completion reads them, so one copy brings them to h_out
+  uint8_t* d_out = nullptr;
+  uint64_t* d_devalloc = nullptr;  // [n_pods] device minors allocated per pod
+  int64_t* d_numaalloc = nullptr;  // [n_pods][16] per-zone allocation of each pod
+  int64_t out_cap = 0;             // pods (d_out, d_devalloc, d_numaalloc)
+  uint64_t* d_cpusets = nullptr;   // [n_pods][4] cpuset of each pod
+  int64_t cpusets_cap = 0;         // bytes
+  int32_t* d_sched = nullptr;      // ke_schedule bookkeeping (SchedLayout): hand-off flags, the T helpers' lists
+  int64_t sched_cap = 0;           // bytes
+  PinnedVec<uint8_t> h_out;        // the read-back staging (HostOutLayout)
+  std::vector<hipEvent_t> tev;     // the call's events (pool): span, the call's end per stream, samples
+  void swap(CallBufs& o) {
+    host_pods.swap(o.host_pods);
+    h_out.swap(o.h_out);
+    tev.swap(o.tev);
+    std::swap(d_pods, o.d_pods), std::swap(pods_cap, o.pods_cap);
+    std::swap(d_out, o.d_out), std::swap(d_devalloc, o.d_devalloc), std::swap(d_numaalloc, o.d_numaalloc);
+    std::swap(out_cap, o.out_cap), std::swap(d_cpusets, o.d_cpusets), std::swap(cpusets_cap, o.cpusets_cap);
+    std::swap(d_sched, o.d_sched), std::swap(sched_cap, o.sched_cap);
+  }
+};
+
 struct DeviceState {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -6976,9 +6979,7 @@ struct DeviceState {
   Row* d_rows = nullptr;
   int32_t* d_idx = nullptr;
   int64_t staging_cap = 0;
-  // pods
-  DevPod* d_pods = nullptr;
-  int64_t pods_cap = 0;
+  CallBufs call, alt;
   DevPodHint* d_ph = nullptr;  // the hinted pods' records of the current call
   int64_t ph_cap = 0;
   // node eligibility sets: rows 0 .. ns_n of capacity / 64 words (row 0 all ones); a call's set ids
@@ -6995,12 +6996,6 @@ struct DeviceState {
   uint32_t* d_cand = nullptr;    // [MAX_BATCH][KMAX]
   int32_t* d_cand_cnt = nullptr;
   int32_t* d_batch_base = nullptr;  // a zero word (batch base of the parity / bench launches)
-  int32_t* d_sched = nullptr;       // ke_schedule bookkeeping: hand-off flags, the T helpers' lists
-  int64_t sched_cap = 0;            // bytes
-  // ke_schedule's read-back block (OutLayout): scores, placements, the call's error word, fixup stamps and the
-  // batch stamps, contiguous in the order the completion reads them, so one copy brings them to h_out
-  uint8_t* d_out = nullptr;
-  int64_t out_cap = 0;              // pods (d_out, d_devalloc, d_numaalloc)
   // parity outputs
   void* d_parity = nullptr;
   int64_t parity_cap = 0;
@@ -7022,11 +7017,8 @@ struct DeviceState {
   size_t pt_words = 0;           // soa.pt capacity (uint64 words)
   uint16_t* d_dsraw = nullptr;   // [capacity] raw DeviceShare score + 1 of the batch's DeviceShare pod
   uint32_t* d_dsmax = nullptr;   // 1 + max raw score over the feasible nodes of the batch's pod
-  uint64_t* d_devalloc = nullptr;  // [n_pods] device minors allocated per pod
   int64_t* d_dsrows = nullptr;   // staging for DeviceShare row uploads
   int64_t ds_staging_cap = 0;
-  PinnedVec<DevPod> host_pods;    // the last uploaded queue (batch segmentation), page-locked
-  PinnedVec<uint8_t> h_out;       // ke_schedule's readback staging (placements, allocations, stamps)
   PinnedVec<int64_t> h_refresh[2];  // device_refresh's row staging (every table's rows + indices), two in turn
   PinnedVec<uint8_t> h_rsv;       // a matched pod's RsvPair / RsvOvr uploads
   PinnedVec<int32_t> h_rsv_out;   // k_rsv_pick's result words, read back by the call's own copies
@@ -7034,7 +7026,6 @@ struct DeviceState {
   std::vector<DevPodHint> host_ph;  // its hinted pods' records (the async upload reads them)
   // NUMA topology
   bool numa_alloc = false;         // soa.nf / soa.nm allocated
-  int64_t* d_numaalloc = nullptr;  // [n_pods][16] per-zone allocation of each pod (ke_schedule)
   int64_t* d_numarows = nullptr;   // staging for NUMA row uploads
   int64_t numa_staging_cap = 0;
   bool ext_alloc = false;          // soa.xf / soa.xm allocated (NodeResourcesFitPlus / ScarceResourceAvoidance)
@@ -7048,39 +7039,14 @@ struct DeviceState {
   bool cpu_alloc = false;          // soa.cs / soa.cpu allocated
   int64_t* d_cpurows = nullptr;    // staging for CPU table uploads
   int64_t cpu_staging_cap = 0;     // nodes
-  uint64_t* d_cpusets = nullptr;   // [n_pods][4] cpuset of each pod (ke_schedule)
-  int64_t cpusets_cap = 0;         // bytes
   uint8_t* d_aff = nullptr;        // [capacity] NUMA affinity per node of a singleton batch's eval
   // pipelined schedule: eval + select run on `estream` one batch ahead of the Reserve chain on `stream`
   hipStream_t estream = nullptr;
-  // a call's staging copies (pod upload, bookkeeping words) and read-back run on `cstream`: the next call's uploads
-  // proceed while this one still runs, and the Reserve stream goes from one call's Reserve kernel to the next.
-  // Opt-in (KOORDEVAL_STAGING_STREAM=1): on the C3 bench it measured 78-85 G against 92 G with everything on `stream`
-  // (tools/_ab.sh, one box, alternated), so by default the staging work stays on `stream` (nullptr here)
-  hipStream_t cstream = nullptr;
-  hipEvent_t ev_setup = nullptr, ev_rend = nullptr;
   // a second eval stream with its own score matrix / part lists: consecutive batches of a stale-list run
   // alternate between the two, so batch b+1's eval overlaps batch b's select (nullptr: clusters too large to
   // double the score matrix)
   hipStream_t estream2 = nullptr;
   hipEvent_t ev_sel2 = nullptr;
-  std::vector<hipEvent_t> tev;  // device_schedule's events (pool): span, the call's end per stream, samples
-  // the other call's buffers of two in flight (ke_schedule_submit): swapped with the fields of the same name
-  struct CallBufs {
-    PinnedVec<DevPod> host_pods;
-    DevPod* d_pods = nullptr;
-    int64_t pods_cap = 0;
-    uint8_t* d_out = nullptr;
-    uint64_t* d_devalloc = nullptr;
-    int64_t* d_numaalloc = nullptr;
-    int64_t out_cap = 0;
-    uint64_t* d_cpusets = nullptr;
-    int64_t cpusets_cap = 0;
-    int32_t* d_sched = nullptr;
-    int64_t sched_cap = 0;
-    PinnedVec<uint8_t> h_out;
-    std::vector<hipEvent_t> tev;
-  } alt;
   uint16_t* d_scores2 = nullptr;
   uint32_t* d_split2 = nullptr;
   uint32_t* d_stale = nullptr;      // [2][MAX_BATCH][KSTALE] stale-snapshot candidate lists
@@ -7101,7 +7067,6 @@ struct DeviceState {
   int refresh_cur = 0;
   std::vector<std::function<void(const int32_t*)>> deferred;  // device_refresh(defer): its scatters, gated
   int32_t* d_rsv_gate = nullptr;    // k_rsv_check's word: a fused matched pod's speculation failed (1)
-  bool refresh_sync = false;        // KOORDEVAL_REFRESH_SYNC=1: the host waits for every refresh (A/B)
   bool pipeline = true;             // ke_set_pipeline
   bool pipe_fixup = false;          // ke_set_pipeline(2): exact lists from k_fixup for every run (else quota runs only)
   // dynamic LDS of the eval streams' LDS-free kernels: more than what a Reserve workgroup (ResLds) leaves free of
@@ -7127,13 +7092,6 @@ struct DeviceState {
   int32_t* d_rsv_out = nullptr;     // [4]
   RsvPickSt* d_rsv_st = nullptr;    // k_rsv_stage's words (node-sharded contexts)
 };
-
-// Contiguous node range of shard `rank`: 512-aligned chunks (k_select's 16-B loads stay aligned).
-void shard_range(int n_nodes, int rank, int world, int* lo, int* hi) {
-  const int chunk = ((n_nodes + world - 1) / world + 511) & ~511;
-  *lo = std::min(rank * chunk, n_nodes);
-  *hi = std::min(*lo + chunk, n_nodes);
-}
 
 static int ensure(void** p, int64_t* cap, int64_t bytes) {
   if (*cap >= bytes) return KE_OK;
@@ -7168,14 +7126,9 @@ int device_create(Context* ctx) {
   if (const char* e = std::getenv("KOORDEVAL_EVAL_PATCH")) d->eval_patch = std::atoi(e) != 0;
   if (const char* e = std::getenv("KOORDEVAL_SELECT_AHEAD")) d->select_ahead = std::atoi(e) != 0;
   if (const char* e = std::getenv("KOORDEVAL_FIX_MERGE")) d->fix_merge = std::atoi(e) != 0;
-  if (const char* e = std::getenv("KOORDEVAL_REFRESH_SYNC")) d->refresh_sync = std::atoi(e) != 0;
   if (const char* e = std::getenv("KOORDEVAL_T_HELPERS_IGNORE")) d->t_help_ignore = std::atoi(e) != 0;
   HIP_OK(hipStreamCreateWithPriority(&d->stream, hipStreamNonBlocking, prio_hi));
   HIP_OK(hipStreamCreateWithPriority(&d->estream, hipStreamNonBlocking, prio_lo));
-  if (const char* e = std::getenv("KOORDEVAL_STAGING_STREAM"); e && std::atoi(e) != 0)
-    HIP_OK(hipStreamCreateWithPriority(&d->cstream, hipStreamNonBlocking, prio_lo));
-  HIP_OK(hipEventCreateWithFlags(&d->ev_setup, hipEventDisableTiming));
-  HIP_OK(hipEventCreateWithFlags(&d->ev_rend, hipEventDisableTiming));
   for (int e = 0; e < DeviceState::EV_RING; e++) {
     HIP_OK(hipEventCreateWithFlags(&d->ev_res[e], hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags(&d->ev_sel[e], hipEventDisableTiming));
@@ -7335,12 +7288,12 @@ void device_destroy(Context* ctx) {
   (void)hipSetDevice(d->device);
   if (d->stream) (void)hipStreamSynchronize(d->stream);
   if (d->comm) (void)ncclCommDestroy(d->comm);
-  void* ptrs[] = {d->soa.f,     d->soa.flags, d->d_rows,      d->d_idx,          d->d_pods,   d->d_scores,
-                  d->d_cand,    d->d_cand_cnt, d->d_batch_base, d->d_out,
+  void* ptrs[] = {d->soa.f,     d->soa.flags, d->d_rows,      d->d_idx,          d->d_scores,
+                  d->d_cand,    d->d_cand_cnt, d->d_batch_base,
                   d->d_parity, d->d_best,      d->d_gath,    d->d_split,         d->soa.ds,   d->soa.dsm,
-                  d->d_dsraw,   d->d_dsmax,  d->d_devalloc,   d->d_dsrows,       d->soa.nf,   d->soa.nm,
-                  d->d_numaalloc, d->d_numarows, d->d_defer, d->d_defer_cnt, d->soa.cs, d->soa.cpu,
-                  d->d_cpurows, d->d_cpusets, d->d_aff, d->soa.qt, d->soa.qm, d->d_sched, d->d_stale,
+                  d->d_dsraw,   d->d_dsmax,  d->d_dsrows,       d->soa.nf,   d->soa.nm,
+                  d->d_numarows, d->d_defer, d->d_defer_cnt, d->soa.cs, d->soa.cpu,
+                  d->d_cpurows, d->d_aff, d->soa.qt, d->soa.qm, d->d_stale,
                   d->d_stale_cnt, d->d_pre, d->d_trows, d->d_tcnt, d->d_parts_done, d->d_scores2, d->d_split2, d->d_chg, d->soa.rec, d->soa.pt, d->soa.kerr,
                   d->soa.xf, d->soa.xm, d->d_xrows, d->soa.dsx, d->d_ph, d->d_vfo, d->d_rsv, d->d_rsv_out, d->d_rsv_st,
                   d->d_rsv_views, d->d_ds_views, d->d_numa_views, d->d_rovr, d->d_rsv_gate, d->d_ns_tbl, d->d_nsc_tbl};
@@ -7356,15 +7309,13 @@ void device_destroy(Context* ctx) {
   for (hipEvent_t e : d->ev_refresh)
     if (e) (void)hipEventDestroy(e);
   if (d->estream) (void)hipStreamDestroy(d->estream);
-  if (d->cstream) (void)hipStreamDestroy(d->cstream);
-  if (d->ev_setup) (void)hipEventDestroy(d->ev_setup);
-  if (d->ev_rend) (void)hipEventDestroy(d->ev_rend);
   if (d->estream2) (void)hipStreamDestroy(d->estream2);
   if (d->ev_sel2) (void)hipEventDestroy(d->ev_sel2);
-  for (auto& e : d->tev) (void)hipEventDestroy(e);
-  for (auto& e : d->alt.tev) (void)hipEventDestroy(e);
-  for (void* p : {(void*)d->alt.d_pods, (void*)d->alt.d_out, (void*)d->alt.d_devalloc, (void*)d->alt.d_numaalloc, (void*)d->alt.d_cpusets, (void*)d->alt.d_sched})
-    if (p) (void)hipFree(p);
+  for (CallBufs* c : {&d->call, &d->alt}) {
+    for (auto& e : c->tev) (void)hipEventDestroy(e);
+    for (void* p : {(void*)c->d_pods, (void*)c->d_out, (void*)c->d_devalloc, (void*)c->d_numaalloc, (void*)c->d_cpusets, (void*)c->d_sched})
+      if (p) (void)hipFree(p);
+  }
   if (d->stream) (void)hipStreamDestroy(d->stream);
   delete d;
   ctx->dev = nullptr;
@@ -7837,12 +7788,8 @@ int device_refresh_flush(Context* ctx, const int32_t* gate) {
   HIP_OK(hipGetLastError());
   // no host wait: the staging is reused only after ev_refresh (above), and the kernels reading the rows run on
   // `stream` after the scatters or wait for an event recorded there after them (device_schedule_enqueue's ev_start)
-  if (d->refresh_sync) {
-    HIP_OK(hipStreamSynchronize(d->stream));
-  } else {
-    HIP_OK(hipEventRecord(d->ev_refresh[d->refresh_cur], d->stream));
-    d->refresh_pending[d->refresh_cur] = true;
-  }
+  HIP_OK(hipEventRecord(d->ev_refresh[d->refresh_cur], d->stream));
+  d->refresh_pending[d->refresh_cur] = true;
   return KE_OK;
 }
 
@@ -7929,13 +7876,11 @@ static int node_scores_sync(Context* ctx) {
 // The call's upload block: the DevPod records, the node set ids when present (int32 each) and room for
 // tail_words more int32 words, laid out alike in the page-locked host_pods and in d_pods, so one copy carries
 // it.  Without `tail` the block is copied here; with it the caller fills *tail (ke_schedule's batch bases) and
-// copies *block_bytes itself.  *copies counts the copies enqueued on ustream.
-static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, hipStream_t ustream = nullptr,
-                       int64_t tail_words = 0, int32_t** tail = nullptr, int64_t* block_bytes = nullptr,
+// copies *block_bytes itself.  *copies counts the copies enqueued (on the Reserve stream).
+static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t tail_words = 0, int32_t** tail = nullptr, int64_t* block_bytes = nullptr,
                        int* copies = nullptr) {
   DeviceState* d = ctx->dev;
-  if (!ustream) ustream = d->stream;
-  PinnedVec<DevPod>& dp = d->host_pods;
+  PinnedVec<DevPod>& dp = d->call.host_pods;
   // the call's node set ids and score table ids (a non-zero one among either): one word per pod behind the
   // records, the set id alone or -- in a call with table ids -- (table id << 16) | set id
   const int32_t* ns = ctx->ns_call;
@@ -7960,25 +7905,25 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, hipStre
     }
   }
   const int64_t bytes = sizeof(DevPod) * (int64_t)n_pods + sizeof(int32_t) * (ns_words + tail_words);
-  int rc = ensure((void**)&d->d_pods, &d->pods_cap, std::max<int64_t>(bytes, (int64_t)sizeof(DevPod)));
+  int rc = ensure((void**)&d->call.d_pods, &d->call.pods_cap, std::max<int64_t>(bytes, (int64_t)sizeof(DevPod)));
   if (rc) return rc;
   int32_t* const h_words = reinterpret_cast<int32_t*>(dp.data() + n_pods);
   d->soa.ns_ids = nullptr;
   if (ns || sc) {
     static_assert(KE_MAX_NODE_SETS < (1 << 16) && KE_MAX_NODE_SCORE_TABLES < (1 << 15), "the packed id word");
     for (int32_t p = 0; p < n_pods; p++) h_words[p] = (ns ? ns[p] : 0) | (sc ? sc[p] << 16 : 0);
-    d->soa.ns_ids = reinterpret_cast<int32_t*>(d->d_pods + n_pods);
+    d->soa.ns_ids = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods);
   }
   if (tail) *tail = h_words + ns_words;
   if (block_bytes) *block_bytes = bytes;
   if (!tail && bytes) {
-    HIP_OK(hipMemcpyAsync(d->d_pods, dp.data(), (size_t)bytes, hipMemcpyHostToDevice, ustream));
+    HIP_OK(hipMemcpyAsync(d->call.d_pods, dp.data(), (size_t)bytes, hipMemcpyHostToDevice, d->stream));
     if (copies) ++*copies;
   }
   if (!ph.empty()) {
     rc = ensure((void**)&d->d_ph, &d->ph_cap, sizeof(DevPodHint) * (int64_t)ph.size());
     if (rc) return rc;
-    HIP_OK(hipMemcpyAsync(d->d_ph, ph.data(), sizeof(DevPodHint) * ph.size(), hipMemcpyHostToDevice, ustream));
+    HIP_OK(hipMemcpyAsync(d->d_ph, ph.data(), sizeof(DevPodHint) * ph.size(), hipMemcpyHostToDevice, d->stream));
     if (copies) ++*copies;
   }
   d->soa.ph = d->d_ph;
@@ -7986,6 +7931,109 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, hipStre
   // recorded on d->stream after them; dp / ph stay untouched until the call's final synchronisation
   return KE_OK;
 }
+
+// ---- the dispatcher ----------------------------------------------------------------------------------------------------
+// From a launch's runtime flags to the kernel instantiation, one function per kernel family.  Which instantiations
+// exist is written here and nowhere else: a launch site names the family and passes flags.  A combination without
+// an instantiation gives nullptr (the launch site fails with KE_ERR_DEVICE), never a neighbouring kernel; ke_capi.cpp
+// (take_node_sets) refuses those calls first, so none arrives.  Each function is a few compares and a pointer.
+#define KV(c) decltype(c)::value
+template <class F>
+static auto with_bool(bool v, F&& f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
+// NS (per-pod node sets / score tables) x EXT (FitPlus / SRA in the plain evaluation): the kernels that turn a plain
+// batch's (pod, node) pair into a score or key carry both
+template <class F>
+static auto with_ns_ext(int ns, bool ext, F&& f) {
+  auto e = [&](auto NS) { return with_bool(ext, [&](auto EXT) { return f(NS, EXT); }); };
+  return ns == NS_SCORES ? e(std::integral_constant<int, NS_SCORES>{})
+         : ns            ? e(std::integral_constant<int, NS_SETS>{})
+                         : e(std::integral_constant<int, 0>{});
+}
+template <class F>
+static auto with_ns(int ns, F&& f) {
+  return with_ns_ext(ns, false, [&](auto NS, auto) { return f(NS); });
+}
+
+using EvalParityFn = decltype(&k_eval_parity<false, false>);
+static EvalParityFn pick_eval_parity(bool numa, bool cpu, int ns) {
+  return with_ns(ns, [&](auto NS) {
+    return with_bool(numa, [&](auto NUMA) {
+      return with_bool(cpu, [&](auto CPU) -> EvalParityFn { return k_eval_parity<KV(NUMA), KV(CPU), KV(NS)>; });
+    });
+  });
+}
+static auto pick_parity_finalize(int ns) {
+  return with_bool(ns == NS_SCORES, [](auto SC) { return k_parity_finalize<KV(SC)>; });
+}
+// DS x NUMA x CPU; the plain instantiation (none of them) also NS x EXT, and a DeviceShare one the hint path H (a
+// hinted pod without a DeviceShare request is evaluated without it, as a plain pod is).  EXT is the plain
+// instantiation's alone: eval_pair reads AF_EXT at run time.
+using EvalBatchFn = decltype(&k_eval_batch<false, false, false>);
+static EvalBatchFn pick_eval_batch(bool ds, bool numa, bool cpu, bool hint, bool ext, int ns) {
+  if (!ds && !numa && !cpu)
+    return with_ns_ext(ns, ext, [](auto NS, auto EXT) -> EvalBatchFn {
+      return k_eval_batch<false, false, false, KV(EXT), false, KV(NS)>;
+    });
+  if (ns) return nullptr;
+  return with_bool(numa, [&](auto NUMA) {
+    return with_bool(cpu, [&](auto CPU) -> EvalBatchFn {
+      if (ds && hint) return k_eval_batch<true, KV(NUMA), KV(CPU), false, true>;
+      return ds ? k_eval_batch<true, KV(NUMA), KV(CPU)> : k_eval_batch<false, KV(NUMA), KV(CPU)>;
+    });
+  });
+}
+static auto pick_eval_plain(bool ext, int ns) {
+  return with_ns_ext(ns, ext, [](auto NS, auto EXT) { return k_eval_plain<KV(EXT), KV(NS)>; });
+}
+static auto pick_patch(bool ext, int ns) {
+  return with_ns_ext(ns, ext, [](auto NS, auto EXT) { return k_patch<KV(EXT), KV(NS)>; });
+}
+static auto pick_fixup(bool ext, int ns) {
+  return with_ns_ext(ns, ext, [](auto NS, auto EXT) { return k_fixup<KV(EXT), KV(NS)>; });
+}
+// parts: the select left its parts unmerged in the split buffer and the fix merges them first
+static auto pick_fixlist(bool ext, bool parts, int ns) {
+  return with_ns_ext(ns, ext, [&](auto NS, auto EXT) {
+    return parts ? k_fixlist<KV(EXT), true, KV(NS)> : k_fixlist<KV(EXT), false, KV(NS)>;
+  });
+}
+// DS x NUMA x QUOTA, and NS for the plain instantiation
+using ResolveFn = decltype(&k_resolve<false, false, false>);
+static ResolveFn pick_resolve(bool ds, bool numa, bool quota, int ns) {
+  if (!ds && !numa && !quota) return with_ns(ns, [](auto NS) -> ResolveFn { return k_resolve<false, false, false, KV(NS)>; });
+  if (ns) return nullptr;
+  return with_bool(ds, [&](auto DS) {
+    return with_bool(numa, [&](auto NUMA) {
+      return with_bool(quota, [](auto QUOTA) -> ResolveFn { return k_resolve<KV(DS), KV(NUMA), KV(QUOTA)>; });
+    });
+  });
+}
+static unsigned resolve_threads(bool numa) { return numa ? res_threads<true>() : res_threads<false>(); }
+// QUOTA x EXT, or NS x EXT without quota
+using ResolveRunFn = decltype(&k_resolve_run<false, false>);
+static ResolveRunFn pick_resolve_run(bool quota, bool ext, int ns) {
+  if (quota) return ns ? nullptr : with_bool(ext, [](auto EXT) -> ResolveRunFn { return k_resolve_run<true, KV(EXT)>; });
+  return with_ns_ext(ns, ext, [](auto NS, auto EXT) -> ResolveRunFn { return k_resolve_run<false, KV(EXT), KV(NS)>; });
+}
+static auto pick_select(bool ds, bool resident) {
+  return with_bool(ds, [&](auto DS) { return resident ? k_select<KV(DS), SEL_RC> : k_select<KV(DS), 0>; });
+}
+static auto pick_argmax1(bool ds) {
+  return with_bool(ds, [](auto DS) { return k_argmax1<KV(DS)>; });
+}
+static auto pick_numa_fallback(bool parity, bool cpu) {
+  return with_bool(parity, [&](auto P) { return cpu ? k_numa_fallback<KV(P), true> : k_numa_fallback<KV(P), false>; });
+}
+static auto pick_numa_finish(bool parity, bool cpu) {
+  return with_bool(parity, [&](auto P) { return cpu ? k_numa_finish<KV(P), true> : k_numa_finish<KV(P), false>; });
+}
+static auto pick_cpuset_reserve(bool ds, bool numa) {
+  return with_bool(ds, [&](auto DS) { return numa ? k_cpuset_reserve<KV(DS), true> : k_cpuset_reserve<KV(DS), false>; });
+}
+#undef KV
+static int no_variant(const char* what) { return fail(KE_ERR_DEVICE, std::string("internal: no kernel variant for ") + what); }
 
 int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, uint8_t* status, uint8_t* reason,
                 int16_t* la, int16_t* numa, int16_t* ds, int16_t* total, int32_t* best) {
@@ -8024,7 +8072,7 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
   const KArgs k = make_kargs(ctx, now);
   const int ppb = EVAL_PPB;
   bool cpu = false;
-  for (const DevPod& q : d->host_pods) cpu = cpu || (q.flags & PF_CPUSET);
+  for (const DevPod& q : d->call.host_pods) cpu = cpu || (q.flags & PF_CPUSET);
   if (cpu && !d->cpu_alloc) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
   if (N > 0) {
     dim3 grid((unsigned)((N + EVAL_BLOCK - 1) / EVAL_BLOCK), (unsigned)((P + ppb - 1) / ppb));
@@ -8034,29 +8082,25 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
       rc = ensure((void**)&d->d_defer_cnt, &d->defer_cnt_cap, sizeof(uint32_t));
       if (rc) return rc;
       HIP_OK(hipMemsetAsync(d->d_defer_cnt, 0, sizeof(uint32_t), d->stream));
-      hipLaunchKernelGGL((ns == NS_SCORES ? (cpu ? k_eval_parity<true, true, NS_SCORES> : k_eval_parity<true, false, NS_SCORES>)
-                          : ns ? (cpu ? k_eval_parity<true, true, NS_SETS> : k_eval_parity<true, false, NS_SETS>)
-                             : (cpu ? k_eval_parity<true, true> : k_eval_parity<true, false>)), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->d_pods, (int)P,
+      hipLaunchKernelGGL(pick_eval_parity(true, cpu, ns), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->call.d_pods, (int)P,
                          ppb, k, d_status, d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, d->d_defer, d->d_defer_cnt);
       HIP_OK(hipGetLastError());
       uint32_t* fb = reinterpret_cast<uint32_t*>(d->d_defer + M);
-      hipLaunchKernelGGL((cpu ? k_numa_fallback<true, true> : k_numa_fallback<true, false>), dim3(FALLBACK_BLOCKS),
-                         dim3(64), 0, d->stream, d->soa, d->d_pods,
+      hipLaunchKernelGGL(pick_numa_fallback(true, cpu), dim3(FALLBACK_BLOCKS),
+                         dim3(64), 0, d->stream, d->soa, d->call.d_pods,
                          d->d_batch_base, k, d->d_defer, d->d_defer_cnt, d->d_scores, d->capacity, (int)N, d_status,
                          d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, nullptr, nullptr, fb);
-      hipLaunchKernelGGL((cpu ? k_numa_finish<true, true> : k_numa_finish<true, false>), dim3(FINISH_BLOCKS),
-                         dim3(64), 0, d->stream, d->soa, d->d_pods,
+      hipLaunchKernelGGL(pick_numa_finish(true, cpu), dim3(FINISH_BLOCKS),
+                         dim3(64), 0, d->stream, d->soa, d->call.d_pods,
                          d->d_batch_base, k, d->d_defer, d->d_defer_cnt, d->d_scores, d->capacity, (int)N, d_status,
                          d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, nullptr, nullptr, fb);
     } else {
-      hipLaunchKernelGGL((ns == NS_SCORES ? (cpu ? k_eval_parity<false, true, NS_SCORES> : k_eval_parity<false, false, NS_SCORES>)
-                          : ns ? (cpu ? k_eval_parity<false, true, NS_SETS> : k_eval_parity<false, false, NS_SETS>)
-                             : (cpu ? k_eval_parity<false, true> : k_eval_parity<false, false>)), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->d_pods, (int)P,
+      hipLaunchKernelGGL(pick_eval_parity(false, cpu, ns), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->call.d_pods, (int)P,
                          ppb, k, d_status, d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, nullptr, nullptr);
     }
     HIP_OK(hipGetLastError());
     dim3 grid2((unsigned)((N + EVAL_BLOCK - 1) / EVAL_BLOCK), (unsigned)P);
-    hipLaunchKernelGGL((ns == NS_SCORES ? k_parity_finalize<true> : k_parity_finalize<false>), grid2, dim3(EVAL_BLOCK), 0,
+    hipLaunchKernelGGL(pick_parity_finalize(ns), grid2, dim3(EVAL_BLOCK), 0,
                        d->stream, (int)N, k, d_ds, d_total, d_dsmax, d->d_best, d->soa);
     HIP_OK(hipGetLastError());
   }
@@ -8085,20 +8129,7 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
 // outputs, stamps, hand-off words, readback staging and events are per call).
 void device_swap_call_buffers(Context* ctx) {
   DeviceState* d = ctx->dev;
-  DeviceState::CallBufs& a = d->alt;
-  d->host_pods.swap(a.host_pods);
-  std::swap(d->d_pods, a.d_pods);
-  std::swap(d->pods_cap, a.pods_cap);
-  std::swap(d->d_out, a.d_out);
-  std::swap(d->d_devalloc, a.d_devalloc);
-  std::swap(d->d_numaalloc, a.d_numaalloc);
-  std::swap(d->out_cap, a.out_cap);
-  std::swap(d->d_cpusets, a.d_cpusets);
-  std::swap(d->cpusets_cap, a.cpusets_cap);
-  std::swap(d->d_sched, a.d_sched);
-  std::swap(d->sched_cap, a.sched_cap);
-  d->h_out.swap(a.h_out);
-  d->tev.swap(a.tev);
+  d->call.swap(d->alt);
 }
 
 // a failed enqueue may have left part of its launches on the streams: wait for every stream of the context
@@ -8140,752 +8171,71 @@ int device_schedule(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t no
   return fin(chosen, score);
 }
 
-int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, bool want_score,
-                            DevFinish* fin) {
-  DeviceState* d = ctx->dev;
-  using clk = std::chrono::steady_clock;
-  auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
-  auto tp = clk::now();
-  HIP_OK(hipSetDevice(d->device));
-  const bool fused = ctx->rsv_fused;  // the last pod: a matched pod behind plain ones (its rows' scatters deferred)
-  int rc = device_refresh(ctx, now, fused);
-  if (rc) return rc;
-  ctx->host_ms[1] = ms_since(tp);
-  ctx->last_batch_ms.clear();
-  ctx->last_dev_alloc.clear();
-  ctx->last_total_ms = 0;
-  ctx->last_pod_lat.clear();
-  if (n_pods == 0) return KE_OK;
-  tp = clk::now();
-  hipStream_t const cs = d->cstream ? d->cstream : d->stream;  // the call's staging stream
-  // a call with node set ids (a plain queue, ke_capi.cpp take_node_sets): the NS instantiations of every kernel that
-  // turns a (pod, node) pair into a score or key
-  // (NS_SETS), or with score table ids (NS_SCORES: these read the set table too, id 0 = its all-ones row 0)
-  const int ns = ctx->nsc_call ? NS_SCORES : ctx->ns_call ? NS_SETS : 0;
-  if (ns) {
-    if ((ctx->ns_call && (int64_t)ctx->ns_call_ids.size() != n_pods) ||
-        (ctx->nsc_call && (int64_t)ctx->nsc_call_ids.size() != n_pods))
-      return fail(KE_ERR_DEVICE, "internal: node set / score table ids of another call");
-    rc = node_sets_sync(ctx);
-    if (rc) return rc;
-  }
-  if (ns == NS_SCORES) {
-    rc = node_scores_sync(ctx);
-    if (rc) return rc;
-  }
-  // host-counted copies / fills this call enqueues on the Reserve stream (ke_debug_call_boundary)
-  int n_copies = 0, n_fills = 0;
-  auto copy_async = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
-    n_copies += s == d->stream;
-    return hipMemcpyAsync(dst, src, bytes, kind, s);
-  };
-  auto fill_async = [&](void* dst, int v, size_t bytes, hipStream_t s) {
-    n_fills += s == d->stream;
-    return hipMemsetAsync(dst, v, bytes, s);
-  };
-  // the upload block: records, node set ids, then the batch bases (at most one batch per pod, and the end);
-  // copied once the bases are known
-  int32_t* h_bases = nullptr;
-  int64_t upload_bytes = 0;
-  int ph_copies = 0;
-  rc = upload_pods(ctx, n_pods, pods, cs, (int64_t)n_pods + 1, &h_bases, &upload_bytes, &ph_copies);
-  if (rc) return rc;
-  n_copies += cs == d->stream ? ph_copies : 0;
-  ctx->host_ms[2] = ms_since(tp);
-  tp = clk::now();
-  // Batches: runs of up to B pods without DeviceShare requests (exact speculative batching, DESIGN.md
-  // §4), and every DeviceShare pod alone: its NormalizeScore needs the max over all feasible nodes of
-  // the current state.
-  // A pod that may bind CPUs is alone in its batch too: its Reserve runs the CPU accumulator
-  // (k_cpuset_reserve) and may fail, and later pods read the CPU table it patches.
-  const int B = ctx->cfg.pod_batch;
-  struct Batch {
-    int pods;
-    bool ds, cpu;  // DeviceShare-capable batch (its pods' NormalizeScore) / singleton of a pod that may bind CPUs
-    bool cut;      // a DeviceShare batch with DeviceShare pods: the replay may stop early
-    bool hint;     // singleton of a pod with device hints: its eval kernel carries the hint path (H)
-  };
+// ---- one ke_schedule call: plan (ke_plan.h), enqueue in named steps (ScheduleCall), completion (Completion) ----------
+using clk = std::chrono::steady_clock;
+static double ms_since(clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); }
+// sampled per-kernel HIP event pairs (ke_set_profiling) on the eval stream, per sampled batch: eval start, eval end,
+// select end, select start (after k_patch and its wait)
+constexpr int PE = 4;
+
+// What a call's completion needs once its enqueue has returned.  ctx and its DeviceState outlive every call.  Two
+// pointers must stay valid until the completion has run: `pods` (the caller's queue: ke_schedule_submit's caller
+// keeps it until the wait) and `h`, the page-locked h_out of the call's buffer set (the next call takes the other
+// set, and a third is not enqueued before this one completed).  The events are the buffer set's pool's.
+struct Completion {
+  Context* ctx;
   std::vector<Batch> batches;
-  // DeviceShare pods share batches (exact: the replay checks each pod's normalisation max and stops the
-  // batch where it may have moved) unless the nodes are sharded or carry NUMA policies (then
-  // each is a singleton batch)
-  const bool ds_batch = !(d->world > 1 || d->comm || d->host_fn) && !d->numa_alloc && ctx->n_nodes > 0;
-  ctx->last_ds_cuts = 0;
-  for (int32_t p = 0; p < n_pods;) {
-    const uint32_t f = d->host_pods[p].flags;
-    if ((f & PF_CPUSET) || ((f & PF_DS) && !ds_batch) || (f & PF_DS_HINT) || (fused && p == n_pods - 1)) {
-      // hinted pods and a fused matched pod: singletons
-      batches.push_back({1, (f & PF_DS) != 0, (f & PF_CPUSET) != 0, false, (f & PF_DS_HINT) != 0});
-      p++;
-      continue;
-    }
-    int bp = 0;
-    bool has_ds = false, ds_pods = false;
-    while (p + bp < n_pods && bp < B && !(fused && p + bp == n_pods - 1)) {
-      const uint32_t g = d->host_pods[p + bp].flags;
-      if ((g & PF_CPUSET) || ((g & PF_DS) && !ds_batch) || (g & PF_DS_HINT)) break;
-      has_ds = has_ds || (g & PF_DS);
-      ds_pods = ds_pods || (g & PF_DS);
-      bp++;
-    }
-    batches.push_back({bp, has_ds, false, ds_pods && bp > 1, false});
-    p += bp;
-  }
-  bool any_cpu = false;
-  for (const Batch& b : batches) any_cpu = any_cpu || b.cpu;
-  if (any_cpu && !d->cpu_alloc) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
-  const int n_batches = (int)batches.size();
-  const int64_t out_bytes = sizeof(int32_t) * (int64_t)n_pods;
-  // The read-back block, device and h_out alike (16-byte aligned parts): scores, placements, the call's error
-  // word, the fixup stamps [2 nb], the batch end stamps [nb + 1] (st[0]: the call's start), the replay stamps
-  // [PST nb], the eval start stamps [nb] -- and, not read back, one more eval stamp (a re-run remainder's)
-  struct OutLayout {
-    size_t score, chosen, err, fst, st, pst, est, end, total;
-    OutLayout(size_t np, size_t nb) {
-      size_t off = 0;
-      auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = (off + bytes + 15) & ~(size_t)15;
-        return o;
-      };
-      score = take(4 * np), chosen = take(4 * np), err = take(8), fst = take(16 * nb), st = take(8 * (nb + 1));
-      pst = take(8 * PST * nb), est = take(8 * nb);
-      end = est + 8 * nb;
-      total = est + 8 * (nb + 1);
-    }
-  };
-  if (d->out_cap < n_pods) {
-    if (d->d_out) HIP_OK(hipFree(d->d_out));
-    if (d->d_devalloc) HIP_OK(hipFree(d->d_devalloc));
-    if (d->d_numaalloc) HIP_OK(hipFree(d->d_numaalloc));
-    d->d_out = nullptr;
-    d->d_devalloc = nullptr;
-    d->d_numaalloc = nullptr;
-    d->out_cap = 0;
-    HIP_OK(hipMalloc(&d->d_out, OutLayout((size_t)n_pods, (size_t)n_pods).total));  // (n_batches <= n_pods)
-    HIP_OK(hipMalloc(&d->d_devalloc, sizeof(uint64_t) * n_pods));
-    d->out_cap = n_pods;
-  }
-  const OutLayout ol((size_t)n_pods, (size_t)n_batches);
-  int32_t* const d_chosen = reinterpret_cast<int32_t*>(d->d_out + ol.chosen);
-  int32_t* const d_chosen_score = reinterpret_cast<int32_t*>(d->d_out + ol.score);
-  int32_t* const d_err = reinterpret_cast<int32_t*>(d->d_out + ol.err);
-  uint64_t* const d_fst = reinterpret_cast<uint64_t*>(d->d_out + ol.fst);
-  uint64_t* const d_st = reinterpret_cast<uint64_t*>(d->d_out + ol.st);
-  uint64_t* const d_pst = reinterpret_cast<uint64_t*>(d->d_out + ol.pst);
-  // (every singleton batch's k_cpuset_reserve writes its pod's entry; the table is read back, and so zeroed by
-  // k_call_begin, only in a call with a cpuset pod)
-  rc = ensure((void**)&d->d_cpusets, &d->cpusets_cap, sizeof(uint64_t) * 4 * (int64_t)n_pods);
-  if (rc) return rc;
-  bool any_hint = false;
-  for (const DevPod& q : d->host_pods) any_hint = any_hint || (q.flags & PF_DS_HINT);
-  d->soa.vfo = nullptr;
-  if (any_hint) {  // the VF ranks the hinted pods' Reserves take
-    rc = ensure((void**)&d->d_vfo, &d->vfo_cap, 2 * DS_MINORS * (int64_t)n_pods);
-    if (rc) return rc;
-    HIP_OK(fill_async(d->d_vfo, 0xFF, 2 * DS_MINORS * (size_t)n_pods, d->stream));
-    d->soa.vfo = d->d_vfo;
-  }
-  const bool numa = d->numa_alloc;
-  if (numa && !d->d_numaalloc) HIP_OK(hipMalloc(&d->d_numaalloc, sizeof(int64_t) * 16 * d->out_cap));
-  if (numa) {  // deferred-pair list of one batch (reused) + a counter per batch
-    rc = ensure((void**)&d->d_defer, &d->defer_cap, (sizeof(uint64_t) + sizeof(uint32_t)) * MAX_BATCH * d->capacity);
-    if (rc) return rc;
-    rc = ensure((void**)&d->d_defer_cnt, &d->defer_cnt_cap, sizeof(uint32_t) * n_batches);
-    if (rc) return rc;
-    HIP_OK(fill_async(d->d_defer_cnt, 0, sizeof(uint32_t) * n_batches, d->stream));
-  }
-  KArgs k = make_kargs(ctx, now);
-  if (ctx->rsv_affinity) k.flags |= AF_RSV_ONLY;  // the Reservation Filter: RsvOvr.rfilter of the pod's nodes
-  if (!ctx->rsv_pairs.empty() || ctx->rsv_affinity) {  // one matched pod (ke_schedule's segment of its own)
-    if (n_pods != 1 && !fused) return fail(KE_ERR_UNSUPPORTED, "matched reservations need a singleton segment");
-    for (const RsvPair& q : ctx->rsv_pairs)
-      if (q.node < 0 || q.node >= ctx->n_nodes) return fail(KE_ERR_DEVICE, "reservation pair node out of range");
-    rc = ensure((void**)&d->d_rsv, &d->rsv_cap, (int64_t)sizeof(RsvPair) * (int64_t)ctx->rsv_pairs.size());
-    if (rc) return rc;
-  }
-  if (fused || !ctx->rsv_pairs.empty() || ctx->rsv_affinity) {
-    if (!d->h_rsv_out.resize(5)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the reservation staging");
-    for (int i = 0; i < 4; i++) d->h_rsv_out[i] = -1;
-    d->h_rsv_out[4] = 0;  // the fused pod's gate (k_rsv_check)
-  }
-  if (fused && !d->d_rsv_gate) HIP_OK(hipMalloc(&d->d_rsv_gate, sizeof(int32_t)));
-  // the matched pod's pairs and allocate-from-reservation decisions, staged page-locked (the previous call's copies
-  // from this buffer completed with that call)
-  const size_t rsv_bytes = sizeof(RsvPair) * ctx->rsv_pairs.size(), ovr_bytes = sizeof(RsvOvr) * ctx->rsv_ovr.size();
-  if (rsv_bytes + ovr_bytes && !d->h_rsv.resize(rsv_bytes + ovr_bytes))
-    return fail(KE_ERR_DEVICE, "hipHostMalloc of the reservation staging");
-  if (!ctx->rsv_pairs.empty() || ctx->rsv_affinity) {
-    if (rsv_bytes) {
-      std::memcpy(d->h_rsv.data(), ctx->rsv_pairs.data(), rsv_bytes);
-      HIP_OK(copy_async(d->d_rsv, d->h_rsv.data(), rsv_bytes, hipMemcpyHostToDevice, d->stream));
-    }
-    HIP_OK(fill_async(d->d_rsv_out, 0xFF, sizeof(int32_t) * 4, d->stream));
-  }
-  d->soa.n_rovr = 0;  // a matched pod's allocate-from-reservation decisions (NF_RSV_CS rows read them)
-  if (!ctx->rsv_ovr.empty()) {
-    rc = ensure((void**)&d->d_rovr, &d->rovr_cap, (int64_t)sizeof(RsvOvr) * (int64_t)ctx->rsv_ovr.size());
-    if (rc) return rc;
-    std::memcpy(d->h_rsv.data() + rsv_bytes, ctx->rsv_ovr.data(), ovr_bytes);
-    HIP_OK(copy_async(d->d_rovr, d->h_rsv.data() + rsv_bytes, ovr_bytes, hipMemcpyHostToDevice, d->stream));
-    d->soa.rovr = d->d_rovr;
-    d->soa.n_rovr = (int32_t)ctx->rsv_ovr.size();
-  }
-  const bool quota = !ctx->quotas.empty();  // ElasticQuota admission + Reserve in the Reserve kernels
-  if (quota) {
-    if (ctx->quota_dirty) {
-      rc = device_quota_upload(ctx);
-      if (rc) return rc;
-    }
-    k.flags |= AF_QUOTA | (ctx->qargs.enable_check_parent_quota ? AF_QUOTA_PARENT : 0u);
-  }
-  const int N = ctx->n_nodes;
-  const int ppb = EVAL_PPB;
-  // first pod of every batch and the end (the kernels' batch base pointer is d_bases + b)
-  std::vector<int32_t> bases((size_t)n_batches + 1);
-  for (int b = 0, p = 0; b <= n_batches; b++) {
-    bases[b] = p;
-    if (b < n_batches) p += batches[b].pods;
-  }
-  // pipelined runs: maximal stretches of plain batches (no DeviceShare / cpuset pod) in a
-  // context without NUMA policies; run_end[b] > 0 marks the first batch of a run and holds its end
-  // (a lone plain batch between singletons gains nothing from the second stream: it runs serially)
-  auto eligible = [&](int b) {
-    return d->pipeline && N > 0 && !numa && !batches[b].ds && !batches[b].cpu && !(fused && b == n_batches - 1);
-  };
-  std::vector<int> run_end((size_t)n_batches, 0);
-  for (int b = 0; b < n_batches;) {
-    if (!eligible(b)) {
-      b++;
-      continue;
-    }
-    int e = b;
-    while (e < n_batches && eligible(e)) e++;
-    if (e - b >= 2) run_end[b] = e;
-    b = e;
-  }
-  // d_sched: ready [n], done [n], T-helper counts [n], select-started counts [n], the Reserve kernels' residency
-  // flags [n] (by run start), each with a spare word; the T helpers' lists and maxima (THelp).  The batch bases
-  // [n+1] lie in the upload block behind the records (and node set ids); the error word and the fixup stamps in
-  // the read-back block.
-  const int64_t sched_words = (5 * ((int64_t)n_batches + 1) + 1) & ~1LL;  // (the lists behind stay 8-byte aligned)
-  constexpr int64_t THELP_WORDS = 2 * (1 + MAX_BATCH) + 2 * MAX_BATCH;
-  rc = ensure((void**)&d->d_sched, &d->sched_cap, sizeof(int32_t) * (sched_words + THELP_WORDS));
-  if (rc) return rc;
-  int32_t* d_bases = reinterpret_cast<int32_t*>(d->d_pods + n_pods) + (ns ? n_pods : 0);
-  int32_t* d_ready = d->d_sched;
-  int32_t* d_done = d_ready + n_batches + 1;
-  int32_t* d_tready = d_done + n_batches + 1;
-  int32_t* d_sstart = d_tready + n_batches + 1;
-  int32_t* d_rres = d_sstart + n_batches + 1;
-  int32_t* d_tlist = d->d_sched + sched_words;
-  uint32_t* d_tmx = reinterpret_cast<uint32_t*>(d_tlist + 2 * (1 + MAX_BATCH));
-  const bool sharded = d->world > 1 || d->comm || d->host_fn;
-  // one copy for everything the call uploads (on its staging stream)
-  std::copy(bases.begin(), bases.end(), h_bases);
-  HIP_OK(copy_async(d->d_pods, d->host_pods.data(), (size_t)(upload_bytes - (int64_t)sizeof(int32_t) * (n_pods - n_batches)),
-                    hipMemcpyHostToDevice, cs));
-  HIP_OK(hipEventRecord(d->ev_setup, cs));
-  // sampled per-kernel HIP event pairs (ke_set_profiling) on the eval stream: eval, select
-  constexpr int PE = 4;  // eval start, eval end, select end, select start (after k_patch and its wait)
-  const int every = d->profile_every;
-  // the call's timing events (the whole span, the samples) come from the context's pool: creating them per call
-  // cost the host ~3 us an event
-  const size_t n_tev = 5 + (every > 0 ? (size_t)((n_batches + every - 1) / every) * PE : 0);
-  while (d->tev.size() < n_tev) {
-    hipEvent_t e;
-    HIP_OK(hipEventCreate(&e));
-    d->tev.push_back(e);
-  }
-  hipEvent_t e0 = d->tev[0], e1 = d->tev[1];
-  const hipEvent_t done_ev[3] = {d->tev[2], d->tev[3], d->tev[4]};  // the call's end on each stream
-  std::vector<hipEvent_t> ev(d->tev.begin() + 5, d->tev.begin() + (long)n_tev);
-  HIP_OK(hipStreamWaitEvent(d->stream, d->ev_setup, 0));
-  HIP_OK(hipEventRecord(e0, d->stream));
-  {
-    // the call's own words start at zero: the hand-off words, the error word and the fixup stamps (adjacent in
-    // the read-back block), the cpuset table when a pod may bind CPUs; and the call's start stamp.  (The split
-    // selects' counters stay zero between calls -- an aborted call resets them.)
-    const int64_t nw_out = (int64_t)(ol.st - ol.err) / 4, nw_cs = any_cpu ? 8 * (int64_t)n_pods : 0;
-    const int64_t nw = std::max(std::max(sched_words, nw_out), nw_cs);
-    hipLaunchKernelGGL(k_call_begin, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, d->stream,
-                       reinterpret_cast<uint32_t*>(d->d_sched), sched_words, reinterpret_cast<uint32_t*>(d_err), nw_out,
-                       reinterpret_cast<uint32_t*>(d->d_cpusets), nw_cs, d_st);
-  }
-  HIP_OK(hipEventRecord(d->ev_start, d->stream));
-  HIP_OK(hipStreamWaitEvent(d->estream, d->ev_start, 0));
-  uint64_t* estamps = reinterpret_cast<uint64_t*>(d->d_out + ol.est);  // eval start of each batch
-  constexpr int R = DeviceState::EV_RING;
-  int n_pipelined = 0;
-  // Batch b's eval + candidate lists on stream `es`.  pipe: stale top-(k_j + KMAX) lists into the run's
-  // stale buffer (k_fixup makes them exact); else the exact top-k_j lists straight into d_cand.
-  bool rerun = false;  // the current serial batch is the remainder of a DeviceShare batch that stopped early
-  int pre_b = -1;      // a serial batch whose eval + select is already enqueued (behind a DeviceShare cut check)
-  // dwait (pipelined, stale lists): the eval first waits for that done flag -- in k_eval_plain itself, else a
-  // k_handoff ahead of it; rpub: the select publishes the lists to the running Reserve kernel itself when it
-  // can (split or one-workgroup select, unsharded) -- *published tells the caller
-  bool published = false;
-  auto eval_select = [&](int b, bool pipe, hipStream_t es, const int32_t* dwait = nullptr,
-                         int32_t* rpub = nullptr, bool alt = false, const int32_t* pwait = nullptr,
-                         const int32_t* ptl = nullptr, int32_t* sstart = nullptr, int32_t dwant = 1,
-                         bool pre = false) -> int {
-    published = false;
-    uint16_t* const scores = alt ? d->d_scores2 : d->d_scores;  // (the second eval stream's buffers)
-    uint32_t* const split = alt ? d->d_split2 : d->d_split;
-    int32_t* const pdone = d->d_parts_done + (alt ? MAX_BATCH : 0);
-    const int bp = batches[b].pods;
-    const bool ds = batches[b].ds, cpu = batches[b].cpu;
-    const bool prof = every > 0 && b % every == 0;
-    hipEvent_t* pe = prof ? &ev[(size_t)(b / every) * PE] : nullptr;
-    const int32_t* bbase = d_bases + b;
-    const bool argmax1 = !sharded && bp == 1 && !pipe && N > 0;  // selectHost of one pod: a grid-wide argmax
-    // this rank's node range (unsharded and loopback: every node)
-    int lo = 0, hi = N;
-    if (N > 0 && sharded && !d->loopback) shard_range(N, d->rank, d->world, &lo, &hi);
-    // a plain batch with nodes to evaluate: k_eval_batch writes the eval-start stamp itself (one launch
-    // less on the eval stream); else k_batch_begin — a re-run remainder keeps its batch's first dequeue
-    // stamp (latency counts from there)
-    const bool fold_begin = !ds && !argmax1 && !rerun && hi > lo;
-    if (!fold_begin)
-      hipLaunchKernelGGL(k_batch_begin, dim3(1), dim3(MAX_BATCH), 0, es, estamps + (rerun ? n_batches : b), ds ? d->d_dsmax : nullptr,
-                         argmax1 ? d->d_cand : nullptr);
-    // (with two eval streams the wait is a one-wave kernel ahead of the eval, outside its timing: an eval grid
-    // spinning on the flag would hold the CUs the other stream's select needs)
-    const bool plain_rec = !cpu && !ds && !numa && use_record_eval(bp);
-    const bool wait_kernel = dwait && (!plain_rec || alt || (d->estream2 != nullptr && !sharded) || hi <= lo);
-    if (wait_kernel) hipLaunchKernelGGL(k_handoff, dim3(1), dim3(64), d->excl_lds, es, nullptr, 0, dwait, d_err, nullptr, dwant);
-    if (prof) HIP_OK(hipEventRecord(pe[0], es));
-    // (select-ahead: top-(k_j + 2 KMAX) into the pre-fix buffer, k_fixlist makes the Reserve kernel's lists)
-    const int L = pre ? KSTALE2 : pipe ? KSTALE : KMAX, kext = pre ? 2 * KMAX : pipe ? KMAX : 0;
-    uint32_t* lists = pre ? d->d_pre + (size_t)(b & 1) * MAX_BATCH * KSTALE2
-                          : pipe ? d->d_stale + (size_t)(b & 1) * MAX_BATCH * KSTALE : d->d_cand;
-    int32_t* lists_cnt = pre ? reinterpret_cast<int32_t*>(d->d_pre + (size_t)2 * MAX_BATCH * KSTALE2) + (b & 1) * MAX_BATCH
-                             : pipe ? d->d_stale_cnt + (b & 1) * MAX_BATCH : d->d_cand_cnt;
-    if (N > 0) {
-      const bool single = bp == 1;
-      if (hi > lo) {
-        // a singleton batch has one pod's worth of lanes: single-wave blocks spread it over every CU
-        const int eb = single ? 64 : EVAL_BLOCK;
-        const dim3 grid = eval_grid(hi - lo, eb, bp, ppb);
-        auto eval = (ds && batches[b].hint)
-                        ? (cpu ? (numa ? k_eval_batch<true, true, true, false, true> : k_eval_batch<true, false, true, false, true>)
-                               : (numa ? k_eval_batch<true, true, false, false, true> : k_eval_batch<true, false, false, false, true>))
-                  : cpu ? (ds ? (numa ? k_eval_batch<true, true, true> : k_eval_batch<true, false, true>)
-                              : (numa ? k_eval_batch<false, true, true> : k_eval_batch<false, false, true>))
-                        : ds ? (numa ? k_eval_batch<true, true, false> : k_eval_batch<true, false, false>)
-                             : (numa ? k_eval_batch<false, true, false>
-                                     : ns == NS_SCORES
-                                         ? ((k.flags & AF_EXT) ? k_eval_batch<false, false, false, true, false, NS_SCORES>
-                                                               : k_eval_batch<false, false, false, false, false, NS_SCORES>)
-                                     : ns ? ((k.flags & AF_EXT) ? k_eval_batch<false, false, false, true, false, NS_SETS>
-                                                                : k_eval_batch<false, false, false, false, false, NS_SETS>)
-                                          : ((k.flags & AF_EXT) ? k_eval_batch<false, false, false, true>
-                                                                : k_eval_batch<false, false, false>));
-        uint32_t* dcnt = numa ? d->d_defer_cnt + b : nullptr;
-        if (plain_rec)  // plain batch: the record-based evaluation
-          hipLaunchKernelGGL((ns == NS_SCORES ? ((k.flags & AF_EXT) ? k_eval_plain<true, NS_SCORES> : k_eval_plain<false, NS_SCORES>)
-                              : ns ? ((k.flags & AF_EXT) ? k_eval_plain<true, NS_SETS> : k_eval_plain<false, NS_SETS>)
-                                 : ((k.flags & AF_EXT) ? k_eval_plain<true> : k_eval_plain<false>)), grid, dim3(eb), 0, es, d->soa,
-                             lo, hi, d->d_pods, bbase, bp, k, scores, d->capacity, fold_begin ? estamps + b : nullptr,
-                             wait_kernel ? nullptr : dwait, d_err);
-        else
-          hipLaunchKernelGGL(eval, grid, dim3(eb), 0, es, d->soa, lo, hi, d->d_pods, bbase, bp,
-                             ppb, k, scores, d->capacity, d->d_dsraw, d->d_defer, dcnt, d->d_aff, d->d_dsmax,
-                             fold_begin ? estamps + b : nullptr);
-        if (numa) {  // a DeviceShare pod defers only on nodes without a device cache (no DeviceShare hints there)
-          uint32_t* fb = reinterpret_cast<uint32_t*>(d->d_defer + (int64_t)MAX_BATCH * d->capacity);
-          hipLaunchKernelGGL((cpu ? k_numa_fallback<false, true> : k_numa_fallback<false, false>), dim3(FALLBACK_BLOCKS),
-                             dim3(64), 0, es, d->soa, d->d_pods,
-                             bbase, k, d->d_defer, dcnt, scores, d->capacity, 0, nullptr, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, ds ? d->d_dsmax : nullptr, cpu ? d->d_aff : nullptr,
-                             ds ? d->d_dsraw : nullptr, fb);
-          hipLaunchKernelGGL((cpu ? k_numa_finish<false, true> : k_numa_finish<false, false>), dim3(FINISH_BLOCKS),
-                             dim3(64), 0, es, d->soa, d->d_pods,
-                             bbase, k, d->d_defer, dcnt, scores, d->capacity, 0, nullptr, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, ds ? d->d_dsmax : nullptr, cpu ? d->d_aff : nullptr,
-                             ds ? d->d_dsraw : nullptr, fb);
-        }
-      }
-      if (prof) HIP_OK(hipEventRecord(pe[1], es));
-      // a plain batch over many nodes: its pods' selections split over several workgroups each (>= 256
-      // workgroups in all, parts of >= 4096 nodes), merged by k_merge
-      const int parts = ds ? 1 : select_parts(N, bp, L);
-      // the nodes batch b-2 changed, once it is done (k_patch waits for the flag; folding it into the split select
-      // was measured slower: 256 select workgroups spinning on the flag)
-      if (pwait)
-        hipLaunchKernelGGL((ns == NS_SCORES ? ((k.flags & AF_EXT) ? k_patch<true, NS_SCORES> : k_patch<false, NS_SCORES>)
-                            : ns ? ((k.flags & AF_EXT) ? k_patch<true, NS_SETS> : k_patch<false, NS_SETS>)
-                               : ((k.flags & AF_EXT) ? k_patch<true> : k_patch<false>)), dim3((unsigned)bp), dim3(64), d->excl_lds, es,
-                           d->soa, d->d_pods, bbase, k, ptl, scores, d->capacity, pwait, d_err);
-      if (ds && sharded && !d->loopback) {  // DefaultNormalizeScore's max over the feasible nodes of all ranks
-        const int crc = coll_all_reduce(d, d->d_dsmax, 1, KE_COLL_U32, KE_COLL_MAX, es);
-        if (crc) return crc;
-      }
-      if (prof) HIP_OK(hipEventRecord(pe[3], es));
-      auto select = [&](int slo, int shi, uint32_t* cand, int32_t* cnt, int32_t* pub) {
-        // register-resident when a wave's segment fits SEL_RC steps, else streamed
-        const bool rc = select_seg(slo, shi) <= SEL_RC * 512;
-        auto sel = ds ? (rc ? k_select<true, SEL_RC> : k_select<true, 0>) : (rc ? k_select<false, SEL_RC> : k_select<false, 0>);
-        hipLaunchKernelGGL(sel, dim3((unsigned)bp), dim3(SELECT_BLOCK), 0, es, scores, d->capacity, slo, shi, cand,
-                           cnt, d->d_dsraw, d->d_dsmax, k.wp_ds, kext, L, (int64_t)0, nullptr, nullptr, nullptr, pub, sstart);
-      };
-      if (argmax1) {  // d_cand[0] zeroed by k_batch_begin
-        hipLaunchKernelGGL((ds ? k_argmax1<true> : k_argmax1<false>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0,
-                           es, scores, 0, N, d->d_dsraw, d->d_dsmax, k.wp_ds, d->d_cand, d->d_cand_cnt);
-        if ((!ctx->rsv_pairs.empty() || ctx->rsv_affinity) && (!fused || b == n_batches - 1)) {
-          // the pod's matched reservations: the Reservation plugin
-          hipLaunchKernelGGL(k_rsv_pick, dim3(1), dim3(64), 0, es, scores, d->d_rsv, (int)ctx->rsv_pairs.size(),
-                             (int64_t)ctx->cfg.weight_reservation, (int)ctx->rsv_affinity, d->d_cand, d->d_rsv_out,
-                             ds ? d->d_dsraw : nullptr, d->d_dsmax, k.wp_ds);
-          HIP_OK(copy_async(d->h_rsv_out.data(), d->d_rsv_out, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, es));
-        }
-      } else if (!sharded && parts > 1) {
-        const int gw = gath_words(L);
-        const bool rc = select_seg(0, select_part(0, N, parts)) <= SEL_RC * 512;
-        // (select-ahead: no parts_done -- the parts stay sorted in `split` and k_fixlist<PARTS> merges them)
-        hipLaunchKernelGGL((rc ? k_select<false, SEL_RC> : k_select<false, 0>), dim3((unsigned)bp, (unsigned)parts),
-                           dim3(SELECT_BLOCK), 0, es, scores, d->capacity, 0, (int)N, split,
-                           reinterpret_cast<int32_t*>(split + MAX_BATCH * L), d->d_dsraw, d->d_dsmax, k.wp_ds,
-                           kext, L, (int64_t)gw, lists, lists_cnt, (pre && d->fix_merge) ? nullptr : pdone, rpub,
-                           sstart);  // the last part merges
-        published = rpub != nullptr;
-      } else if (!sharded) {
-        select(0, N, lists, lists_cnt, ds ? nullptr : rpub);
-        published = rpub != nullptr && !ds;
-      } else {
-        // node-sharded: per-shard top-k_j, all-gather, merge
-        const int gw = gath_words(L);
-        for (int r = 0; r < d->world; r++) {
-          if (!d->loopback && r != d->rank) continue;
-          int slo, shi;
-          shard_range(N, r, d->world, &slo, &shi);
-          uint32_t* blk = d->d_gath + (int64_t)r * gw;
-          select(slo, shi, blk, reinterpret_cast<int32_t*>(blk + MAX_BATCH * L), nullptr);
-        }
-        if (!d->loopback) {
-          uint32_t* mine = d->d_gath + (int64_t)d->rank * gw;  // in place: send = own block of recv
-          const int crc = coll_all_gather(d, mine, d->d_gath, (size_t)gw, es);
-          if (crc) return crc;
-        }
-        hipLaunchKernelGGL(k_merge, dim3((unsigned)bp), dim3(MERGE_BLOCK), 0, es, d->d_gath, d->world, L, kext,
-                           lists, lists_cnt);
-        if (!ctx->rsv_pairs.empty() || ctx->rsv_affinity) {  // a matched singleton: the Reservation plugin in stages
-          int rlo = 0, rhi = N;
-          if (!d->loopback) shard_range(N, d->rank, d->world, &rlo, &rhi);
-          const int K = (int)ctx->rsv_pairs.size();
-          const int64_t wr = (int64_t)ctx->cfg.weight_reservation;
-          const int aff = (int)ctx->rsv_affinity;
-          RsvPickSt* st = d->d_rsv_st;
-          const uint16_t* rds = ds ? d->d_dsraw : nullptr;
-          const bool coll = !d->loopback && (d->comm || d->host_fn);
-          int crc = 0;
-          hipLaunchKernelGGL(k_rsv_stage<0>, dim3(1), dim3(64), 0, es, scores, d->d_rsv, K, rlo, rhi, wr, aff, lists, st, d->d_rsv_out, rds, d->d_dsmax, k.wp_ds);
-          if (coll && (crc = coll_all_reduce(d, &st->order, 1, KE_COLL_I64, KE_COLL_MIN, es))) return crc;
-          hipLaunchKernelGGL(k_rsv_stage<1>, dim3(1), dim3(64), 0, es, scores, d->d_rsv, K, rlo, rhi, wr, aff, lists, st, d->d_rsv_out, rds, d->d_dsmax, k.wp_ds);
-          if (coll && (crc = coll_all_reduce(d, &st->node, 1, KE_COLL_I32, KE_COLL_MIN, es))) return crc;
-          hipLaunchKernelGGL(k_rsv_stage<2>, dim3(1), dim3(64), 0, es, scores, d->d_rsv, K, rlo, rhi, wr, aff, lists, st, d->d_rsv_out, rds, d->d_dsmax, k.wp_ds);
-          if (coll && (crc = coll_all_reduce(d, &st->mx, 1, KE_COLL_I32, KE_COLL_MAX, es))) return crc;
-          hipLaunchKernelGGL(k_rsv_stage<3>, dim3(1), dim3(64), 0, es, scores, d->d_rsv, K, rlo, rhi, wr, aff, lists, st, d->d_rsv_out, rds, d->d_dsmax, k.wp_ds);
-          if (coll && (crc = coll_all_reduce(d, &st->best, 1, KE_COLL_U64, KE_COLL_MAX, es))) return crc;
-          hipLaunchKernelGGL(k_rsv_stage<4>, dim3(1), dim3(64), 0, es, scores, d->d_rsv, K, rlo, rhi, wr, aff, lists, st, d->d_rsv_out, rds, d->d_dsmax, k.wp_ds);
-          if (coll && (crc = coll_all_reduce(d, &st->wt, 2, KE_COLL_I32, KE_COLL_MAX, es))) return crc;  // wt, nw
-          hipLaunchKernelGGL(k_rsv_stage<5>, dim3(1), dim3(64), 0, es, scores, d->d_rsv, K, rlo, rhi, wr, aff, lists, st, d->d_rsv_out, rds, d->d_dsmax, k.wp_ds);
-          HIP_OK(copy_async(d->h_rsv_out.data(), d->d_rsv_out, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, es));
-        }
-      }
-    } else {
-      if (prof) HIP_OK(hipEventRecord(pe[1], es));
-      if (prof) HIP_OK(hipEventRecord(pe[3], es));
-      HIP_OK(fill_async(lists_cnt, 0, sizeof(int32_t) * MAX_BATCH, es));
-    }
-    if (prof) HIP_OK(hipEventRecord(pe[2], es));
-    return KE_OK;
-  };
-  // Two streams (pipelining).  A run of plain batches: one persistent k_resolve_run on
-  // `stream` resolves them all; on `estream` batch b's eval + select run while batch b-1 is being
-  // resolved (they see the Reserves of batches <= b-2), and k_fixup waits for batch b-1's done flag,
-  // re-evaluates the nodes it chose and publishes the exact lists.  Any other batch (DeviceShare /
-  // cpuset singletons, NUMA-policy contexts, pipeline off) is serial: its eval waits for the previous
-  // batch's Reserve (HIP events), its lists are exact, its Reserve kernel waits for its lists.
-  // the candidate lists of batches [b0, e) are in descending key order: they come out of a merge (split or
-  // node-sharded select), not straight out of one k_select workgroup (unordered)
-  auto run_sorted = [&](int b0, int e) {
-    for (int b = b0; b < e; b++) {
-      const int bp = batches[b].pods;
-      if (N <= 0 || batches[b].ds) return false;
-      if (sharded) continue;
-      if (select_parts(N, bp) <= 1) return false;
-    }
-    return true;
-  };
-  ctx->host_ms[3] = ms_since(tp);
-  const auto host_t0 = std::chrono::steady_clock::now();
-  for (int b = 0; b < n_batches;) {
-    if (run_end[b] > 0) {
-      const int r0 = b, e = run_end[b];
-      const bool ext = (k.flags & AF_EXT) != 0;
-      const bool fixup = quota || d->pipe_fixup;  // the replay_batch path (quota) needs exact lists
-      const THelp th{d_tlist, d_tmx, d_tready, fixup ? 0 : d->t_helpers, d->t_help_ignore, d_rres + r0};
-      // batches alternate between the eval streams -- unsharded only: a node-sharded batch's all-gather must run
-      // in the same order on every rank's communicator, which two streams of one rank would not guarantee
-      const bool two_es = !fixup && d->estream2 != nullptr && !sharded;
-      const bool ahead = two_es && d->eval_patch && d->select_ahead;  // (k_fixlist's lists: descending)
-      hipLaunchKernelGGL((quota ? (ext ? k_resolve_run<true, true> : k_resolve_run<true, false>)
-                          : ns == NS_SCORES ? (ext ? k_resolve_run<false, true, NS_SCORES> : k_resolve_run<false, false, NS_SCORES>)
-                          : ns  ? (ext ? k_resolve_run<false, true, NS_SETS> : k_resolve_run<false, false, NS_SETS>)
-                                : (ext ? k_resolve_run<false, true> : k_resolve_run<false, false>)), dim3(1 + th.H), dim3(res_threads<false>()), 0,
-                         d->stream, d->soa, d->d_pods, d_bases, r0, e - r0, k, d->d_cand, d->d_cand_cnt, d_chosen,
-                         d_chosen_score, ctx->cfg.global_node_offset, d_st, d_pst,
-                         d->d_devalloc, d_ready, d_done, d_err, d->d_trows, d->d_tcnt, d->d_chg, N,
-                         fixup ? nullptr : d->d_stale, fixup ? nullptr : d->d_stale_cnt, (int)(ahead || run_sorted(r0, e)), th);
-      if (r0 > 0) HIP_OK(hipStreamWaitEvent(d->estream, d->ev_res[(r0 - 1) % R], 0));
-      if (two_es) HIP_OK(hipStreamWaitEvent(d->estream2, r0 > 0 ? d->ev_res[(r0 - 1) % R] : d->ev_start, 0));
-      for (int q = r0; q < e; q++) {
-        const bool first = q == r0;
-        if (!fixup) {  // the stale lists go to the replay as they are; batch q's eval waits for batch q-2's done
-          const bool alt = two_es && ((q - r0) & 1);
-          hipStream_t es = alt ? d->estream2 : d->estream;
-          if (ahead) {
-            // select-ahead: batch q's eval waits for batch q-3 (the first two of the run for the Reserve kernel's
-            // residency: k_fixlist workgroups spinning on a done flag must never keep it off the CUs), its select
-            // follows at once, and k_fixlist brings in batch q-2's changed nodes and publishes the lists
-            const int32_t* ew = q - 3 >= r0 ? d_done + (q - 3) : q - 2 < r0 ? d_rres + r0 : nullptr;
-            rc = eval_select(q, true, es, ew, nullptr, alt, nullptr, nullptr, nullptr, 1, true);
-            if (rc) return rc;
-            const uint32_t* pre = d->d_pre + (size_t)(q & 1) * MAX_BATCH * KSTALE2;
-            const int32_t* pre_cnt = reinterpret_cast<const int32_t*>(d->d_pre + (size_t)2 * MAX_BATCH * KSTALE2) + (q & 1) * MAX_BATCH;
-            const int sp = N > 0 && !batches[q].ds ? select_parts(N, batches[q].pods, KSTALE2) : 1;
-            if (d->fix_merge && sp > 1)  // the select left its parts unmerged in the split buffer: the fix merges them
-              hipLaunchKernelGGL((ns == NS_SCORES ? (ext ? k_fixlist<true, true, NS_SCORES> : k_fixlist<false, true, NS_SCORES>)
-                                  : ns ? (ext ? k_fixlist<true, true, NS_SETS> : k_fixlist<false, true, NS_SETS>)
-                                     : (ext ? k_fixlist<true, true> : k_fixlist<false, true>)), dim3((unsigned)batches[q].pods),
-                                 dim3(FIXL_PARTS_BLOCK), 0, es, d->soa, d->d_pods, d_bases + q, k,
-                                 alt ? d->d_split2 : d->d_split, nullptr, d_tlist + ((q - 2) & 1) * (1 + MAX_BATCH),
-                                 q - 2 >= r0 ? d_done + (q - 2) : nullptr,
-                                 d->d_stale + (size_t)(q & 1) * MAX_BATCH * KSTALE, d->d_stale_cnt + (q & 1) * MAX_BATCH,
-                                 d_ready + q, d_err, (int64_t)gath_words(KSTALE2), sp);
-            else
-              hipLaunchKernelGGL((ns == NS_SCORES ? (ext ? k_fixlist<true, false, NS_SCORES> : k_fixlist<false, false, NS_SCORES>)
-                                  : ns ? (ext ? k_fixlist<true, false, NS_SETS> : k_fixlist<false, false, NS_SETS>)
-                                     : (ext ? k_fixlist<true> : k_fixlist<false>)), dim3((unsigned)batches[q].pods), dim3(FIXL_BLOCK),
-                                 0, es, d->soa, d->d_pods, d_bases + q, k, pre, pre_cnt,
-                                 d_tlist + ((q - 2) & 1) * (1 + MAX_BATCH), q - 2 >= r0 ? d_done + (q - 2) : nullptr,
-                                 d->d_stale + (size_t)(q & 1) * MAX_BATCH * KSTALE, d->d_stale_cnt + (q & 1) * MAX_BATCH,
-                                 d_ready + q, d_err, (int64_t)0, 1);
-            continue;
-          }
-          // two eval streams: batch q's eval waits only for batch q-3, k_patch brings in batch q-2's changed nodes
-          const bool patch = two_es && d->eval_patch && q - 2 >= r0;
-          // with k_patch, batch q's eval waits for batch q-1's select to start (it followed k_patch(q-1), which
-          // waited for done[q-3]): the select's workgroups are resident before this eval's grid takes the CUs
-          const bool after_sel = two_es && d->eval_patch;
-          const int32_t* ew = after_sel ? (q - 1 >= r0 ? d_sstart + (q - 1) : d_rres + r0)
-                                        : (q - 2 >= r0 ? d_done + (q - 2) : nullptr);
-          // (every workgroup of batch q-1's select counts itself in sstart[q-1])
-          const int32_t want = after_sel && q - 1 >= r0 ? batches[q - 1].pods * std::max(1, select_parts(N, batches[q - 1].pods)) : 1;
-          rc = eval_select(q, true, es, ew, d_ready + q, alt, patch ? d_done + (q - 2) : nullptr,
-                           d_tlist + ((q - 2) & 1) * (1 + MAX_BATCH), after_sel ? d_sstart + q : nullptr, want);
-          if (rc) return rc;
-          if (!published)
-            hipLaunchKernelGGL(k_handoff, dim3(1), dim3(64), d->excl_lds, es, d_ready + q, (int32_t)batches[q].pods, nullptr,
-                               d_err, nullptr, 1);
-          continue;
-        }
-        rc = eval_select(q, true, d->estream);
-        if (rc) return rc;
-        hipLaunchKernelGGL((ns == NS_SCORES ? (ext ? k_fixup<true, NS_SCORES> : k_fixup<false, NS_SCORES>)
-                            : ns ? (ext ? k_fixup<true, NS_SETS> : k_fixup<false, NS_SETS>) : (ext ? k_fixup<true> : k_fixup<false>)),
-                           dim3((unsigned)batches[q].pods), dim3(FIX_BLOCK), 0, d->estream, d->soa, d->d_pods,
-                           d_bases + q, k, d->d_stale + (size_t)(q & 1) * MAX_BATCH * KSTALE,
-                           d->d_stale_cnt + (q & 1) * MAX_BATCH, d->d_trows, d->d_tcnt, d->d_cand, d->d_cand_cnt,
-                           d_done, first ? -1 : q - 1, d_ready + q, d_err, d_fst + 2 * q);
-      }
-      HIP_OK(hipEventRecord(d->ev_res[(e - 1) % R], d->stream));
-      HIP_OK(hipEventRecord(d->ev_sel[(e - 1) % R], d->estream));
-      if (two_es) HIP_OK(hipEventRecord(d->ev_sel2, d->estream2));
-      n_pipelined += e - r0;
-      b = e;
-      if (b < n_batches && run_end[b] == 0) {  // a serial batch next: the run's eval streams drain first
-        HIP_OK(hipStreamWaitEvent(d->stream, d->ev_sel[(e - 1) % R], 0));
-        if (two_es) HIP_OK(hipStreamWaitEvent(d->stream, d->ev_sel2, 0));
-      }
-      continue;
-    }
-    // serial batch: eval, select and Reserve in order on one stream (no cross-stream hand-off)
-    const int bp = batches[b].pods;
-    const bool ds = batches[b].ds, cpu = batches[b].cpu;
-    const int32_t* bbase = d_bases + b;
-    const bool fused_b = fused && b == n_batches - 1;
-    if (fused_b) {  // the fused matched pod: the speculation check, then its rows (gated) before its eval
-      hipLaunchKernelGGL(k_rsv_check, dim3(1), dim3(256), 0, d->stream, d_chosen, bases[b], d->d_rsv,
-                         (int)ctx->rsv_pairs.size(), ctx->cfg.global_node_offset, d->d_rsv_gate);
-      rc = device_refresh_flush(ctx, d->d_rsv_gate);
-      if (rc) return rc;
-    }
-    if (pre_b != b) rc = eval_select(b, false, d->stream);
-    pre_b = -1;
-    if (rc) return rc;
-    if (fused_b) {
-      hipLaunchKernelGGL(k_rsv_gate_apply, dim3(1), dim3(64), 0, d->stream, d->d_rsv_gate, d->d_cand_cnt);
-      HIP_OK(copy_async(d->h_rsv_out.data() + 4, d->d_rsv_gate, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
-    }
-    if (bp == 1) {  // one pod: the single-node Reserve (cpuset accumulator when it binds)
-      int elo = 0, ehi = 0;  // nodes whose affinities this batch's eval stored in d_aff (binding batches)
-      if (cpu && numa) {
-        ehi = N;
-        if (sharded && !d->loopback) shard_range(N, d->rank, d->world, &elo, &ehi);
-      }
-      hipLaunchKernelGGL((ds ? (numa ? k_cpuset_reserve<true, true> : k_cpuset_reserve<true, false>)
-                             : (numa ? k_cpuset_reserve<false, true> : k_cpuset_reserve<false, false>)),
-                         dim3(1), dim3(64), 0, d->stream, d->soa,
-                         d->d_pods, bbase, k, d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score,
-                         ctx->cfg.global_node_offset, d_st, d_pst, b, d->d_devalloc,
-                         numa ? d->d_numaalloc : nullptr, d->d_cpusets,
-                         d->d_aff, elo, ehi);
-    } else {
-      auto resolve = quota ? (ds ? (numa ? k_resolve<true, true, true> : k_resolve<true, false, true>)
-                                 : (numa ? k_resolve<false, true, true> : k_resolve<false, false, true>))
-                           : (ds ? (numa ? k_resolve<true, true, false> : k_resolve<true, false, false>)
-                                 : (numa ? k_resolve<false, true, false>
-                                         : ns == NS_SCORES ? k_resolve<false, false, false, NS_SCORES>
-                                         : ns ? k_resolve<false, false, false, NS_SETS> : k_resolve<false, false, false>));
-      hipLaunchKernelGGL(resolve, dim3(1), dim3(numa ? res_threads<true>() : res_threads<false>()), 0, d->stream, d->soa, d->d_pods, bbase, bp, k,
-                         d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score, ctx->cfg.global_node_offset,
-                         d_st, d_pst, b, d->d_devalloc, d->d_numaalloc, d->d_chg, N,
-                         (int)run_sorted(b, b + 1));
-      if (batches[b].cut) {  // a DeviceShare batch may stop early: re-run its remaining pods as batch b
-        if (!d->h_cut.resize(1)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the cut word");
-        HIP_OK(copy_async(d->h_cut.data(), d->d_dsmax + DSB_CUT, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
-        // the next serial batch's eval + select go in behind the read-back, so the device keeps working while the
-        // host waits for the cut (without one they stand; with one the re-run batch overwrites what they wrote)
-        if (b + 1 < n_batches && run_end[b + 1] == 0 && !(fused && b + 1 == n_batches - 1)) {
-          const bool keep = rerun;
-          rerun = false;
-          rc = eval_select(b + 1, false, d->stream);
-          rerun = keep;
-          if (rc) return rc;
-          pre_b = b + 1;
-        }
-        HIP_OK(hipStreamSynchronize(d->stream));
-        const int32_t cut = d->h_cut[0];
-        if (cut >= 0) {
-          pre_b = -1;
-          if (cut <= bases[b] || cut >= bases[b] + bp) return fail(KE_ERR_DEVICE, "DeviceShare batch cut out of range");
-          batches[b].pods = bases[b] + bp - cut;
-          bases[b] = cut;
-          HIP_OK(copy_async(d_bases + b, &bases[b], sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
-          ctx->last_ds_cuts++;
-          rerun = true;
-          continue;
-        }
-      }
-      rerun = false;
-    }
-    if (b + 1 < n_batches && run_end[b + 1] > 0)  // the next run's eval stream waits for this Reserve
-      HIP_OK(hipEventRecord(d->ev_res[b % R], d->stream));
-    b++;
-  }
-  HIP_OK(hipGetLastError());
-  ctx->last_enqueue_ms = ctx->host_ms[4] = ms_since(host_t0);
-  tp = clk::now();
-  const auto t_fl = clk::now();
-  flush_mirror_async(*ctx);  // the earlier calls' deferred host mirror, on a host thread while the device works
-  const double flush_ms = ms_since(t_fl);
-  HIP_OK(hipEventRecord(e1, d->stream));
-  HIP_OK(hipEventRecord(d->ev_rend, d->stream));  // the read-back on the staging stream after the Reserve chain
-  HIP_OK(hipStreamWaitEvent(cs, d->ev_rend, 0));
-  // The call's outputs go to one page-locked staging area (async copies, no host wait) and are copied out after
-  // the synchronisation; allocations none of the call's batches can make are not read back (zero).
-  bool any_ds = false;
-  for (const Batch& bt : batches) any_ds = any_ds || bt.ds || bt.hint;
-  const bool vf_out = d->soa.vfo != nullptr;
-  const size_t np = (size_t)n_pods, nb = (size_t)n_batches;
-  // h_out: the read-back block from its first wanted part (the scores lead it, so a call without them starts at
-  // the placements), then the context's error word and what only some calls have
-  const size_t blk0 = want_score ? ol.score : ol.chosen;
-  size_t off = (ol.end - blk0 + 15) & ~(size_t)15;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = (off + bytes + 15) & ~(size_t)15;
-    return o;
-  };
-  const size_t o_chosen = ol.chosen - blk0, o_score = ol.score - blk0, o_err = ol.err - blk0, o_fst = ol.fst - blk0,
-               o_st = ol.st - blk0, o_pst = ol.pst - blk0, o_est = ol.est - blk0, o_kerr = take(4),
-               o_dev = take(any_ds ? 8 * np : 0), o_cs = take(any_cpu ? 32 * np : 0),
-               o_vf = take(vf_out ? 2 * DS_MINORS * np : 0), o_numa = take(numa ? 8 * 16 * np : 0),
-               o_dcnt = take(numa ? 4 * nb : 0);
-  if (!d->h_out.resize(off)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the readback staging buffer");
-  uint8_t* const h = d->h_out.data();
-  auto d2h = [&](size_t o, const void* src, size_t bytes) -> int {
-    if (bytes) HIP_OK(copy_async(h + o, src, bytes, hipMemcpyDeviceToHost, cs));
-    return KE_OK;
-  };
-  if ((rc = d2h(0, d->d_out + blk0, ol.end - blk0)) || (rc = d2h(o_kerr, d->soa.kerr, 4))) return rc;
-  if (any_ds && (rc = d2h(o_dev, d->d_devalloc, 8 * np))) return rc;
-  if (any_cpu && (rc = d2h(o_cs, d->d_cpusets, 32 * np))) return rc;
-  if (vf_out && (rc = d2h(o_vf, d->d_vfo, 2 * DS_MINORS * np))) return rc;
-  if (numa && (rc = d2h(o_numa, d->d_numaalloc, 8 * 16 * np))) return rc;
-  if (numa && (rc = d2h(o_dcnt, d->d_defer_cnt, 4 * nb))) return rc;
-  const int64_t cb_copies = n_copies, cb_fills = n_fills;
-  const bool behind = ctx->call_behind;  // (ke_schedule_submit: enqueued behind a call in flight)
-  // the call's end on every stream: its completion waits for these events, not for the streams (a submission
-  // behind it may already be queued on them)
-  HIP_OK(hipEventRecord(done_ev[0], cs));
-  HIP_OK(hipEventRecord(done_ev[1], d->estream));
-  if (d->estream2) HIP_OK(hipEventRecord(done_ev[2], d->estream2));
-  double enq_ms[5];
-  for (int i = 0; i < 5; i++) enq_ms[i] = ctx->host_ms[i];
-  const auto entry = ctx->call_entry;
-  *fin = [=, batches = std::move(batches), bases = std::move(bases), run_end = std::move(run_end),
-          ev = std::move(ev)](int32_t* chosen, int32_t* score) mutable -> int {
+  std::vector<int32_t> bases;
+  std::vector<int> run_end;
+  HostOutLayout ho;
+  const uint8_t* h;
+  int32_t n_pods;
+  const ke_pod* pods;
+  bool want_score, numa, quota, any_ds, any_cpu, vf_out;
+  hipEvent_t e0, e1, done_ev[3];  // the span on the Reserve stream; the call's end on each stream
+  std::vector<hipEvent_t> ev;     // the samples (PE per sampled batch)
+  double enq_ms[5], flush_ms;
+  clk::time_point entry;
+  bool behind;  // (ke_schedule_submit: enqueued behind a call in flight)
+  int64_t copies, fills;
+  int n_pipelined;
+};
+
+static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
+  Context* const ctx = c.ctx;
+  DeviceState* const d = ctx->dev;
   HIP_OK(hipSetDevice(d->device));
   auto tp = clk::now();
-  for (int i = 0; i < 5; i++) ctx->host_ms[i] = enq_ms[i];
-  ctx->host_ms[7] = flush_ms;  // (ke_schedule adds its own part of the mirror)
-  std::vector<uint64_t> st(nb + 1), pst(PST * nb), est(nb), fst(2 * nb);
-  std::vector<uint32_t> dcnt(numa ? nb : 0);
-  int32_t herr = 0, kerr = 0;
+  for (int i = 0; i < 5; i++) ctx->host_ms[i] = c.enq_ms[i];
+  ctx->host_ms[7] = c.flush_ms;  // (ke_schedule adds its own part of the mirror)
   // while the device runs: the host copies of the segment's pods for the deferred mirror (flush_mirror;
   // ke_schedule records which of them were placed)
   ctx->pending_base = (int64_t)ctx->pending_pods.size();
-  ctx->pending_pods.insert(ctx->pending_pods.end(), pods, pods + n_pods);
-  HIP_OK(hipEventSynchronize(done_ev[0]));
-  HIP_OK(hipEventSynchronize(done_ev[1]));
-  if (d->estream2) HIP_OK(hipEventSynchronize(done_ev[2]));
+  ctx->pending_pods.insert(ctx->pending_pods.end(), c.pods, c.pods + c.n_pods);
+  // the call's end on every stream: events, not the streams (a submission behind it may already be queued on them)
+  HIP_OK(hipEventSynchronize(c.done_ev[0]));
+  HIP_OK(hipEventSynchronize(c.done_ev[1]));
+  if (d->estream2) HIP_OK(hipEventSynchronize(c.done_ev[2]));
   const auto t_sync = clk::now();
-  std::memcpy(chosen, h + o_chosen, (size_t)out_bytes);
-  if (score && want_score) std::memcpy(score, h + o_score, (size_t)out_bytes);
-  if (any_ds) {
-    ctx->last_dev_alloc.resize(np);
-    std::memcpy(ctx->last_dev_alloc.data(), h + o_dev, 8 * np);
-  } else {
-    ctx->last_dev_alloc.clear();  // (readers take absent entries as zero)
-  }
-  if (any_cpu) {
-    ctx->last_cpusets.resize(4 * np);
-    std::memcpy(ctx->last_cpusets.data(), h + o_cs, 32 * np);
-  } else {
-    ctx->last_cpusets.clear();
-  }
-  ctx->last_vf.clear();
-  if (vf_out) {
-    ctx->last_vf.resize(2 * DS_MINORS * np);
-    std::memcpy(ctx->last_vf.data(), h + o_vf, 2 * DS_MINORS * np);
-  }
-  ctx->last_numa_alloc.clear();
-  if (numa) {
-    ctx->last_numa_alloc.resize(16 * np);
-    std::memcpy(ctx->last_numa_alloc.data(), h + o_numa, 8 * 16 * np);
-    std::memcpy(dcnt.data(), h + o_dcnt, 4 * nb);
-  }
-  std::memcpy(&herr, h + o_err, 4);
-  std::memcpy(&kerr, h + o_kerr, 4);
+  const HostOutLayout& ho = c.ho;
+  const uint8_t* const h = c.h;
+  const size_t np = (size_t)c.n_pods, nb = c.batches.size();
+  std::memcpy(chosen, h + ho.chosen, 4 * np);
+  if (score && c.want_score) std::memcpy(score, h + ho.score, 4 * np);
+  // allocations none of the call's batches can make were not read back (readers take absent entries as zero)
+  ctx->last_dev_alloc.assign(reinterpret_cast<const uint64_t*>(h + ho.dev),
+                             reinterpret_cast<const uint64_t*>(h + ho.dev) + (c.any_ds ? np : 0));
+  ctx->last_cpusets.assign(reinterpret_cast<const uint64_t*>(h + ho.cs),
+                           reinterpret_cast<const uint64_t*>(h + ho.cs) + (c.any_cpu ? 4 * np : 0));
+  ctx->last_vf.assign(reinterpret_cast<const int8_t*>(h + ho.vf),
+                      reinterpret_cast<const int8_t*>(h + ho.vf) + (c.vf_out ? 2 * DS_MINORS * np : 0));
+  ctx->last_numa_alloc.assign(reinterpret_cast<const int64_t*>(h + ho.numa),
+                              reinterpret_cast<const int64_t*>(h + ho.numa) + (c.numa ? 16 * np : 0));
+  int32_t herr = 0, kerr = 0;
+  std::memcpy(&herr, h + ho.err, 4);
+  std::memcpy(&kerr, h + ho.kerr, 4);
   const uint64_t prev_end = ctx->prev_end_tick;  // (a failed call leaves none behind)
   ctx->prev_end_tick = 0;
-  std::memcpy(fst.data(), h + o_fst, 16 * nb);
-  std::memcpy(st.data(), h + o_st, 8 * (nb + 1));
-  std::memcpy(pst.data(), h + o_pst, 8 * PST * nb);
-  std::memcpy(est.data(), h + o_est, 8 * nb);
   ctx->host_ms[5] = ms_since(tp);
   tp = clk::now();
   if (herr) {
@@ -8899,143 +8249,696 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
                                                       : "internal: a hinted pod reached a kernel without the hint path");
   }
   float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-  ctx->last_total_ms = ms;
-  ctx->last_pipelined = n_pipelined;
-  // s_memrealtime ticks -> ms, calibrated against the event-timed span of the whole queue
-  const double span = (double)(st[n_batches] - st[0]);
-  const double ms_per_tick = span > 0 ? ms / span : 1e-5;
-  // ke_debug_call_boundary: the device time between the previous call's last batch end and this call's first
-  // Reserve prologue (a call enqueued behind one in flight; the completions run in submission order)
-  ctx->call_boundary[0] = 0;  // (no batch's eval is enqueued ahead of the previous call's end)
-  ctx->call_boundary[1] = cb_copies;
-  ctx->call_boundary[2] = cb_fills;
-  ctx->call_boundary[3] = behind && prev_end && pst[0] > prev_end ? (int64_t)((double)(pst[0] - prev_end) * ms_per_tick * 1e6) : 0;
-  ctx->prev_end_tick = st[n_batches];
-  // a batch's device service time: from its eval start to the end of its Reserve
-  ctx->last_batch_ms.resize(n_batches);
-  for (int b = 0; b < n_batches; b++) {
-    const uint64_t t0 = std::max(std::min(est[b], st[b + 1]), st[0]);
-    ctx->last_batch_ms[b] = (double)(st[b + 1] - t0) * ms_per_tick;
-  }
-  // a pod's latency: from the ke_schedule call's entry (its dequeue) to its batch's Reserve end,
-  // the device stamps placed on the host clock by aligning the last one with the return of the final
-  // synchronisation (later than the true end: an upper bound)
-  {
-    const double sync_ms = std::chrono::duration<double, std::milli>(t_sync - entry).count();
-    ctx->last_pod_lat.resize((size_t)n_pods);
-    for (int b = 0, p0 = 0; b < n_batches; b++) {  // (a DeviceShare batch cut and re-run covers its first part too)
-      const double lat = sync_ms - (double)(st[n_batches] - st[b + 1]) * ms_per_tick;
-      const int p1 = bases[b] + batches[b].pods;
-      for (int p = p0; p < p1; p++) ctx->last_pod_lat[(size_t)p] = lat;
-      p0 = p1;
-    }
-  }
-  double pro = 0, loop = 0;  // resolve kernel: prologue (candidate/row staging) vs sequential replay
-  // phases: prologue, then the speculative replay's first round (P, R + S, V), its later rounds, and the
-  // write-back (the one-wave replay of other batches counts entirely as write-back)
-  double ph[6] = {0, 0, 0, 0, 0, 0};
-  for (int b = 0; b < n_batches; b++) {
-    const uint64_t* p = &pst[PST * (size_t)b];
-    pro += (double)(p[4] - p[0]) * ms_per_tick;
-    loop += (double)(st[b + 1] - p[4]) * ms_per_tick;
-    const bool spec = p[1] > p[4];
-    ph[0] += (double)(p[4] - p[0]);
-    ph[1] += spec ? (double)(p[1] - p[4]) : 0.0;
-    ph[2] += spec ? (double)(p[2] - p[1]) : 0.0;
-    ph[3] += spec ? (double)(p[3] - p[2]) : 0.0;
-    ph[4] += spec ? (double)(p[5] - p[3]) : 0.0;
-    ph[5] += (double)(st[b + 1] - (spec ? p[5] : p[4]));
-  }
-  ctx->kstat_resolve_prologue_ms = pro / n_batches;
-  ctx->kstat_resolve_loop_ms = loop / n_batches;
-  for (int i = 0; i < 6; i++) ctx->kstat_resolve_phase_ms[i] = ph[i] * ms_per_tick / n_batches;
-  std::vector<char> in_run((size_t)n_batches, 0);  // a pipelined batch after the first of its run
-  for (int b = 0; b < n_batches; b++)
-    if (run_end[b] > 0)
-      for (int q = b + 1; q < run_end[b]; q++) in_run[(size_t)q] = 1;
-  std::vector<char> in_run_t(in_run);  // ... with T maxima the helpers may deliver
-  if (quota || d->pipe_fixup || d->t_helpers == 0) std::fill(in_run_t.begin(), in_run_t.end(), 0);
-  {  // the speculative replay's first round in detail: T set-up, the prediction loop, wave 1's T
-     // rows (concurrent with the loop), wave 0's R
-    double sub[4] = {0, 0, 0, 0};
-    int ns = 0, nt = 0, hits = 0;
-    for (int b = 0; b < n_batches; b++) {
-      const uint64_t* p = &pst[PST * (size_t)b];
-      if (!(p[1] > p[4])) continue;
-      ns++;
-      sub[0] += (double)(p[8] - p[4]);
-      sub[1] += (double)(p[9] > p[8] ? p[9] - p[8] : 0);
-      sub[2] += (double)(p[10] > p[8] ? p[10] - p[8] : 0);
-      sub[3] += (double)(p[11] > p[1] ? p[11] - p[1] : 0);
-      if (in_run_t[(size_t)b]) nt++, hits += p[12] == 1;
-    }
-    for (int i = 0; i < 4; i++) ctx->kstat_resolve_sub_ms[i] = ns ? sub[i] * ms_per_tick / ns : 0;
-    ctx->kstat_resolve_sub_ms[4] = nt ? (double)hits / nt : 0;
-    // the progressive S of wave 1 (batches with helper T maxima): its polls, record loads + Reserves, rows, and
-    // its end after the T set-up
-    double wv[4] = {0, 0, 0, 0};
-    int nw = 0;
-    for (int b = 0; b < n_batches; b++) {
-      const uint64_t* p = &pst[PST * (size_t)b];
-      if (!(p[1] > p[4]) || !in_run_t[(size_t)b] || p[15] <= p[8]) continue;
-      nw++;
-      wv[0] += (double)p[13];
-      wv[1] += (double)(p[14] & 0xffffffffu);
-      wv[2] += (double)(p[14] >> 32);
-      wv[3] += (double)(p[15] - p[8]);
-    }
-    for (int i = 0; i < 4; i++) ctx->kstat_resolve_wave1_ms[i] = nw ? wv[i] * ms_per_tick / nw : 0;
-  }
-  ctx->kstat_numa_deferred = 0;
-  for (uint32_t c : dcnt) ctx->kstat_numa_deferred += c;
-  // per-batch Reserve time from the in-kernel stamps (start of the batch's prologue -> end of its
-  // replay); hand-off = end of batch b-1's replay -> start of batch b (run batches after the first);
-  // fixup = k_fixup's workgroup 0 from its wait to its publish
-  double res_sum = 0, ho_sum = 0, fx_sum = 0;
-  int ho_n = 0, fx_n = 0;
-  for (int b = 0; b < n_batches; b++) {
-    res_sum += (double)(st[b + 1] - pst[PST * (size_t)b]) * ms_per_tick;
-    if (fst[2 * b + 1] > fst[2 * b]) {
-      fx_sum += (double)(fst[2 * b + 1] - fst[2 * b]) * ms_per_tick;
-      fx_n++;
-    }
-    if (in_run[(size_t)b] && pst[PST * (size_t)b] > st[b]) {
-      ho_sum += (double)(pst[PST * (size_t)b] - st[b]) * ms_per_tick;
-      ho_n++;
-    }
-  }
-  ctx->kstat_resolve_ms = n_batches ? res_sum / n_batches : 0;
-  double rows_fetched = 0, rows_changed = 0;
-  double spec_rounds = 0;
-  for (int b = 0; b < n_batches; b++) {
-    rows_fetched += (double)(pst[PST * (size_t)b + 6] & 0xFFFFFFFFull);
-    spec_rounds += (double)(pst[PST * (size_t)b + 6] >> 32);
-    rows_changed += (double)pst[PST * (size_t)b + 7];
-  }
-  ctx->kstat_spec_failed = n_batches ? spec_rounds / n_batches : 0;
-  ctx->kstat_rows_fetched = n_batches ? rows_fetched / n_batches : 0;
-  ctx->kstat_rows_changed = n_batches ? rows_changed / n_batches : 0;
-  ctx->kstat_fixup_ms = fx_n ? fx_sum / fx_n : 0;
-  ctx->kstat_handoff_ms = ho_n ? ho_sum / ho_n : 0;
-  ctx->kstat_samples = 0;
-  ctx->kstat_eval_ms = ctx->kstat_select_ms = 0;
-  for (size_t s = 0; s + PE - 1 < ev.size(); s += PE) {
+  HIP_OK(hipEventElapsedTime(&ms, c.e0, c.e1));
+  std::vector<float> samples;  // (eval, select) per sampled batch
+  for (size_t s = 0; s + PE - 1 < c.ev.size(); s += PE) {
     float a = 0, b = 0;
-    HIP_OK(hipEventElapsedTime(&a, ev[s], ev[s + 1]));
-    HIP_OK(hipEventElapsedTime(&b, ev[s + 3], ev[s + 2]));
-    ctx->kstat_eval_ms += a;
-    ctx->kstat_select_ms += b;
-    ctx->kstat_samples++;
+    HIP_OK(hipEventElapsedTime(&a, c.ev[s], c.ev[s + 1]));
+    HIP_OK(hipEventElapsedTime(&b, c.ev[s + 3], c.ev[s + 2]));
+    samples.push_back(a);
+    samples.push_back(b);
   }
-  if (ctx->kstat_samples) {
-    ctx->kstat_eval_ms /= ctx->kstat_samples;
-    ctx->kstat_select_ms /= ctx->kstat_samples;
-  }
+  StatsIn in{};
+  in.batches = &c.batches, in.bases = &c.bases, in.run_end = &c.run_end;
+  in.n_pods = c.n_pods, in.n_pipelined = c.n_pipelined;
+  in.st = reinterpret_cast<const uint64_t*>(h + ho.st), in.pst = reinterpret_cast<const uint64_t*>(h + ho.pst);
+  in.est = reinterpret_cast<const uint64_t*>(h + ho.est), in.fst = reinterpret_cast<const uint64_t*>(h + ho.fst);
+  in.dcnt = reinterpret_cast<const uint32_t*>(h + ho.dcnt), in.n_dcnt = c.numa ? nb : 0;
+  in.span_ms = ms;
+  in.sync_ms = std::chrono::duration<double, std::milli>(t_sync - c.entry).count();
+  in.prev_end = prev_end, in.behind = c.behind, in.copies = c.copies, in.fills = c.fills;
+  in.t_maxima = !(c.quota || d->pipe_fixup || d->t_helpers == 0);
+  in.samples = samples.data(), in.n_samples = (int)(samples.size() / 2);
+  call_stats(*ctx, in);
   ctx->host_ms[6] = ms_since(tp);
   return KE_OK;
+}
+
+// eval_select's arguments: batch b's eval + candidate lists on stream `es`, in the mode of its SelectPlan
+struct EvalSelect {
+  int b;
+  hipStream_t es;
+  bool alt = false;  // the second eval stream: its own score matrix, part lists and part counters
+  // (pipelined) the eval first waits for *dwait to reach dwant -- in k_eval_plain itself, else a k_handoff ahead of it
+  const int32_t* dwait = nullptr;
+  int32_t dwant = 1;
+  // the select publishes the lists to the running Reserve kernel itself (*rpub) when it can -- split or
+  // one-workgroup select, unsharded: ScheduleCall::published tells
+  int32_t* rpub = nullptr;
+  // k_patch ahead of the select: the nodes of T list ptl (batch b-2 changed them), once *pwait says it is done
+  const int32_t* pwait = nullptr;
+  const int32_t* ptl = nullptr;
+  int32_t* sstart = nullptr;  // every workgroup of the select counts itself here
+};
+
+// The enqueue of one call: what its steps share.  The steps run in the order of device_schedule_enqueue.
+struct ScheduleCall {
+  static constexpr int R = DeviceState::EV_RING;
+  Context* const ctx;
+  DeviceState* const d;
+  CallBufs& c;
+  const int32_t n_pods;
+  const ke_pod* const pods;
+  const bool want_score;
+  const int N;
+  const bool fused;    // the last pod: a matched pod behind plain ones (its rows' scatters deferred)
+  const bool numa;
+  const bool quota;    // ElasticQuota admission + Reserve in the Reserve kernels
+  const bool sharded;
+  const bool matched;  // one matched pod (ke_schedule's segment of its own, or the fused one): the Reservation plugin
+  // a call with node set ids (a plain queue, ke_capi.cpp take_node_sets): the NS instantiations of every kernel that
+  // turns a (pod, node) pair into a score or key (NS_SETS), or with score table ids (NS_SCORES: these read the set
+  // table too, id 0 = its all-ones row 0)
+  const int ns;
+  // the plan
+  bool fixup = false, two_es = false, ahead = false;  // the schedule of the call's pipelined runs (plan())
+  std::vector<Batch> batches;
+  std::vector<int32_t> bases;
+  std::vector<int> run_end;
+  std::vector<SelectPlan> sel;
+  SelectKnob knob;
+  int n_batches = 0;
+  bool any_cpu = false;
+  OutLayout ol{0, 0};
+  SchedLayout sl{0};
+  KArgs k{};
+  bool ext = false;
+  // the upload block's tail (the batch bases) and the device pointers into the call's blocks
+  int32_t* h_bases = nullptr;
+  int64_t upload_bytes = 0;
+  int32_t *d_bases = nullptr, *d_ready = nullptr, *d_done = nullptr, *d_tready = nullptr, *d_sstart = nullptr,
+          *d_rres = nullptr, *d_tlist = nullptr, *d_chosen = nullptr, *d_chosen_score = nullptr, *d_err = nullptr;
+  uint32_t* d_tmx = nullptr;
+  uint64_t *d_fst = nullptr, *d_st = nullptr, *d_pst = nullptr, *estamps = nullptr;  // (estamps: eval start of each batch)
+  // progress
+  bool rerun = false;      // the current serial batch is the remainder of a DeviceShare batch that stopped early
+  int pre_b = -1;          // a serial batch whose eval + select is already enqueued (behind a DeviceShare cut check)
+  bool published = false;  // the last eval_select's select published its lists itself
+  int n_copies = 0, n_fills = 0;  // host-counted copies / fills of the call (ke_debug_call_boundary)
+  int n_pipelined = 0;
+  // the call's timing events, from the buffer set's pool (creating them per call cost the host ~3 us an event)
+  int every = 0;
+  hipEvent_t e0 = nullptr, e1 = nullptr, done_ev[3] = {};
+  std::vector<hipEvent_t> ev;
+
+  ScheduleCall(Context* ctx_, int32_t n, const ke_pod* p, bool ws)
+      : ctx(ctx_), d(ctx_->dev), c(d->call), n_pods(n), pods(p), want_score(ws), N(ctx_->n_nodes), fused(ctx_->rsv_fused),
+        numa(d->numa_alloc), quota(!ctx_->quotas.empty()), sharded(d->world > 1 || d->comm || d->host_fn),
+        matched(!ctx_->rsv_pairs.empty() || ctx_->rsv_affinity),
+        ns(ctx_->nsc_call ? NS_SCORES : ctx_->ns_call ? NS_SETS : 0) {}
+
+  hipError_t copy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    n_copies++;
+    return hipMemcpyAsync(dst, src, bytes, kind, s);
+  }
+  hipError_t fill_async(void* dst, int v, size_t bytes, hipStream_t s) {
+    n_fills++;
+    return hipMemsetAsync(dst, v, bytes, s);
+  }
+
+  // the set / score tables brought up to date, and the upload block staged: records, node set ids, then the batch
+  // bases (at most one batch per pod, and the end) -- copied once the bases are known (begin())
+  int stage() {
+    int rc;
+    if (ns) {
+      if ((ctx->ns_call && (int64_t)ctx->ns_call_ids.size() != n_pods) ||
+          (ctx->nsc_call && (int64_t)ctx->nsc_call_ids.size() != n_pods))
+        return fail(KE_ERR_DEVICE, "internal: node set / score table ids of another call");
+      if ((rc = node_sets_sync(ctx))) return rc;
+    }
+    if (ns == NS_SCORES && (rc = node_scores_sync(ctx))) return rc;
+    return upload_pods(ctx, n_pods, pods, (int64_t)n_pods + 1, &h_bases, &upload_bytes, &n_copies);
+  }
+
+  // host only: batches, runs, each batch's select and the layouts
+  int plan() {
+    // the knob is read per call: tests set it between contexts of one process
+    knob = select_knob(std::getenv("KOORDEVAL_SELECT_PARTS"));
+    ctx->last_ds_cuts = 0;
+    batches = plan_batches(c.host_pods.data(), n_pods, ctx->cfg.pod_batch, !sharded && !numa && N > 0, fused);
+    for (const Batch& b : batches) any_cpu = any_cpu || b.cpu;
+    if (any_cpu && !d->cpu_alloc) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
+    n_batches = (int)batches.size();
+    bases = plan_bases(batches);
+    run_end = plan_runs(batches, d->pipeline, N, numa, fused);
+    // Two streams (pipelining).  A run of plain batches: one persistent k_resolve_run on `stream`
+    // resolves them all while the eval streams prepare the lists of the batches ahead.  `fixup` (the replay_batch
+    // path of quota needs exact lists; ke_set_pipeline(2)): batch b's stale eval + select run while batch b-1 is
+    // being resolved, and k_fixup waits for b-1's done flag, re-evaluates the nodes it chose and publishes the exact
+    // lists.  Else the stale lists go to the replay as they are, and batches alternate between two eval streams --
+    // unsharded only: a node-sharded batch's all-gather must run in the same order on every rank's communicator,
+    // which two streams of one rank would not guarantee -- with the k_patch schedule or, `ahead`, select-ahead.
+    // Any other batch (DeviceShare / cpuset singletons, NUMA-policy contexts, pipeline off) is serial: its eval
+    // waits for the previous batch's Reserve, its lists are exact, its Reserve kernel waits for its lists.
+    fixup = quota || d->pipe_fixup;
+    two_es = !fixup && d->estream2 != nullptr && !sharded;
+    ahead = two_es && d->eval_patch && d->select_ahead;
+    std::vector<SelMode> mode((size_t)n_batches, SEL_EXACT);
+    for (int b = 0; b < n_batches; b++)
+      for (int q = b; q < run_end[b]; q++) mode[(size_t)q] = ahead ? SEL_AHEAD : SEL_STALE;
+    sel.resize((size_t)n_batches);
+    for (int b = 0; b < n_batches; b++) sel[(size_t)b] = plan_select(N, batches[b], mode[(size_t)b], sharded, knob);
+    ol = OutLayout((size_t)n_pods, (size_t)n_batches);
+    sl = SchedLayout(n_batches);
+    return KE_OK;
+  }
+
+  // the call's output buffers, grown when needed, and what only some calls have (VF ranks, NUMA allocations)
+  int buffers() {
+    int rc;
+    if (c.out_cap < n_pods) {
+      if (c.d_out) HIP_OK(hipFree(c.d_out));
+      if (c.d_devalloc) HIP_OK(hipFree(c.d_devalloc));
+      if (c.d_numaalloc) HIP_OK(hipFree(c.d_numaalloc));
+      c.d_out = nullptr;
+      c.d_devalloc = nullptr;
+      c.d_numaalloc = nullptr;
+      c.out_cap = 0;
+      HIP_OK(hipMalloc(&c.d_out, OutLayout((size_t)n_pods, (size_t)n_pods).total));  // (n_batches <= n_pods)
+      HIP_OK(hipMalloc(&c.d_devalloc, sizeof(uint64_t) * n_pods));
+      c.out_cap = n_pods;
+    }
+    d_chosen = reinterpret_cast<int32_t*>(c.d_out + ol.chosen);
+    d_chosen_score = reinterpret_cast<int32_t*>(c.d_out + ol.score);
+    d_err = reinterpret_cast<int32_t*>(c.d_out + ol.err);
+    d_fst = reinterpret_cast<uint64_t*>(c.d_out + ol.fst);
+    d_st = reinterpret_cast<uint64_t*>(c.d_out + ol.st);
+    d_pst = reinterpret_cast<uint64_t*>(c.d_out + ol.pst);
+    estamps = reinterpret_cast<uint64_t*>(c.d_out + ol.est);
+    // (every singleton batch's k_cpuset_reserve writes its pod's entry; the table is read back, and so zeroed by
+    // k_call_begin, only in a call with a cpuset pod)
+    if ((rc = ensure((void**)&c.d_cpusets, &c.cpusets_cap, sizeof(uint64_t) * 4 * (int64_t)n_pods))) return rc;
+    bool any_hint = false;
+    for (const DevPod& q : c.host_pods) any_hint = any_hint || (q.flags & PF_DS_HINT);
+    d->soa.vfo = nullptr;
+    if (any_hint) {  // the VF ranks the hinted pods' Reserves take
+      if ((rc = ensure((void**)&d->d_vfo, &d->vfo_cap, 2 * DS_MINORS * (int64_t)n_pods))) return rc;
+      HIP_OK(fill_async(d->d_vfo, 0xFF, 2 * DS_MINORS * (size_t)n_pods, d->stream));
+      d->soa.vfo = d->d_vfo;
+    }
+    if (numa && !c.d_numaalloc) HIP_OK(hipMalloc(&c.d_numaalloc, sizeof(int64_t) * 16 * c.out_cap));
+    if (numa) {  // deferred-pair list of one batch (reused) + a counter per batch
+      if ((rc = ensure((void**)&d->d_defer, &d->defer_cap, (sizeof(uint64_t) + sizeof(uint32_t)) * MAX_BATCH * d->capacity)))
+        return rc;
+      if ((rc = ensure((void**)&d->d_defer_cnt, &d->defer_cnt_cap, sizeof(uint32_t) * n_batches))) return rc;
+      HIP_OK(fill_async(d->d_defer_cnt, 0, sizeof(uint32_t) * n_batches, d->stream));
+    }
+    return KE_OK;
+  }
+
+  // the kernel arguments; a matched pod's pairs and allocate-from-reservation decisions, staged page-locked (the
+  // previous call's copies from this buffer completed with that call); the quota table
+  int reservations(int64_t now) {
+    int rc;
+    k = make_kargs(ctx, now);
+    if (ctx->rsv_affinity) k.flags |= AF_RSV_ONLY;  // the Reservation Filter: RsvOvr.rfilter of the pod's nodes
+    if (matched) {
+      if (n_pods != 1 && !fused) return fail(KE_ERR_UNSUPPORTED, "matched reservations need a singleton segment");
+      for (const RsvPair& q : ctx->rsv_pairs)
+        if (q.node < 0 || q.node >= N) return fail(KE_ERR_DEVICE, "reservation pair node out of range");
+      if ((rc = ensure((void**)&d->d_rsv, &d->rsv_cap, (int64_t)sizeof(RsvPair) * (int64_t)ctx->rsv_pairs.size()))) return rc;
+    }
+    if (fused || matched) {
+      if (!d->h_rsv_out.resize(5)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the reservation staging");
+      for (int i = 0; i < 4; i++) d->h_rsv_out[i] = -1;
+      d->h_rsv_out[4] = 0;  // the fused pod's gate (k_rsv_check)
+    }
+    if (fused && !d->d_rsv_gate) HIP_OK(hipMalloc(&d->d_rsv_gate, sizeof(int32_t)));
+    const size_t rsv_bytes = sizeof(RsvPair) * ctx->rsv_pairs.size(), ovr_bytes = sizeof(RsvOvr) * ctx->rsv_ovr.size();
+    if (rsv_bytes + ovr_bytes && !d->h_rsv.resize(rsv_bytes + ovr_bytes))
+      return fail(KE_ERR_DEVICE, "hipHostMalloc of the reservation staging");
+    if (matched) {
+      if (rsv_bytes) {
+        std::memcpy(d->h_rsv.data(), ctx->rsv_pairs.data(), rsv_bytes);
+        HIP_OK(copy_async(d->d_rsv, d->h_rsv.data(), rsv_bytes, hipMemcpyHostToDevice, d->stream));
+      }
+      HIP_OK(fill_async(d->d_rsv_out, 0xFF, sizeof(int32_t) * 4, d->stream));
+    }
+    d->soa.n_rovr = 0;  // a matched pod's allocate-from-reservation decisions (NF_RSV_CS rows read them)
+    if (!ctx->rsv_ovr.empty()) {
+      if ((rc = ensure((void**)&d->d_rovr, &d->rovr_cap, (int64_t)sizeof(RsvOvr) * (int64_t)ctx->rsv_ovr.size()))) return rc;
+      std::memcpy(d->h_rsv.data() + rsv_bytes, ctx->rsv_ovr.data(), ovr_bytes);
+      HIP_OK(copy_async(d->d_rovr, d->h_rsv.data() + rsv_bytes, ovr_bytes, hipMemcpyHostToDevice, d->stream));
+      d->soa.rovr = d->d_rovr;
+      d->soa.n_rovr = (int32_t)ctx->rsv_ovr.size();
+    }
+    if (quota) {
+      if (ctx->quota_dirty && (rc = device_quota_upload(ctx))) return rc;
+      k.flags |= AF_QUOTA | (ctx->qargs.enable_check_parent_quota ? AF_QUOTA_PARENT : 0u);
+    }
+    ext = (k.flags & AF_EXT) != 0;
+    return KE_OK;
+  }
+
+  // the bookkeeping words, the one copy of everything the call uploads, the call's events, and k_call_begin
+  int begin() {
+    int rc;
+    if ((rc = ensure((void**)&c.d_sched, &c.sched_cap, (int64_t)sizeof(int32_t) * sl.total))) return rc;
+    d_bases = reinterpret_cast<int32_t*>(c.d_pods + n_pods) + (ns ? n_pods : 0);
+    d_ready = c.d_sched + sl.ready, d_done = c.d_sched + sl.done, d_tready = c.d_sched + sl.tready;
+    d_sstart = c.d_sched + sl.sstart, d_rres = c.d_sched + sl.rres, d_tlist = c.d_sched + sl.tlist;
+    d_tmx = reinterpret_cast<uint32_t*>(c.d_sched + sl.tmx);
+    std::copy(bases.begin(), bases.end(), h_bases);
+    HIP_OK(copy_async(c.d_pods, c.host_pods.data(), (size_t)(upload_bytes - (int64_t)sizeof(int32_t) * (n_pods - n_batches)),
+                      hipMemcpyHostToDevice, d->stream));
+    every = d->profile_every;
+    const size_t n_tev = 5 + (every > 0 ? (size_t)((n_batches + every - 1) / every) * PE : 0);
+    while (c.tev.size() < n_tev) {
+      hipEvent_t e;
+      HIP_OK(hipEventCreate(&e));
+      c.tev.push_back(e);
+    }
+    e0 = c.tev[0], e1 = c.tev[1];
+    for (int i = 0; i < 3; i++) done_ev[i] = c.tev[2 + i];  // the call's end on each stream
+    ev.assign(c.tev.begin() + 5, c.tev.begin() + (long)n_tev);
+    HIP_OK(hipEventRecord(e0, d->stream));
+    // the call's own words start at zero: the hand-off words, the error word and the fixup stamps (adjacent in
+    // the read-back block), the cpuset table when a pod may bind CPUs; and the call's start stamp.  (The split
+    // selects' counters stay zero between calls -- an aborted call resets them.)
+    const int64_t nw_out = (int64_t)(ol.st - ol.err) / 4, nw_cs = any_cpu ? 8 * (int64_t)n_pods : 0;
+    const int64_t nw = std::max(std::max(sl.words, nw_out), nw_cs);
+    hipLaunchKernelGGL(k_call_begin, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, d->stream,
+                       reinterpret_cast<uint32_t*>(c.d_sched), sl.words, reinterpret_cast<uint32_t*>(d_err), nw_out,
+                       reinterpret_cast<uint32_t*>(c.d_cpusets), nw_cs, d_st);
+    HIP_OK(hipEventRecord(d->ev_start, d->stream));
+    HIP_OK(hipStreamWaitEvent(d->estream, d->ev_start, 0));
+    return KE_OK;
+  }
+
+  // the buffers of one eval_select: the stream's score matrix, part lists and part counters; the lists it makes
+  struct EvalBufs {
+    uint16_t* scores;
+    uint32_t* split;
+    int32_t* pdone;
+    uint32_t* lists;
+    int32_t* cnt;
   };
-  return KE_OK;
+
+  // Batch a.b's eval + candidate lists on stream a.es, in the mode of its plan: exact top-k_j lists straight into
+  // d_cand; stale top-(k_j + KMAX) lists into the run's stale buffer; select-ahead top-(k_j + 2 KMAX) lists into the
+  // pre-fix buffer (k_fixlist makes the Reserve kernel's lists).
+  int eval_select(const EvalSelect& a) {
+    published = false;
+    const int b = a.b;
+    hipStream_t const es = a.es;
+    const Batch& bt = batches[b];
+    const SelectPlan& sp = sel[(size_t)b];
+    const bool pipe = sp.mode != SEL_EXACT, pre = sp.mode == SEL_AHEAD;
+    const int bp = bt.pods;
+    const bool ds = bt.ds, cpu = bt.cpu;
+    EvalBufs eb;
+    eb.scores = a.alt ? d->d_scores2 : d->d_scores;
+    eb.split = a.alt ? d->d_split2 : d->d_split;
+    eb.pdone = d->d_parts_done + (a.alt ? MAX_BATCH : 0);
+    eb.lists = pre    ? d->d_pre + (size_t)(b & 1) * MAX_BATCH * KSTALE2
+               : pipe ? d->d_stale + (size_t)(b & 1) * MAX_BATCH * KSTALE
+                      : d->d_cand;
+    eb.cnt = pre    ? reinterpret_cast<int32_t*>(d->d_pre + (size_t)2 * MAX_BATCH * KSTALE2) + (b & 1) * MAX_BATCH
+             : pipe ? d->d_stale_cnt + (b & 1) * MAX_BATCH
+                    : d->d_cand_cnt;
+    const bool prof = every > 0 && b % every == 0;
+    hipEvent_t* pe = prof ? &ev[(size_t)(b / every) * PE] : nullptr;
+    const int32_t* bbase = d_bases + b;
+    const bool argmax1 = !sharded && bp == 1 && !pipe && N > 0;  // selectHost of one pod: a grid-wide argmax
+    // this rank's node range (unsharded and loopback: every node)
+    int lo = 0, hi = N;
+    if (N > 0 && sharded && !d->loopback) shard_range(N, d->rank, d->world, &lo, &hi);
+    // a plain batch with nodes to evaluate: k_eval_batch writes the eval-start stamp itself (one launch
+    // less on the eval stream); else k_batch_begin — a re-run remainder keeps its batch's first dequeue
+    // stamp (latency counts from there)
+    const bool fold_begin = !ds && !argmax1 && !rerun && hi > lo;
+    if (!fold_begin)
+      hipLaunchKernelGGL(k_batch_begin, dim3(1), dim3(MAX_BATCH), 0, es, estamps + (rerun ? n_batches : b),
+                         ds ? d->d_dsmax : nullptr, argmax1 ? d->d_cand : nullptr);
+    // (with two eval streams the wait is a one-wave kernel ahead of the eval, outside its timing: an eval grid
+    // spinning on the flag would hold the CUs the other stream's select needs)
+    const bool plain_rec = !cpu && !ds && !numa && use_record_eval(bp);
+    const bool wait_kernel = a.dwait && (!plain_rec || a.alt || (d->estream2 != nullptr && !sharded) || hi <= lo);
+    if (wait_kernel)
+      hipLaunchKernelGGL(k_handoff, dim3(1), dim3(64), d->excl_lds, es, nullptr, 0, a.dwait, d_err, nullptr, a.dwant);
+    if (prof) HIP_OK(hipEventRecord(pe[0], es));
+    if (N <= 0) {
+      if (prof) HIP_OK(hipEventRecord(pe[1], es));
+      if (prof) HIP_OK(hipEventRecord(pe[3], es));
+      HIP_OK(fill_async(eb.cnt, 0, sizeof(int32_t) * MAX_BATCH, es));
+    } else {
+      int rc;
+      if (hi > lo && (rc = launch_eval(a, eb, lo, hi, plain_rec, fold_begin ? estamps + b : nullptr,
+                                       wait_kernel ? nullptr : a.dwait)))
+        return rc;
+      if (prof) HIP_OK(hipEventRecord(pe[1], es));
+      // the nodes batch b-2 changed, once it is done (k_patch waits for the flag; folding it into the split select
+      // was measured slower: 256 select workgroups spinning on the flag)
+      if (a.pwait)
+        hipLaunchKernelGGL(pick_patch(ext, ns), dim3((unsigned)bp), dim3(64), d->excl_lds, es, d->soa, c.d_pods, bbase, k,
+                           a.ptl, eb.scores, d->capacity, a.pwait, d_err);
+      if (ds && sharded && !d->loopback) {  // DefaultNormalizeScore's max over the feasible nodes of all ranks
+        if ((rc = coll_all_reduce(d, d->d_dsmax, 1, KE_COLL_U32, KE_COLL_MAX, es))) return rc;
+      }
+      if (prof) HIP_OK(hipEventRecord(pe[3], es));
+      if ((rc = launch_select(a, eb, argmax1))) return rc;
+    }
+    if (prof) HIP_OK(hipEventRecord(pe[2], es));
+    return KE_OK;
+  }
+
+  // the eval kernel of batch a.b over this rank's nodes [lo, hi), and the BestEffort fallback of a NUMA context
+  int launch_eval(const EvalSelect& a, const EvalBufs& eb, int lo, int hi, bool plain_rec, uint64_t* stamp,
+                  const int32_t* dwait) {
+    const int b = a.b, bp = batches[b].pods;
+    const bool ds = batches[b].ds, cpu = batches[b].cpu;
+    const int32_t* bbase = d_bases + b;
+    // a singleton batch has one pod's worth of lanes: single-wave blocks spread it over every CU
+    const int blk = bp == 1 ? 64 : EVAL_BLOCK;
+    const dim3 grid = eval_grid(hi - lo, blk, bp, EVAL_PPB);
+    uint32_t* dcnt = numa ? d->d_defer_cnt + b : nullptr;
+    if (plain_rec) {  // plain batch: the record-based evaluation
+      hipLaunchKernelGGL(pick_eval_plain(ext, ns), grid, dim3(blk), 0, a.es, d->soa, lo, hi, c.d_pods, bbase, bp, k,
+                         eb.scores, d->capacity, stamp, dwait, d_err);
+    } else {
+      const auto eval = pick_eval_batch(ds, numa, cpu, batches[b].hint, ext, ns);
+      if (!eval) return no_variant("k_eval_batch with node sets and a DeviceShare / NUMA / cpuset batch");
+      hipLaunchKernelGGL(eval, grid, dim3(blk), 0, a.es, d->soa, lo, hi, c.d_pods, bbase, bp, EVAL_PPB, k, eb.scores,
+                         d->capacity, d->d_dsraw, d->d_defer, dcnt, d->d_aff, d->d_dsmax, stamp);
+    }
+    if (numa) {  // a DeviceShare pod defers only on nodes without a device cache (no DeviceShare hints there)
+      uint32_t* fb = reinterpret_cast<uint32_t*>(d->d_defer + (int64_t)MAX_BATCH * d->capacity);
+      hipLaunchKernelGGL(pick_numa_fallback(false, cpu), dim3(FALLBACK_BLOCKS), dim3(64), 0, a.es, d->soa, c.d_pods, bbase,
+                         k, d->d_defer, dcnt, eb.scores, d->capacity, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         nullptr, ds ? d->d_dsmax : nullptr, cpu ? d->d_aff : nullptr, ds ? d->d_dsraw : nullptr, fb);
+      hipLaunchKernelGGL(pick_numa_finish(false, cpu), dim3(FINISH_BLOCKS), dim3(64), 0, a.es, d->soa, c.d_pods, bbase,
+                         k, d->d_defer, dcnt, eb.scores, d->capacity, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         nullptr, ds ? d->d_dsmax : nullptr, cpu ? d->d_aff : nullptr, ds ? d->d_dsraw : nullptr, fb);
+    }
+    return KE_OK;
+  }
+
+  // the candidate lists of batch a.b out of its scores: a grid-wide argmax (one pod, serial), a split select (a plain
+  // batch over many nodes: its pods' selections split over several workgroups each, merged by the last part or left
+  // to k_fixlist), one workgroup per pod, or node-sharded: per-shard top-k_j, all-gather, merge
+  int launch_select(const EvalSelect& a, const EvalBufs& eb, bool argmax1) {
+    const int b = a.b, bp = batches[b].pods;
+    const bool ds = batches[b].ds;
+    const SelectPlan& sp = sel[(size_t)b];
+    hipStream_t const es = a.es;
+    const bool rsv_here = matched && (!fused || b == n_batches - 1);  // the pod's matched reservations
+    auto select = [&](int slo, int shi, bool resident, uint32_t* cand, int32_t* cnt, int32_t* pub) {
+      hipLaunchKernelGGL(pick_select(ds, resident), dim3((unsigned)bp), dim3(SELECT_BLOCK), 0, es, eb.scores, d->capacity,
+                         slo, shi, cand, cnt, d->d_dsraw, d->d_dsmax, k.wp_ds, sp.kext, sp.L, (int64_t)0, nullptr, nullptr,
+                         nullptr, pub, a.sstart);
+    };
+    if (argmax1) {  // d_cand[0] zeroed by k_batch_begin
+      hipLaunchKernelGGL(pick_argmax1(ds), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, es, eb.scores, 0, N,
+                         d->d_dsraw, d->d_dsmax, k.wp_ds, d->d_cand, d->d_cand_cnt);
+      if (rsv_here) {  // the Reservation plugin
+        hipLaunchKernelGGL(k_rsv_pick, dim3(1), dim3(64), 0, es, eb.scores, d->d_rsv, (int)ctx->rsv_pairs.size(),
+                           (int64_t)ctx->cfg.weight_reservation, (int)ctx->rsv_affinity, d->d_cand, d->d_rsv_out,
+                           ds ? d->d_dsraw : nullptr, d->d_dsmax, k.wp_ds);
+        HIP_OK(copy_async(d->h_rsv_out.data(), d->d_rsv_out, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, es));
+      }
+    } else if (!sharded && sp.parts > 1) {
+      // (select-ahead: no parts_done -- the parts stay sorted in `split` and k_fixlist<PARTS> merges them)
+      hipLaunchKernelGGL(pick_select(false, sp.rc_split), dim3((unsigned)bp, (unsigned)sp.parts), dim3(SELECT_BLOCK), 0, es,
+                         eb.scores, d->capacity, 0, (int)N, eb.split, reinterpret_cast<int32_t*>(eb.split + MAX_BATCH * sp.L),
+                         d->d_dsraw, d->d_dsmax, k.wp_ds, sp.kext, sp.L, (int64_t)gath_words(sp.L), eb.lists, eb.cnt,
+                         (sp.mode == SEL_AHEAD && d->fix_merge) ? nullptr : eb.pdone, a.rpub,
+                         a.sstart);  // the last part merges
+      published = a.rpub != nullptr;
+    } else if (!sharded) {
+      select(0, N, sp.rc_one, eb.lists, eb.cnt, ds ? nullptr : a.rpub);
+      published = a.rpub != nullptr && !ds;
+    } else {
+      const int gw = gath_words(sp.L);
+      for (int r = 0; r < d->world; r++) {
+        if (!d->loopback && r != d->rank) continue;
+        int slo, shi;
+        shard_range(N, r, d->world, &slo, &shi);
+        uint32_t* blk = d->d_gath + (int64_t)r * gw;
+        select(slo, shi, select_resident(slo, shi), blk, reinterpret_cast<int32_t*>(blk + MAX_BATCH * sp.L), nullptr);
+      }
+      if (!d->loopback) {
+        uint32_t* mine = d->d_gath + (int64_t)d->rank * gw;  // in place: send = own block of recv
+        const int crc = coll_all_gather(d, mine, d->d_gath, (size_t)gw, es);
+        if (crc) return crc;
+      }
+      hipLaunchKernelGGL(k_merge, dim3((unsigned)bp), dim3(MERGE_BLOCK), 0, es, d->d_gath, d->world, sp.L, sp.kext, eb.lists,
+                         eb.cnt);
+      if (matched) return rsv_stages(es, eb, ds);  // a matched singleton
+    }
+    return KE_OK;
+  }
+
+  // the Reservation plugin of a node-sharded matched singleton, in stages with the ranks' collectives between them
+  int rsv_stages(hipStream_t es, const EvalBufs& eb, bool ds) {
+    int rlo = 0, rhi = N;
+    if (!d->loopback) shard_range(N, d->rank, d->world, &rlo, &rhi);
+    RsvPickSt* st = d->d_rsv_st;
+    const bool coll = !d->loopback && (d->comm || d->host_fn);
+    const struct {
+      decltype(&k_rsv_stage<0>) stage;
+      void* word;  // all-reduced behind the stage (`count` of them)
+      size_t count;
+      int dt, op;
+    } stages[6] = {{k_rsv_stage<0>, &st->order, 1, KE_COLL_I64, KE_COLL_MIN}, {k_rsv_stage<1>, &st->node, 1, KE_COLL_I32, KE_COLL_MIN},
+                   {k_rsv_stage<2>, &st->mx, 1, KE_COLL_I32, KE_COLL_MAX},    {k_rsv_stage<3>, &st->best, 1, KE_COLL_U64, KE_COLL_MAX},
+                   {k_rsv_stage<4>, &st->wt, 2, KE_COLL_I32, KE_COLL_MAX},    {k_rsv_stage<5>, nullptr, 0, 0, 0}};  // (wt, nw)
+    for (const auto& s : stages) {
+      hipLaunchKernelGGL(s.stage, dim3(1), dim3(64), 0, es, eb.scores, d->d_rsv, (int)ctx->rsv_pairs.size(), rlo, rhi,
+                         (int64_t)ctx->cfg.weight_reservation, (int)ctx->rsv_affinity, eb.lists, st, d->d_rsv_out,
+                         ds ? d->d_dsraw : nullptr, d->d_dsmax, k.wp_ds);
+      int crc;
+      if (coll && s.word && (crc = coll_all_reduce(d, s.word, s.count, s.dt, s.op, es))) return crc;
+    }
+    HIP_OK(copy_async(d->h_rsv_out.data(), d->d_rsv_out, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, es));
+    return KE_OK;
+  }
+
+  // The pipelined run [b, run_end[b]): k_resolve_run on `stream`, every batch's eval + lists on the eval streams in
+  // the call's schedule (plan()).  b becomes the run's end.
+  int run(int& b) {
+    const int r0 = b, e = run_end[b];
+    int rc;
+    const THelp th{d_tlist, d_tmx, d_tready, fixup ? 0 : d->t_helpers, d->t_help_ignore, d_rres + r0};
+    bool sorted = true;  // (every batch's lists descending: k_fixlist's always are)
+    for (int q = r0; q < e; q++) sorted = sorted && sel[(size_t)q].sorted;
+    const auto resolve = pick_resolve_run(quota, ext, ns);
+    if (!resolve) return no_variant("k_resolve_run with node sets and quota");
+    hipLaunchKernelGGL(resolve, dim3(1 + th.H), dim3(res_threads<false>()), 0, d->stream, d->soa, c.d_pods, d_bases, r0,
+                       e - r0, k, d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score, ctx->cfg.global_node_offset, d_st,
+                       d_pst, c.d_devalloc, d_ready, d_done, d_err, d->d_trows, d->d_tcnt, d->d_chg, N,
+                       fixup ? nullptr : d->d_stale, fixup ? nullptr : d->d_stale_cnt, (int)sorted, th);
+    if (r0 > 0) HIP_OK(hipStreamWaitEvent(d->estream, d->ev_res[(r0 - 1) % R], 0));
+    if (two_es) HIP_OK(hipStreamWaitEvent(d->estream2, r0 > 0 ? d->ev_res[(r0 - 1) % R] : d->ev_start, 0));
+    for (int q = r0; q < e; q++) {
+      const int bp = batches[q].pods;
+      uint32_t* const stale = d->d_stale + (size_t)(q & 1) * MAX_BATCH * KSTALE;  // batch q's lists for the replay
+      int32_t* const stale_cnt = d->d_stale_cnt + (q & 1) * MAX_BATCH;
+      const int32_t* const tl2 = d_tlist + ((q - 2) & 1) * (1 + MAX_BATCH);  // the T list of batch q-2
+      EvalSelect a{q, d->estream};
+      if (fixup) {  // stale lists, made exact by k_fixup behind batch q-1
+        if ((rc = eval_select(a))) return rc;
+        hipLaunchKernelGGL(pick_fixup(ext, ns), dim3((unsigned)bp), dim3(FIX_BLOCK), 0, d->estream, d->soa, c.d_pods,
+                           d_bases + q, k, stale, stale_cnt, d->d_trows, d->d_tcnt, d->d_cand, d->d_cand_cnt, d_done,
+                           q == r0 ? -1 : q - 1, d_ready + q, d_err, d_fst + 2 * q);
+        continue;
+      }
+      // the stale lists go to the replay as they are; batches alternate between the eval streams
+      a.alt = two_es && ((q - r0) & 1);
+      a.es = a.alt ? d->estream2 : d->estream;
+      if (ahead) {
+        // select-ahead: batch q's eval waits for batch q-3 (the first two of the run for the Reserve kernel's
+        // residency: k_fixlist workgroups spinning on a done flag must never keep it off the CUs), its select
+        // follows at once, and k_fixlist brings in batch q-2's changed nodes and publishes the lists
+        a.dwait = q - 3 >= r0 ? d_done + (q - 3) : q - 2 < r0 ? d_rres + r0 : nullptr;
+        if ((rc = eval_select(a))) return rc;
+        const SelectPlan& sp = sel[(size_t)q];
+        const int32_t* const done2 = q - 2 >= r0 ? d_done + (q - 2) : nullptr;
+        if (d->fix_merge && sp.parts > 1)  // the select left its parts unmerged in the split buffer: the fix merges them
+          hipLaunchKernelGGL(pick_fixlist(ext, true, ns), dim3((unsigned)bp), dim3(FIXL_PARTS_BLOCK), 0, a.es, d->soa,
+                             c.d_pods, d_bases + q, k, a.alt ? d->d_split2 : d->d_split, nullptr, tl2, done2, stale,
+                             stale_cnt, d_ready + q, d_err, (int64_t)gath_words(sp.L), sp.parts);
+        else
+          hipLaunchKernelGGL(pick_fixlist(ext, false, ns), dim3((unsigned)bp), dim3(FIXL_BLOCK), 0, a.es, d->soa, c.d_pods,
+                             d_bases + q, k, d->d_pre + (size_t)(q & 1) * MAX_BATCH * KSTALE2,
+                             reinterpret_cast<const int32_t*>(d->d_pre + (size_t)2 * MAX_BATCH * KSTALE2) + (q & 1) * MAX_BATCH,
+                             tl2, done2, stale, stale_cnt, d_ready + q, d_err, (int64_t)0, 1);
+        continue;
+      }
+      // the k_patch schedule (two eval streams): batch q's eval waits only for batch q-3 -- through batch q-1's
+      // select having started (it followed k_patch(q-1), which waited for done[q-3]: the select's workgroups are
+      // resident before this eval's grid takes the CUs; every workgroup of that select counts itself in
+      // sstart[q-1]) -- and k_patch brings in batch q-2's changed nodes.  One eval stream: the eval waits for q-2.
+      const bool after_sel = two_es && d->eval_patch;
+      a.dwait = after_sel ? (q - 1 >= r0 ? d_sstart + (q - 1) : d_rres + r0) : (q - 2 >= r0 ? d_done + (q - 2) : nullptr);
+      a.dwant = after_sel && q - 1 >= r0 ? batches[q - 1].pods * sel[(size_t)q - 1].parts : 1;
+      a.rpub = d_ready + q;
+      a.pwait = after_sel && q - 2 >= r0 ? d_done + (q - 2) : nullptr;
+      a.ptl = tl2;
+      a.sstart = after_sel ? d_sstart + q : nullptr;
+      if ((rc = eval_select(a))) return rc;
+      if (!published)
+        hipLaunchKernelGGL(k_handoff, dim3(1), dim3(64), d->excl_lds, a.es, d_ready + q, (int32_t)bp, nullptr, d_err,
+                           nullptr, 1);
+    }
+    HIP_OK(hipEventRecord(d->ev_res[(e - 1) % R], d->stream));
+    HIP_OK(hipEventRecord(d->ev_sel[(e - 1) % R], d->estream));
+    if (two_es) HIP_OK(hipEventRecord(d->ev_sel2, d->estream2));
+    n_pipelined += e - r0;
+    b = e;
+    if (b < n_batches && run_end[b] == 0) {  // a serial batch next: the run's eval streams drain first
+      HIP_OK(hipStreamWaitEvent(d->stream, d->ev_sel[(e - 1) % R], 0));
+      if (two_es) HIP_OK(hipStreamWaitEvent(d->stream, d->ev_sel2, 0));
+    }
+    return KE_OK;
+  }
+
+  // A serial batch: eval, select and Reserve in order on one stream (no cross-stream hand-off).  b advances unless
+  // a DeviceShare batch stopped early: then its remaining pods run again as batch b.
+  int serial(int& b) {
+    const int bp = batches[b].pods;
+    const bool ds = batches[b].ds, cpu = batches[b].cpu;
+    const int32_t* bbase = d_bases + b;
+    const bool fused_b = fused && b == n_batches - 1;
+    int rc = KE_OK;
+    if (fused_b) {  // the fused matched pod: the speculation check, then its rows (gated) before its eval
+      hipLaunchKernelGGL(k_rsv_check, dim3(1), dim3(256), 0, d->stream, d_chosen, bases[b], d->d_rsv,
+                         (int)ctx->rsv_pairs.size(), ctx->cfg.global_node_offset, d->d_rsv_gate);
+      if ((rc = device_refresh_flush(ctx, d->d_rsv_gate))) return rc;
+    }
+    if (pre_b != b) rc = eval_select({b, d->stream});
+    pre_b = -1;
+    if (rc) return rc;
+    if (fused_b) {
+      hipLaunchKernelGGL(k_rsv_gate_apply, dim3(1), dim3(64), 0, d->stream, d->d_rsv_gate, d->d_cand_cnt);
+      HIP_OK(copy_async(d->h_rsv_out.data() + 4, d->d_rsv_gate, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+    }
+    if (bp == 1) {  // one pod: the single-node Reserve (cpuset accumulator when it binds)
+      int elo = 0, ehi = 0;  // nodes whose affinities this batch's eval stored in d_aff (binding batches)
+      if (cpu && numa) {
+        ehi = N;
+        if (sharded && !d->loopback) shard_range(N, d->rank, d->world, &elo, &ehi);
+      }
+      hipLaunchKernelGGL(pick_cpuset_reserve(ds, numa), dim3(1), dim3(64), 0, d->stream, d->soa, c.d_pods, bbase, k,
+                         d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score, ctx->cfg.global_node_offset, d_st, d_pst, b,
+                         c.d_devalloc, numa ? c.d_numaalloc : nullptr, c.d_cpusets, d->d_aff, elo, ehi);
+    } else {
+      const auto resolve = pick_resolve(ds, numa, quota, ns);
+      if (!resolve) return no_variant("k_resolve with node sets and a DeviceShare batch, NUMA or quota");
+      hipLaunchKernelGGL(resolve, dim3(1), dim3(resolve_threads(numa)), 0, d->stream, d->soa, c.d_pods, bbase, bp, k,
+                         d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score, ctx->cfg.global_node_offset, d_st, d_pst, b,
+                         c.d_devalloc, c.d_numaalloc, d->d_chg, N, (int)sel[(size_t)b].sorted);
+      bool again = false;
+      if (batches[b].cut && (rc = cut_check(b, &again))) return rc;
+      rerun = again;
+      if (again) return KE_OK;
+    }
+    if (b + 1 < n_batches && run_end[b + 1] > 0)  // the next run's eval stream waits for this Reserve
+      HIP_OK(hipEventRecord(d->ev_res[b % R], d->stream));
+    b++;
+    return KE_OK;
+  }
+
+  // A DeviceShare batch may stop early: the host reads its cut word and, with a cut, makes its remaining pods batch b
+  // (*again).  The next serial batch's eval + select go in behind the read-back, so the device keeps working while
+  // the host waits (without a cut they stand; with one the re-run batch overwrites what they wrote).
+  int cut_check(int b, bool* again) {
+    int rc;
+    if (!d->h_cut.resize(1)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the cut word");
+    HIP_OK(copy_async(d->h_cut.data(), d->d_dsmax + DSB_CUT, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+    if (b + 1 < n_batches && run_end[b + 1] == 0 && !(fused && b + 1 == n_batches - 1)) {
+      const bool keep = rerun;
+      rerun = false;
+      rc = eval_select({b + 1, d->stream});
+      rerun = keep;
+      if (rc) return rc;
+      pre_b = b + 1;
+    }
+    HIP_OK(hipStreamSynchronize(d->stream));
+    const int32_t cut = d->h_cut[0];
+    if (cut < 0) return KE_OK;
+    pre_b = -1;
+    const int end = bases[b] + batches[b].pods;
+    if (cut <= bases[b] || cut >= end) return fail(KE_ERR_DEVICE, "DeviceShare batch cut out of range");
+    batches[b].pods = end - cut;  // (its pod count changed: its select is planned again)
+    bases[b] = cut;
+    sel[(size_t)b] = plan_select(N, batches[b], SEL_EXACT, sharded, knob);
+    HIP_OK(copy_async(d_bases + b, &bases[b], sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
+    ctx->last_ds_cuts++;
+    *again = true;
+    return KE_OK;
+  }
+
+  // The call's outputs go to one page-locked staging area (async copies, no host wait) and are copied out after
+  // the synchronisation; allocations none of the call's batches can make are not read back (zero).  *fin completes
+  // the call.
+  int readback(DevFinish* fin) {
+    const auto t_fl = clk::now();
+    flush_mirror_async(*ctx);  // the earlier calls' deferred host mirror, on a host thread while the device works
+    const double flush_ms = ms_since(t_fl);
+    HIP_OK(hipEventRecord(e1, d->stream));
+    bool any_ds = false;
+    for (const Batch& bt : batches) any_ds = any_ds || bt.ds || bt.hint;
+    const bool vf_out = d->soa.vfo != nullptr;
+    const size_t np = (size_t)n_pods, nb = (size_t)n_batches;
+    const HostOutLayout ho(ol, np, nb, want_score, any_ds, any_cpu, vf_out, numa);
+    if (!c.h_out.resize(ho.total)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the readback staging buffer");
+    uint8_t* const h = c.h_out.data();
+    HIP_OK(copy_async(h, c.d_out + ho.blk0, ho.blk_bytes, hipMemcpyDeviceToHost, d->stream));
+    HIP_OK(copy_async(h + ho.kerr, d->soa.kerr, 4, hipMemcpyDeviceToHost, d->stream));
+    if (any_ds) HIP_OK(copy_async(h + ho.dev, c.d_devalloc, 8 * np, hipMemcpyDeviceToHost, d->stream));
+    if (any_cpu) HIP_OK(copy_async(h + ho.cs, c.d_cpusets, 32 * np, hipMemcpyDeviceToHost, d->stream));
+    if (vf_out) HIP_OK(copy_async(h + ho.vf, d->d_vfo, 2 * DS_MINORS * np, hipMemcpyDeviceToHost, d->stream));
+    if (numa) HIP_OK(copy_async(h + ho.numa, c.d_numaalloc, 8 * 16 * np, hipMemcpyDeviceToHost, d->stream));
+    if (numa) HIP_OK(copy_async(h + ho.dcnt, d->d_defer_cnt, 4 * nb, hipMemcpyDeviceToHost, d->stream));
+    // the call's end on every stream: its completion waits for these events, not for the streams
+    HIP_OK(hipEventRecord(done_ev[0], d->stream));
+    HIP_OK(hipEventRecord(done_ev[1], d->estream));
+    if (d->estream2) HIP_OK(hipEventRecord(done_ev[2], d->estream2));
+    Completion cp;
+    cp.ctx = ctx;
+    cp.batches = std::move(batches), cp.bases = std::move(bases), cp.run_end = std::move(run_end);
+    cp.ho = ho, cp.h = h;
+    cp.n_pods = n_pods, cp.pods = pods;
+    cp.want_score = want_score, cp.numa = numa, cp.quota = quota;
+    cp.any_ds = any_ds, cp.any_cpu = any_cpu, cp.vf_out = vf_out;
+    cp.e0 = e0, cp.e1 = e1;
+    for (int i = 0; i < 3; i++) cp.done_ev[i] = done_ev[i];
+    cp.ev = std::move(ev);
+    for (int i = 0; i < 5; i++) cp.enq_ms[i] = ctx->host_ms[i];
+    cp.flush_ms = flush_ms;
+    cp.entry = ctx->call_entry, cp.behind = ctx->call_behind;
+    cp.copies = n_copies, cp.fills = n_fills, cp.n_pipelined = n_pipelined;
+    *fin = [cp = std::move(cp)](int32_t* chosen, int32_t* score) { return complete_call(cp, chosen, score); };
+    return KE_OK;
+  }
+};
+
+int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, bool want_score,
+                            DevFinish* fin) {
+  DeviceState* d = ctx->dev;
+  auto tp = clk::now();
+  HIP_OK(hipSetDevice(d->device));
+  int rc = device_refresh(ctx, now, ctx->rsv_fused);  // (a fused matched pod's rows: their scatters deferred)
+  if (rc) return rc;
+  ctx->host_ms[1] = ms_since(tp);
+  ctx->last_batch_ms.clear();
+  ctx->last_dev_alloc.clear();
+  ctx->last_total_ms = 0;
+  ctx->last_pod_lat.clear();
+  if (n_pods == 0) return KE_OK;
+  ScheduleCall call(ctx, n_pods, pods, want_score);
+  tp = clk::now();
+  if ((rc = call.stage())) return rc;
+  ctx->host_ms[2] = ms_since(tp);
+  tp = clk::now();
+  if ((rc = call.plan()) || (rc = call.buffers()) || (rc = call.reservations(now)) || (rc = call.begin())) return rc;
+  ctx->host_ms[3] = ms_since(tp);
+  tp = clk::now();
+  for (int b = 0; b < call.n_batches;)
+    if ((rc = call.run_end[b] > 0 ? call.run(b) : call.serial(b))) return rc;
+  HIP_OK(hipGetLastError());
+  ctx->last_enqueue_ms = ctx->host_ms[4] = ms_since(tp);
+  return call.readback(fin);
 }
 
 // cycles per unit of each phase of kernel `which` (0 k_resolve per pod, 1 k_numa_fallback per deferred pair,
@@ -9089,11 +8992,11 @@ int device_bench_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t 
   // the kernel ke_schedule runs for a plain batch of n_pods
   auto launch = [&]() {
     if (use_record_eval(n_pods))
-      hipLaunchKernelGGL((k_eval_plain<false>), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, 0, N, d->d_pods,
+      hipLaunchKernelGGL(pick_eval_plain(false, 0), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, 0, N, d->call.d_pods,
                          d->d_batch_base, n_pods, k, d->d_scores, d->capacity, nullptr, nullptr, nullptr);
     else
-      hipLaunchKernelGGL((k_eval_batch<false, false, false>), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, 0, N,
-                         d->d_pods, d->d_batch_base, n_pods, ppb, k, d->d_scores, d->capacity, d->d_dsraw, d->d_defer,
+      hipLaunchKernelGGL(pick_eval_batch(false, false, false, false, false, 0), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, 0, N,
+                         d->call.d_pods, d->d_batch_base, n_pods, ppb, k, d->d_scores, d->capacity, d->d_dsraw, d->d_defer,
                          nullptr, d->d_aff, d->d_dsmax, nullptr);
   };
   launch();  // warm

@@ -6,8 +6,9 @@ offset table (an exact integer added to a pair's total) dictates the whole lands
 score sits, how many nodes tie with it, how far below the next level lies.  The builders here return (tables, ids)
 for node_scores_load / schedule(node_scores=...); the reference stays the lock-step one of test_node_scores_host.py.
 
-Nothing here is imported from the library's dispatch: select_boundaries restates the host arithmetic of the select's
-wave segments and parts (the comments of select_seg / select_part in ke_kernels.hip) in Python."""
+Nothing here is imported from the library's dispatch: select_parts and select_boundaries restate the host arithmetic
+of the select's wave segments and parts (select_seg / select_part / select_parts in koordinator_amd/csrc/ke_plan.h) in
+Python; test_plan_host.py pins them to that header."""
 import ctypes as C
 
 import numpy as np
