@@ -661,7 +661,8 @@ int ke_abi_version(void);
 /* sizeof() of ke_config, ke_node, ke_node_metric, ke_pod_metric, ke_aggregated_usage, ke_pod,
  * ke_resource_map, ke_loadaware_args, ke_numa_args, ke_deviceshare_args, ke_device, ke_numa_zone, ke_cpu,
  * ke_quota_args, ke_quota, ke_gpu_partition, ke_ext_args, ke_node_resource, ke_pod_allocation, ke_pod_device_hints,
- * ke_gpu_template, ke_reservation, ke_reservation_alloc, ke_reservation_resource (in that order) for binding-layout checks. */
+ * ke_gpu_template, ke_reservation, ke_reservation_alloc, ke_reservation_resource, ke_pod_diagnosis (in that order) for
+ * binding-layout checks. */
 int ke_abi_struct_sizes(int32_t* sizes, int32_t n);
 /* 1 if this build has a usable HIP device and its gfx950 kernels loaded, else 0. */
 int ke_device_available(void);
@@ -948,6 +949,55 @@ int ke_node_scores_set(ke_ctx* ctx, int32_t node, int32_t n_tables, const uint16
  * call with a different n_pods, or after the table was replaced by a smaller one, is KE_ERR_INVALID.  Does not
  * wait for calls in flight. */
 int ke_pod_node_scores(ke_ctx* ctx, int32_t n_pods, const int32_t* table_ids);
+/* ---- FitError diagnosis of unschedulable pods (additive: KE_ABI_VERSION stays 14) -------------------
+ * A pod ke_schedule left at chosen = -1 must go back to the queue with a framework.FitError.  The reference reads
+ * three parts of it, all reductions of the Filter status map (framework.NodeToStatusMap) findNodesThatFitPod fills:
+ *  - the reason histogram behind the event text "0/N nodes are available: 812 Insufficient cpu, ...";
+ *  - Diagnosis.UnschedulablePlugins, copied into the queued pod info (frameworkext/eventhandlers/
+ *    reservation_handler.go:247-249), by which the queue decides which cluster events move the pod back;
+ *  - the per-node codes, handed to every PostFilter plugin (frameworkext/framework_extender.go:303,
+ *    reservation/plugin.go:571-600, ElasticQuota and coscheduling PostFilter): preemption skips
+ *    UnschedulableAndUnresolvable nodes.
+ * ke_diagnose classifies every (pod, node) pair exactly as ke_eval's status[] / reason[] would for the same
+ * arguments against the current state and returns the reductions only: nothing per pair is materialised on the
+ * device or copied back.  No state changes.  The diagnosis is of the state at the call, not of a pod's own turn
+ * inside an earlier ke_schedule.
+ *  - Each bitmap is optional (NULL).  Row p is words_per_pod words at bits + p*words_per_pod; bit (i & 63) of word
+ *    (i >> 6) = node i.  words_per_pod >= ceil(ke_num_nodes/64), else KE_ERR_INVALID; words and bits at or beyond
+ *    the node count are written as 0.  Without a bitmap words_per_pod is ignored.  An empty / deleted node slot
+ *    and a KE_CODE_ERROR node have no bit in any of them.
+ *  - Per pod: n_feasible + n_unschedulable + n_unresolvable + n_error == n_nodes, n_nodes + n_absent ==
+ *    ke_num_nodes, the reason_nodes[1..] sum to n_unschedulable + n_unresolvable, reason_nodes[0] == n_feasible +
+ *    n_error.
+ *  - Admission is ke_eval's, in its order and with its codes: completes calls in flight, consumes staged
+ *    ke_pod_node_sets ids (a pair outside the set counts under KE_REASON_NODE_SET, unresolvable) and staged
+ *    ke_pod_node_scores ids (ignored: scores do not filter), refuses reservation-matched / ignored / affinity pods
+ *    (KE_ERR_UNSUPPORTED).  ke_pod.quota is not looked at (ElasticQuota rejects in PreFilter, before any node: the
+ *    caller's own status).  A null `out` with n_pods > 0 is KE_ERR_INVALID; a node-sharded context is
+ *    KE_ERR_UNSUPPORTED; a context without a device KE_ERR_NO_DEVICE after the argument checks. */
+#define KE_DIAG_REASONS 128            /* every KE_REASON_* is < 128 (static_assert in the library) */
+#define KE_PLUGIN_LOADAWARE 1u
+#define KE_PLUGIN_NODENUMARESOURCE 2u
+#define KE_PLUGIN_DEVICESHARE 4u
+#define KE_PLUGIN_RESERVATION 8u
+#define KE_PLUGIN_NODERESOURCESFIT 16u
+#define KE_PLUGIN_NODE_SET 32u         /* the caller's in-tree filters (KE_REASON_NODE_SET) */
+typedef struct ke_pod_diagnosis {
+  int32_t n_nodes;         /* populated node slots evaluated: FitError.NumAllNodes */
+  int32_t n_absent;        /* empty / deleted slots below ke_num_nodes; not part of n_nodes or of any count below */
+  int32_t n_feasible;      /* KE_CODE_SUCCESS */
+  int32_t n_unschedulable; /* KE_CODE_UNSCHEDULABLE */
+  int32_t n_unresolvable;  /* KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE */
+  int32_t n_error;         /* KE_CODE_ERROR on a populated node */
+  uint32_t plugins;        /* KE_PLUGIN_* of every reason with a non-zero count: Diagnosis.UnschedulablePlugins */
+  int32_t reserved;
+  int32_t reason_nodes[KE_DIAG_REASONS]; /* nodes per KE_REASON_* (first failing filter, as ke_eval's reason[]) */
+} ke_pod_diagnosis;
+
+int ke_diagnose(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns, ke_pod_diagnosis* out,
+                int32_t words_per_pod, uint64_t* feasible, uint64_t* unschedulable, uint64_t* unresolvable);
+const char* ke_reason_message(int32_t reason);  /* the plugin's message, "" for an unknown code; never NULL */
+uint32_t ke_reason_plugin(int32_t reason);      /* KE_PLUGIN_* of a reason, 0 for NONE / unknown */
 
 /* NodeInfo.Requested / NonZeroRequested (MilliCPU, Memory) of `node` as the plugins see it for a pod that
  * matches no reservation (after the restore above and the Reserves of past ke_schedule calls). */

@@ -5,4 +5,4 @@ C ABI in include/koord_eval.h.  This package holds its ctypes binding (abi, eval
 Kubernetes-object helpers (model) and the synthetic cluster generator (synth).
 """
 from . import abi, model  # noqa: F401
-from .evaluator import Evaluator, KoordEvalError  # noqa: F401
+from .evaluator import Evaluator, KoordEvalError, reason_message, reason_plugin  # noqa: F401

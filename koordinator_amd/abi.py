@@ -421,9 +421,22 @@ class ReservationAlloc(C.Structure):  # ke_reservation_alloc
                 ("device", ((i64 * 3) * MAX_MINORS) * 3), ("owner_device", ((i64 * 3) * MAX_MINORS) * 3)]
 
 
+DIAG_REASONS = 128  # KE_DIAG_REASONS
+PLUGIN_LOADAWARE, PLUGIN_NODENUMARESOURCE, PLUGIN_DEVICESHARE, PLUGIN_RESERVATION = 1, 2, 4, 8  # KE_PLUGIN_*
+PLUGIN_NODERESOURCESFIT, PLUGIN_NODE_SET = 16, 32
+
+
+class PodDiagnosis(C.Structure):  # ke_pod_diagnosis
+    _fields_ = [("n_nodes", i32), ("n_absent", i32), ("n_feasible", i32), ("n_unschedulable", i32),
+                ("n_unresolvable", i32), ("n_error", i32), ("plugins", C.c_uint32), ("reserved", i32),
+                ("reason_nodes", i32 * DIAG_REASONS)]
+
+
 STRUCTS = [Config, Node, NodeMetric, PodMetric, AggregatedUsage, Pod, ResourceMap, LoadAwareArgs, NumaArgs,
            DeviceShareArgs, Device, NumaZone, Cpu, QuotaArgs, Quota, GpuPartition, ExtArgs, NodeResource,
-           PodAllocation, PodDeviceHints, GpuTemplate, Reservation, ReservationAlloc, ReservationResource]
+           PodAllocation, PodDeviceHints, GpuTemplate, Reservation, ReservationAlloc, ReservationResource,
+           PodDiagnosis]
+POD_DIAGNOSIS_DTYPE = np.dtype(PodDiagnosis)
 RESERVATION_DTYPE = np.dtype(Reservation)
 RESERVATION_RESOURCE_DTYPE = np.dtype(ReservationResource)
 RESERVATION_ALLOC_DTYPE = np.dtype(ReservationAlloc)
@@ -530,6 +543,9 @@ EXPORTS = {
     "ke_pods_assign": (C.c_int, [C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ke_estimate_pod": (C.c_int, [C.c_void_p, C.POINTER(Pod), C.c_void_p]),
     "ke_eval": (C.c_int, [C.c_void_p, i32, C.c_void_p, i64] + [C.c_void_p] * 7),
+    "ke_diagnose": (C.c_int, [C.c_void_p, i32, C.c_void_p, i64, C.c_void_p, i32] + [C.c_void_p] * 3),
+    "ke_reason_message": (C.c_char_p, [i32]),
+    "ke_reason_plugin": (C.c_uint32, [i32]),
     "ke_node_devices_set": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
     "ke_node_gpu_partitions": (C.c_int, [C.c_void_p, i32, i32, i32, i32, C.c_void_p]),
     "ke_node_devices_delete": (C.c_int, [C.c_void_p, i32]),

@@ -6,6 +6,7 @@
 #include <deque>
 #include <new>
 
+#include "ke_diag.h"
 #include "ke_host.h"
 
 namespace ke {
@@ -15,6 +16,8 @@ int device_create(Context* ctx);
 void device_destroy(Context* ctx);
 int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, uint8_t* status, uint8_t* reason,
                 int16_t* la, int16_t* numa, int16_t* ds, int16_t* total, int32_t* best);
+int device_diagnose(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, ke_pod_diagnosis* out,
+                    int32_t words_per_pod, uint64_t* const* bits);
 int device_schedule(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, int32_t* chosen, int32_t* score);
 int device_rsv_result(Context* ctx, int32_t* out4);
 int device_rsv_gate(const Context* ctx);
@@ -284,7 +287,8 @@ int ke_abi_struct_sizes(int32_t* sizes, int32_t n) {
                          (int32_t)sizeof(ke_ext_args),     (int32_t)sizeof(ke_node_resource),
                          (int32_t)sizeof(ke_pod_allocation), (int32_t)sizeof(ke_pod_device_hints),
                          (int32_t)sizeof(ke_gpu_template),   (int32_t)sizeof(ke_reservation),
-                         (int32_t)sizeof(ke_reservation_alloc), (int32_t)sizeof(ke_reservation_resource)};
+                         (int32_t)sizeof(ke_reservation_alloc), (int32_t)sizeof(ke_reservation_resource),
+                         (int32_t)sizeof(ke_pod_diagnosis)};
   const int32_t m = (int32_t)(sizeof(all) / sizeof(all[0]));
   for (int32_t i = 0; i < n && i < m; i++) sizes[i] = all[i];
   return m;
@@ -1063,6 +1067,35 @@ int ke_eval(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns, uin
   if (rc) return rc;
   return device_eval(&ctx->c, n_pods, pods, now_ns, status, reason, la_score, numa_score, ds_score, total, best);
 }
+
+// The reductions of ke_eval's status / reason over every node, per pod (include/koord_eval.h).  ke_eval's admission in
+// its order -- the staged set / table ids are consumed first, whatever follows -- then this call's own arguments.
+int ke_diagnose(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns, ke_pod_diagnosis* out,
+                int32_t words_per_pod, uint64_t* feasible, uint64_t* unschedulable, uint64_t* unresolvable) {
+  if (ctx) async_drain(ctx);
+  if (!ctx) return fail(KE_ERR_INVALID, "null context");
+  flush_mirror(ctx->c);
+  int rc = take_node_sets(ctx, n_pods, pods, false);
+  ctx->c.nsc_call = nullptr;  // score offsets do not filter
+  if (rc) return rc;
+  if (n_pods > 0 && !out) return fail(KE_ERR_INVALID, "diagnose: null out");
+  if ((feasible || unschedulable || unresolvable) && words_per_pod < (ctx->c.n_nodes + 63) / 64)
+    return fail(KE_ERR_INVALID, "diagnose: words_per_pod below ceil(ke_num_nodes / 64)");
+  rc = check_pods(pods, n_pods, &ctx->c);
+  if (rc) return rc;
+  if (ctx->c.cfg.global_node_offset != 0 || (ctx->c.dev && device_sharded(&ctx->c)))
+    return fail(KE_ERR_UNSUPPORTED, "diagnose: a node-sharded context");
+  rc = check_numa_deviceshare(ctx, pods, n_pods);
+  if (rc) return rc;
+  rc = check_cpuset(ctx, pods, n_pods);
+  if (rc) return rc;
+  rc = require_device(ctx);
+  if (rc) return rc;
+  uint64_t* const bits[DIAG_BITMAPS] = {feasible, unschedulable, unresolvable};
+  return device_diagnose(&ctx->c, n_pods, pods, now_ns, out, words_per_pod, bits);
+}
+const char* ke_reason_message(int32_t reason) { return diag_reason_message(reason); }
+uint32_t ke_reason_plugin(int32_t reason) { return diag_reason_plugin(reason); }
 
 static int schedule_sync(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns, int32_t* chosen, int32_t* score) {
   if (!ctx || (n_pods > 0 && !chosen)) return fail(KE_ERR_INVALID, "ke_schedule arguments");

@@ -28,6 +28,7 @@
 #include "ke_cpuacc.h"
 #include "ke_merge.h"
 #include "ke_host.h"
+#include "ke_diag.h"
 #include "ke_plan.h"
 #include "ke_types.h"
 
@@ -3246,6 +3247,135 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, int n_nodes, 
   }
 }
 
+// ---- ke_diagnose ------------------------------------------------------------------------------------
+// Where a diagnosis launch leaves its reductions: the raw tallies (ke_diag.h: DIAG_WORDS u32 per pod) and the
+// optional class bitmaps (`wpp` words per pod each, nullptr = not asked for), all zeroed by the host beforehand.
+struct DiagOut {
+  uint32_t* tally;
+  uint64_t* feasible;
+  uint64_t* unschedulable;
+  uint64_t* unresolvable;
+  int32_t wpp;
+};
+// class bitmap of a KE_CODE_* (nullptr: none, or not asked for) -- selects, not an indexed kernel argument
+__device__ __forceinline__ uint64_t* diag_bits(const DiagOut& dg, uint32_t status) {
+  return status == KE_CODE_SUCCESS                              ? dg.feasible
+         : status == KE_CODE_UNSCHEDULABLE                      ? dg.unschedulable
+         : status == KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE     ? dg.unresolvable
+                                                                : nullptr;
+}
+__device__ __forceinline__ int diag_class(uint32_t status) {
+  return status == KE_CODE_SUCCESS                          ? DIAG_FEASIBLE
+         : status == KE_CODE_UNSCHEDULABLE                  ? DIAG_UNSCHEDULABLE
+         : status == KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE ? DIAG_UNRESOLVABLE
+                                                            : DIAG_ERROR;
+}
+// One finished pair (k_numa_finish's diagnosis mode: few pairs, global atomics) into the pod's tallies and bitmap word.
+__device__ __forceinline__ void diag_add_pair(const DiagOut& dg, int p, int64_t i, uint32_t status, uint32_t reason) {
+  uint32_t* const row = dg.tally + (int64_t)p * DIAG_WORDS;
+  const int c = diag_class(status);
+  atomicAdd(&row[c], 1u);
+  atomicAdd(&row[c == DIAG_UNSCHEDULABLE || c == DIAG_UNRESOLVABLE ? (int)(reason & (KE_DIAG_REASONS - 1)) : 0], 1u);
+  uint64_t* const bits = diag_bits(dg, status);
+  if (bits)
+    atomicOr(reinterpret_cast<unsigned long long*>(bits + (int64_t)p * dg.wpp + (i >> 6)), 1ull << (i & 63));
+}
+
+// ke_diagnose's fused Filter + reduction: k_eval_parity's geometry and classification (lane = node, the row loaded
+// once into registers, the block's pods looped wave-uniformly, the same eval_pair call behind the same node-set
+// gate), with nothing written per pair.  A wave's 64 lanes are nodes [64w, 64w + 64), so the ballot of a class is the
+// pod's bitmap word w: lane 0 stores it (plain 8-byte stores, no atomics; skipped for a bitmap not asked for).  The
+// counts go through a per-workgroup LDS table [pod of the group][DIAG_WORDS]: per pod a wave adds its class
+// popcounts and peels the distinct reasons of its failing lanes (the first one's reason -> ballot of the lanes that
+// share it -> popcount; one to three rounds in practice), one LDS atomic each from lane 0; after the pod loop the
+// workgroup adds its non-zero bins to the global table.  Lanes past the last node, empty slots (DIAG_ABSENT alone)
+// and NUMA-deferred pairs (k_numa_finish_diag adds those) contribute to no ballot.
+template <bool NUMA, bool CPU, int NS = 0>
+__global__ __launch_bounds__(EVAL_BLOCK) void k_diag_eval(SoA s, int n_nodes, const DevPod* __restrict__ pods,
+                                                          int n_pods, KArgs k, DiagOut dg, uint64_t* defer_list,
+                                                          uint32_t* defer_cnt, int xcd) {
+  __shared__ uint32_t s_t[EVAL_PPB][DIAG_WORDS];
+  for (int t = threadIdx.x; t < EVAL_PPB * DIAG_WORDS; t += EVAL_BLOCK) (&s_t[0][0])[t] = 0u;
+  __syncthreads();
+  // xcd (the default; a context created under KOORDEVAL_DIAG_XCD=0 takes the A/B's plain mapping): the grid is eval_grid's and the block id is
+  // decoded as in k_eval_batch, every pod group of a node tile on one XCD.  Tiles past the last node are dead lanes.
+  int tile = blockIdx.x, group = blockIdx.y;
+  if (xcd) {
+    const int G = (int)gridDim.y;
+    const int b = (int)(blockIdx.x + blockIdx.y * gridDim.x), r = b >> 3;
+    tile = (r / G) * 8 + (b & 7), group = r % G;
+  }
+  const int i = tile * EVAL_BLOCK + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool live = i < n_nodes;
+  NodeRegs n;
+  if (live) {
+    load_row(s, i, n);
+    prepare_row(n);
+  }
+  const bool valid = live && (n.flags & NF_VALID);
+  const bool expired = live ? node_expired(n, k) : false;
+  NumaNode nv;
+  if (NUMA && live) numa_load(s, i, nv);
+  const bool wave_live = i - lane < n_nodes;  // (the wave's word lies below wpp >= ceil(n_nodes / 64))
+  const int64_t word = i >> 6;
+  const int p0 = group * EVAL_PPB;
+  const int p1 = min(n_pods, p0 + EVAL_PPB);
+  for (int p = p0; p < p1; p++) {
+    uint32_t status = KE_CODE_ERROR, reason = KE_REASON_NONE;
+    bool deferred = false;
+    if (valid) {
+      if (NS && !ns_ok<NS>(s, s.ns_ids[p], i)) {
+        status = KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE;
+        reason = KE_REASON_NODE_SET;
+      } else {
+        const EvalOut o = eval_pair<true, NUMA, NUMA, false, CPU, true>(n, expired, pods[p], k, s, i, nv);
+        deferred = NUMA && o.status == STATUS_DEFERRED;
+        status = o.status;
+        reason = o.reason;
+      }
+    }
+    if (NUMA) defer_push(deferred, ((uint64_t)p << 32) | (uint32_t)i, defer_list, defer_cnt);
+    const bool counted = valid && !deferred;
+    const uint64_t b_ok = __ballot(counted && status == KE_CODE_SUCCESS);
+    const uint64_t b_un = __ballot(counted && status == KE_CODE_UNSCHEDULABLE);
+    const uint64_t b_ur = __ballot(counted && status == KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE);
+    const uint64_t b_all = __ballot(counted);
+    const uint64_t b_abs = __ballot(live && !valid);
+    uint32_t* const row = s_t[p - p0];
+    if (lane == 0) {
+      if (wave_live) {
+        const int64_t w = (int64_t)p * dg.wpp + word;
+        if (dg.feasible) dg.feasible[w] = b_ok;
+        if (dg.unschedulable) dg.unschedulable[w] = b_un;
+        if (dg.unresolvable) dg.unresolvable[w] = b_ur;
+      }
+      const uint32_t c_ok = __popcll(b_ok), c_un = __popcll(b_un), c_ur = __popcll(b_ur);
+      const uint32_t c_err = __popcll(b_all) - c_ok - c_un - c_ur, c_abs = __popcll(b_abs);
+      if (c_ok) atomicAdd(&row[DIAG_FEASIBLE], c_ok);
+      if (c_un) atomicAdd(&row[DIAG_UNSCHEDULABLE], c_un);
+      if (c_ur) atomicAdd(&row[DIAG_UNRESOLVABLE], c_ur);
+      if (c_err) atomicAdd(&row[DIAG_ERROR], c_err);
+      if (c_abs) atomicAdd(&row[DIAG_ABSENT], c_abs);
+      if (c_ok + c_err) atomicAdd(&row[KE_REASON_NONE], c_ok + c_err);
+    }
+    uint64_t rest = b_un | b_ur;  // wave-uniform: the failing lanes whose reason is not yet counted
+    while (rest) {
+      const int lead = __ffsll((unsigned long long)rest) - 1;
+      const uint32_t r = (uint32_t)__shfl((int)reason, lead, 64);
+      const uint64_t same = __ballot(((rest >> lane) & 1ull) && reason == r);
+      if (lane == 0) atomicAdd(&row[r & (KE_DIAG_REASONS - 1)], (uint32_t)__popcll(same));
+      rest &= ~same;
+    }
+  }
+  __syncthreads();
+  uint32_t* const g = dg.tally + (int64_t)p0 * DIAG_WORDS;  // the group's rows are contiguous in both tables
+  for (int t = threadIdx.x; t < (p1 - p0) * DIAG_WORDS; t += EVAL_BLOCK) {
+    const uint32_t v = (&s_t[0][0])[t];
+    if (v) atomicAdd(&g[t], v);
+  }
+}
+
 // DeviceShare NormalizeScore (DefaultNormalizeScore(MaxNodeScore, false): score*100/max when max > 0)
 __device__ __forceinline__ int32_t ds_norm(int32_t raw, uint32_t dsmax1) {
   const int32_t mx = dsmax1 > 0 ? (int32_t)dsmax1 - 1 : 0;
@@ -3929,6 +4059,30 @@ __global__ __launch_bounds__(64) void k_numa_finish(SoA s, const DevPod* __restr
         if (o.total >= 0) atomicMax(dsmax, (uint32_t)o.ds + 1);
       }
     }
+  }
+}
+// k_numa_finish's third output mode as a kernel of its own, so that the two above stay what they are: ke_diagnose's
+// launch (its pods start at 0) evaluates the pair the same way, adds it to the pod's tallies and ORs its bit into the
+// pod's class bitmap word (`dg`); nothing else is written.
+template <bool CS>
+__global__ __launch_bounds__(64) void k_numa_finish_diag(SoA s, const DevPod* __restrict__ pods, KArgs k,
+                                                         const uint64_t* __restrict__ list,
+                                                         const uint32_t* __restrict__ cnt,
+                                                         const uint32_t* __restrict__ fb_in, DiagOut dg) {
+  const uint32_t n = *cnt;
+  for (uint32_t w = blockIdx.x * 64 + threadIdx.x; w < n; w += FINISH_BLOCKS * 64) {
+    const uint64_t it = list[w];
+    const int p = (int)(it >> 32);
+    const int64_t i = (int64_t)(uint32_t)it;
+    const DevPod pod = pods[p];
+    NumaNode nv;
+    numa_load(s, i, nv);
+    NodeRegs nr;
+    load_row(s, i, nr);
+    prepare_row(nr);
+    const bool expired = node_expired(nr, k);
+    const EvalOut o = eval_pair<false, true, false, true, CS>(nr, expired, pod, k, s, i, nv, fb_in[w]);
+    diag_add_pair(dg, p, i, o.status, o.reason);
   }
 }
 
@@ -7001,6 +7155,10 @@ struct DeviceState {
   int64_t parity_cap = 0;
   uint32_t* d_best = nullptr;
   int64_t best_cap = 0;
+  // ke_diagnose: the raw tallies [pods][DIAG_WORDS] u32, then the bitmaps asked for ([pods][words_per_pod] u64 each)
+  void* d_diag = nullptr;
+  int64_t diag_cap = 0;
+  bool diag_xcd = true;  // k_diag_eval's XCD-aware block mapping (KOORDEVAL_DIAG_XCD=0: the plain one, an A/B; §4q)
   int profile_every = 0;
   // node sharding (ke_shard_init): this rank evaluates/selects nodes shard_range(rank); the per-shard
   // candidate lists meet in d_gath through an RCCL all-gather (or, loopback, all shards run here)
@@ -7127,6 +7285,7 @@ int device_create(Context* ctx) {
   if (const char* e = std::getenv("KOORDEVAL_SELECT_AHEAD")) d->select_ahead = std::atoi(e) != 0;
   if (const char* e = std::getenv("KOORDEVAL_FIX_MERGE")) d->fix_merge = std::atoi(e) != 0;
   if (const char* e = std::getenv("KOORDEVAL_T_HELPERS_IGNORE")) d->t_help_ignore = std::atoi(e) != 0;
+  if (const char* e = std::getenv("KOORDEVAL_DIAG_XCD")) d->diag_xcd = std::atoi(e) != 0;
   HIP_OK(hipStreamCreateWithPriority(&d->stream, hipStreamNonBlocking, prio_hi));
   HIP_OK(hipStreamCreateWithPriority(&d->estream, hipStreamNonBlocking, prio_lo));
   for (int e = 0; e < DeviceState::EV_RING; e++) {
@@ -7296,7 +7455,8 @@ void device_destroy(Context* ctx) {
                   d->d_cpurows, d->d_aff, d->soa.qt, d->soa.qm, d->d_stale,
                   d->d_stale_cnt, d->d_pre, d->d_trows, d->d_tcnt, d->d_parts_done, d->d_scores2, d->d_split2, d->d_chg, d->soa.rec, d->soa.pt, d->soa.kerr,
                   d->soa.xf, d->soa.xm, d->d_xrows, d->soa.dsx, d->d_ph, d->d_vfo, d->d_rsv, d->d_rsv_out, d->d_rsv_st,
-                  d->d_rsv_views, d->d_ds_views, d->d_numa_views, d->d_rovr, d->d_rsv_gate, d->d_ns_tbl, d->d_nsc_tbl};
+                  d->d_rsv_views, d->d_ds_views, d->d_numa_views, d->d_rovr, d->d_rsv_gate, d->d_ns_tbl, d->d_nsc_tbl,
+                  d->d_diag};
   if (d->estream) (void)hipStreamSynchronize(d->estream);
   if (d->estream2) (void)hipStreamSynchronize(d->estream2);
   for (void* p : ptrs)
@@ -8029,6 +8189,20 @@ static auto pick_numa_fallback(bool parity, bool cpu) {
 static auto pick_numa_finish(bool parity, bool cpu) {
   return with_bool(parity, [&](auto P) { return cpu ? k_numa_finish<KV(P), true> : k_numa_finish<KV(P), false>; });
 }
+// ke_diagnose: NUMA x CPU x node sets (score table ids are not part of a diagnosis); its deferred pairs finish in
+// k_numa_finish_diag
+using DiagEvalFn = decltype(&k_diag_eval<false, false>);
+static DiagEvalFn pick_diag_eval(bool numa, bool cpu, int ns) {
+  if (ns == NS_SCORES) return nullptr;
+  return with_ns(ns, [&](auto NS) {
+    return with_bool(numa, [&](auto NUMA) {
+      return with_bool(cpu, [&](auto CPU) -> DiagEvalFn { return k_diag_eval<KV(NUMA), KV(CPU), KV(NS)>; });
+    });
+  });
+}
+static auto pick_diag_finish(bool cpu) {
+  return cpu ? k_numa_finish_diag<true> : k_numa_finish_diag<false>;
+}
 static auto pick_cpuset_reserve(bool ds, bool numa) {
   return with_bool(ds, [&](auto DS) { return numa ? k_cpuset_reserve<KV(DS), true> : k_cpuset_reserve<KV(DS), false>; });
 }
@@ -8122,6 +8296,97 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
   ctx->kstat_numa_deferred = deferred;
   if (best)
     for (int64_t p = 0; p < P; p++) best[p] = bk[p] ? key_node(bk[p]) + ctx->cfg.global_node_offset : -1;
+  return KE_OK;
+}
+
+// ke_diagnose: ke_eval's classification of every (pod, node) pair reduced on the device -- refresh,
+// node set sync and pod upload as device_eval, then one zeroed block (the tallies, and the bitmaps only when asked
+// for), k_diag_eval (+ the NUMA deferral's two kernels), one copy back per output and the fold (ke_diag.h).  None of
+// the parity buffers is allocated.  bits[c] (DIAG_BIT_*): the caller's bitmap of words_per_pod words a pod, or nullptr.
+int device_diagnose(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, ke_pod_diagnosis* out,
+                    int32_t words_per_pod, uint64_t* const* bits) {
+  DeviceState* d = ctx->dev;
+  HIP_OK(hipSetDevice(d->device));
+  int rc = device_refresh(ctx, now);
+  if (rc) return rc;
+  if (n_pods == 0) return KE_OK;
+  const int ns = ctx->ns_call ? NS_SETS : 0;  // (score table ids do not filter: ke_diagnose drops them)
+  if (ns) {
+    rc = node_sets_sync(ctx);
+    if (rc) return rc;
+  }
+  rc = upload_pods(ctx, n_pods, pods);
+  if (rc) return rc;
+  const int64_t N = ctx->n_nodes, P = n_pods;
+  int n_bits = 0;
+  for (int c = 0; c < DIAG_BITMAPS; c++) n_bits += bits[c] != nullptr;
+  const int64_t wpp = n_bits ? words_per_pod : 0;
+  static_assert(sizeof(uint32_t) * DIAG_WORDS % sizeof(uint64_t) == 0, "the bitmaps behind the tallies are 8-byte aligned");
+  const int64_t tally_bytes = (int64_t)sizeof(uint32_t) * DIAG_WORDS * P, bits_bytes = (int64_t)sizeof(uint64_t) * P * wpp;
+  rc = ensure(&d->d_diag, &d->diag_cap, tally_bytes + n_bits * bits_bytes);
+  if (rc) return rc;
+  DiagOut dg{};
+  dg.tally = (uint32_t*)d->d_diag;
+  dg.wpp = (int32_t)wpp;
+  uint64_t* d_bits[DIAG_BITMAPS] = {nullptr, nullptr, nullptr};
+  {
+    uint64_t* next = reinterpret_cast<uint64_t*>((uint8_t*)d->d_diag + tally_bytes);
+    for (int c = 0; c < DIAG_BITMAPS; c++)
+      if (bits[c]) d_bits[c] = next, next += P * wpp;
+  }
+  dg.feasible = d_bits[DIAG_BIT_FEASIBLE];
+  dg.unschedulable = d_bits[DIAG_BIT_UNSCHEDULABLE];
+  dg.unresolvable = d_bits[DIAG_BIT_UNRESOLVABLE];
+  HIP_OK(hipMemsetAsync(d->d_diag, 0, (size_t)(tally_bytes + n_bits * bits_bytes), d->stream));
+  HIP_OK(hipMemsetAsync(d->soa.kerr, 0, sizeof(int32_t), d->stream));
+  const KArgs k = make_kargs(ctx, now);
+  bool cpu = false;
+  for (const DevPod& q : d->call.host_pods) cpu = cpu || (q.flags & PF_CPUSET);
+  if (cpu && !d->cpu_alloc) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
+  const bool numa = d->numa_alloc;
+  if (N > 0) {
+    const auto eval = pick_diag_eval(numa, cpu, ns);
+    if (!eval) return no_variant("k_diag_eval");
+    const int xcd = d->diag_xcd;
+    const dim3 grid = xcd ? eval_grid((int)N, EVAL_BLOCK, (int)P, EVAL_PPB)
+                          : dim3((unsigned)((N + EVAL_BLOCK - 1) / EVAL_BLOCK), (unsigned)((P + EVAL_PPB - 1) / EVAL_PPB));
+    const int64_t M = N * P;  // every pair may be deferred
+    if (numa) {
+      rc = ensure((void**)&d->d_defer, &d->defer_cap, (sizeof(uint64_t) + sizeof(uint32_t)) * M);  // pairs, merges
+      if (rc) return rc;
+      rc = ensure((void**)&d->d_defer_cnt, &d->defer_cnt_cap, sizeof(uint32_t));
+      if (rc) return rc;
+      HIP_OK(hipMemsetAsync(d->d_defer_cnt, 0, sizeof(uint32_t), d->stream));
+    }
+    hipLaunchKernelGGL(eval, grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->call.d_pods, (int)P, k, dg,
+                       numa ? d->d_defer : nullptr, numa ? d->d_defer_cnt : nullptr, xcd);
+    HIP_OK(hipGetLastError());
+    if (numa) {
+      uint32_t* fb = reinterpret_cast<uint32_t*>(d->d_defer + M);
+      hipLaunchKernelGGL(pick_numa_fallback(true, cpu), dim3(FALLBACK_BLOCKS), dim3(64), 0, d->stream, d->soa,
+                         d->call.d_pods, d->d_batch_base, k, d->d_defer, d->d_defer_cnt, d->d_scores, d->capacity, (int)N,
+                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, fb);
+      HIP_OK(hipGetLastError());
+      hipLaunchKernelGGL(pick_diag_finish(cpu), dim3(FINISH_BLOCKS), dim3(64), 0, d->stream, d->soa, d->call.d_pods, k,
+                         d->d_defer, d->d_defer_cnt, fb, dg);
+      HIP_OK(hipGetLastError());
+    }
+  }
+  std::vector<uint32_t> raw((size_t)(DIAG_WORDS * P));
+  HIP_OK(hipMemcpyAsync(raw.data(), dg.tally, (size_t)tally_bytes, hipMemcpyDeviceToHost, d->stream));
+  for (int c = 0; c < DIAG_BITMAPS; c++)
+    if (bits[c]) HIP_OK(hipMemcpyAsync(bits[c], d_bits[c], (size_t)bits_bytes, hipMemcpyDeviceToHost, d->stream));
+  uint32_t deferred = 0;
+  if (numa && N > 0)
+    HIP_OK(hipMemcpyAsync(&deferred, d->d_defer_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+  int32_t kerr = 0;
+  HIP_OK(hipMemcpyAsync(&kerr, d->soa.kerr, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+  HIP_OK(hipStreamSynchronize(d->stream));
+  if (kerr & KERR_HINT_ROUTE) return fail(KE_ERR_DEVICE, "internal: a hinted pod reached a kernel without the hint path");
+  ctx->kstat_numa_deferred = deferred;
+  for (int64_t p = 0; p < P; p++)
+    if (!diag_fold(raw.data() + p * DIAG_WORDS, (int32_t)N, &out[p]))
+      return fail(KE_ERR_DEVICE, "internal: the diagnosis tallies of a pod do not add up");
   return KE_OK;
 }
 

@@ -48,6 +48,16 @@ def unpack_node_sets(words, n_nodes):
     return bits[:, :n_nodes].astype(bool)
 
 
+def reason_message(code, lib=None):
+    """ke_reason_message: the plugin's message of a KE_REASON_* code ("" for an unknown one)."""
+    return (lib or abi.load_library()).ke_reason_message(int(code)).decode()
+
+
+def reason_plugin(code, lib=None):
+    """ke_reason_plugin: the abi.PLUGIN_* bit of a KE_REASON_* code (0 for NONE / an unknown one)."""
+    return int((lib or abi.load_library()).ke_reason_plugin(int(code)))
+
+
 def as_pod_array(pods):
     """list[abi.Pod] | np.ndarray(POD_DTYPE) -> contiguous np.ndarray(POD_DTYPE)."""
     if isinstance(pods, np.ndarray):
@@ -369,6 +379,26 @@ class Evaluator:
         self._check(self.lib.ke_eval(self.h, P, abi.ptr(pods), int(now_ns), abi.ptr(out["status"]),
                                      abi.ptr(out["reason"]), abi.ptr(out["la"]), abi.ptr(out["numa"]),
                                      abi.ptr(out["ds"]), abi.ptr(out["total"]), abi.ptr(out["best"])))
+        return out
+
+    def diagnose(self, pods, now_ns, node_sets=None, bitmaps=False):
+        """ke_diagnose: per pod the reductions of eval()'s status / reason over every node, computed on the device
+        with nothing per pair copied back -- int32 [P] arrays n_nodes, n_absent, n_feasible, n_unschedulable,
+        n_unresolvable, n_error, uint32 [P] plugins (abi.PLUGIN_* bits), int32 [P, 128] reason_nodes; with
+        `bitmaps` also the bool [P, N] matrices feasible, unschedulable, unresolvable.  `node_sets` as for eval()."""
+        pods = as_pod_array(pods)
+        if node_sets is not None:
+            self.pod_node_sets(node_sets)
+        P, N = len(pods), self.num_nodes
+        rec = np.zeros(P, abi.POD_DIAGNOSIS_DTYPE)
+        wpp = (N + 63) // 64
+        names = ("feasible", "unschedulable", "unresolvable")
+        words = {k: np.zeros((P, wpp), np.uint64) for k in names} if bitmaps else {}
+        self._check(self.lib.ke_diagnose(self.h, P, abi.ptr(pods), int(now_ns), abi.ptr(rec), wpp,
+                                         *[abi.ptr(words.get(k)) for k in names]))
+        out = {k: np.ascontiguousarray(rec[k]) for k in rec.dtype.names if k != "reserved"}
+        for k, w in words.items():
+            out[k] = unpack_node_sets(w, N)
         return out
 
     def schedule(self, pods, now_ns, matches=None, node_sets=None, node_scores=None):
