@@ -671,7 +671,9 @@ int ke_device_available(void);
 /* Insert or replace node `node` (0 <= node < node_capacity).  Keeps its NodeMetric / assigned pods. */
 int ke_node_upsert(ke_ctx* ctx, int32_t node, const ke_node* n);
 /* Node informer delete (the scheduler cache's RemoveNode, k8s v1.28.7): the node leaves the snapshot, so no
- * pod is evaluated against it (ke_eval reports KE_CODE_ERROR for it, ke_schedule never chooses it).  The state of
+ * pod is evaluated against it (ke_eval reports KE_CODE_ERROR for it -- except in a call with node sets, where an
+ * empty slot outside the pod's set reports KE_REASON_NODE_SET as every node outside the set does; ke_diagnose counts
+ * it as absent either way -- and ke_schedule never chooses it).  The state of
  * the other informers stays until their own events remove it — as the scheduler's caches keep it: the NodeMetric
  * (ke_nodemetric_delete), the podAssignCache (ke_pod_unassign / ke_pod_release), NodeInfo.Requested of pods still
  * bound there, the NRT topology (ke_node_topology_delete), the device cache (ke_node_devices_delete), the

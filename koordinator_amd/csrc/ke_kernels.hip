@@ -3179,8 +3179,24 @@ __global__ void k_gather_rows(SoA s, Row* __restrict__ rows, int n) {
   rows[i] = r;
 }
 
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v);
-__device__ __forceinline__ int lanes_below(uint64_t m);
+// ---- wave-wide primitives (DPP reductions from the device library, ballots) ---------------------
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) { return __ockl_wfred_max_u32(v); }
+__device__ __forceinline__ int wave_sum(int v) { return __ockl_wfred_add_i32(v); }
+__device__ __forceinline__ int lanes_below(uint64_t m) {  // popcount of m over lanes < this lane
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+}
+// exclusive prefix over lanes of a small per-lane count c (0 <= c < 16) and the wave total
+__device__ __forceinline__ int lane_prefix16(int c, int* total) {
+  int pre = 0, tot = 0;
+#pragma unroll
+  for (int b = 0; b < 4; b++) {
+    const uint64_t m = __ballot((c >> b) & 1);
+    pre += lanes_below(m) << b;
+    tot += __popcll(m) << b;
+  }
+  *total = tot;
+  return pre;
+}
 
 // Append `item` to a deferred-pair list (one atomic per wavefront).
 __device__ __forceinline__ void defer_push(bool want, uint64_t item, uint64_t* __restrict__ list, uint32_t* cnt) {
@@ -3190,22 +3206,86 @@ __device__ __forceinline__ void defer_push(bool want, uint64_t item, uint64_t* _
   uint32_t base = 0;
   if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(cnt, (uint32_t)__popcll(bal));
   base = __shfl(base, leader, 64);
-  const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-  if (want) list[base + below] = item;
+  if (want) list[base + (uint32_t)lanes_below(bal)] = item;
 }
 
-// parity mode: full status / score matrices [pod][node]; `total` holds the LoadAware + NUMA part
-// until k_parity_finalize adds the normalized DeviceShare score.  dsmax[p] = 1 + max raw DeviceShare
-// score over the pod's feasible nodes (DefaultNormalizeScore's maxCount).
-// NS: pods with a node set (SoA::ns_ids): a pair outside the set is KE_REASON_NODE_SET ahead of every other
-// filter -- scores 0, total -1, never deferred, and not part of the pod's DeviceShare normalisation max.
-template <bool NUMA, bool CPU, int NS = 0>
-__global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, int n_nodes, const DevPod* __restrict__ pods,
-                                                            int n_pods, int pods_per_block, KArgs k,
-                                                            uint8_t* status, uint8_t* reason, int16_t* la,
-                                                            int16_t* numa, int16_t* ds, int16_t* total,
-                                                            uint32_t* dsmax, uint64_t* defer_list,
-                                                            uint32_t* defer_cnt) {
+// ---- where a finished (pod p, node i) pair goes: one sink per caller, passed by value as one kernel argument ------
+// ke_eval's parity matrices [pod][node]; `total` holds the LoadAware + NUMA part until k_parity_finalize adds the
+// normalized DeviceShare score.  dsmax[p] = 1 + max raw DeviceShare score over the pod's feasible nodes
+// (DefaultNormalizeScore's maxCount).
+struct ParityOut {
+  uint8_t* status;
+  uint8_t* reason;
+  int16_t* la;
+  int16_t* numa;
+  int16_t* ds;
+  int16_t* total;
+  uint32_t* dsmax;
+  int32_t n_nodes;
+  __device__ __forceinline__ void store(int p, int64_t i, const EvalOut& o) const {
+    const int64_t o_idx = (int64_t)p * n_nodes + i;
+    status[o_idx] = o.status;
+    reason[o_idx] = o.reason;
+    la[o_idx] = o.la;
+    numa[o_idx] = o.numa;
+    ds[o_idx] = o.ds;
+    total[o_idx] = (int16_t)o.total;
+  }
+  // (k_numa_finish: few pairs, one atomic each; k_eval_parity stores and reduces the maximum over its wave first)
+  __device__ __forceinline__ void put(int p, int64_t i, const DevPod&, const EvalOut& o) const {
+    store(p, i, o);
+    if (o.total >= 0) atomicMax(&dsmax[p], (uint32_t)o.ds + 1);
+  }
+};
+// a ke_schedule batch's score rows, for a binding batch the affinity (aff_out, else nullptr) and for a DeviceShare
+// singleton its raw score + 1 for the normalisation (dsraw / dsmax, else nullptr)
+struct BatchOut {
+  uint16_t* scores;
+  int64_t score_stride;
+  uint8_t* aff_out;
+  uint16_t* dsraw;
+  uint32_t* dsmax;
+  __device__ __forceinline__ void put(int p, int64_t i, const DevPod& pod, const EvalOut& o) const {
+    scores[(int64_t)p * score_stride + i] = (uint16_t)(o.total + 1);
+    if (aff_out) aff_out[i] = o.aff;
+    if (dsraw && (pod.flags & PF_DS)) {  // a DeviceShare singleton: its raw score (0 here) for the normalisation
+      dsraw[i] = o.total >= 0 ? (uint16_t)(o.ds + 1) : (uint16_t)0;
+      if (o.total >= 0) atomicMax(dsmax, (uint32_t)o.ds + 1);
+    }
+  }
+};
+
+// The classification ke_eval and ke_diagnose share, of (pod p, node i) in the first pass: the pod's node set ahead of
+// every other filter (NS: the call carries ids; a pair outside the set is KE_REASON_NODE_SET -- scores 0, total -1,
+// never deferred, and not part of the pod's DeviceShare normalisation max), then eval_pair; *deferred: the pair is
+// left to k_numa_fallback / k_numa_finish (o.status == STATUS_DEFERRED).
+template <bool NUMA, bool CPU, int NS>
+__device__ __forceinline__ EvalOut classify_pair(const SoA& s, const NodeRegs& n, bool expired, const DevPod* pods, int p,
+                                                 const KArgs& k, int i, const NumaNode& nv, bool* deferred) {
+  *deferred = false;
+  if (NS && !ns_ok<NS>(s, s.ns_ids[p], i)) {  // (one table word a wave: the lanes' addresses are equal)
+    EvalOut o;
+    o.status = KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE;
+    o.reason = KE_REASON_NODE_SET;
+    o.aff = 0;
+    o.la = o.numa = o.ds = 0;
+    o.total = -1;
+    return o;
+  }
+  const EvalOut o = eval_pair<true, NUMA, NUMA, false, CPU, true>(n, expired, pods[p], k, s, i, nv);
+  *deferred = NUMA && o.status == STATUS_DEFERRED;
+  return o;
+}
+
+// parity mode: the full status / score matrices of `out`, every pair classified by classify_pair (an empty slot by
+// eval_pair's own NF_VALID test, behind the node-set gate).
+// IDS: the call carries per-pod ids (SoA::ns_ids): the low half of a word is the pod's node set (the high half, a
+// score table id, is k_parity_finalize's).
+template <bool NUMA, bool CPU, bool IDS = false>
+__global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, const DevPod* __restrict__ pods, int n_pods,
+                                                            int pods_per_block, KArgs k, ParityOut out,
+                                                            uint64_t* defer_list, uint32_t* defer_cnt) {
+  const int n_nodes = out.n_nodes;
   const int i = blockIdx.x * EVAL_BLOCK + threadIdx.x;
   const bool live = i < n_nodes;
   NodeRegs n;
@@ -3221,75 +3301,59 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, int n_nodes, 
   for (int p = p0; p < p1; p++) {
     uint32_t m = 0;
     bool deferred = false;
-    if (NS && live && !ns_ok<NS>(s, s.ns_ids[p], i)) {  // (one table word a wave: the lanes' addresses are equal)
-      const int64_t o_idx = (int64_t)p * n_nodes + i;
-      status[o_idx] = KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE;
-      reason[o_idx] = KE_REASON_NODE_SET;
-      la[o_idx] = 0;
-      numa[o_idx] = 0;
-      ds[o_idx] = 0;
-      total[o_idx] = -1;
-    } else if (live) {
-      const EvalOut o = eval_pair<true, NUMA, NUMA, false, CPU, true>(n, expired, pods[p], k, s, i, nv);
-      deferred = NUMA && o.status == STATUS_DEFERRED;
-      const int64_t o_idx = (int64_t)p * n_nodes + i;
-      status[o_idx] = o.status;
-      reason[o_idx] = o.reason;
-      la[o_idx] = o.la;
-      numa[o_idx] = o.numa;
-      ds[o_idx] = o.ds;
-      total[o_idx] = (int16_t)o.total;
+    if (live) {
+      const EvalOut o = classify_pair<NUMA, CPU, IDS ? NS_SCORES : 0>(s, n, expired, pods, p, k, i, nv, &deferred);
+      out.store(p, i, o);
       m = o.total >= 0 ? (uint32_t)o.ds + 1 : 0u;
     }
     if (NUMA) defer_push(deferred, ((uint64_t)p << 32) | (uint32_t)i, defer_list, defer_cnt);
-    m = __ockl_wfred_max_u32(m);
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(&dsmax[p], m);
+    m = wave_max_u32(m);
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(&out.dsmax[p], m);
   }
 }
 
 // ---- ke_diagnose ------------------------------------------------------------------------------------
 // Where a diagnosis launch leaves its reductions: the raw tallies (ke_diag.h: DIAG_WORDS u32 per pod) and the
 // optional class bitmaps (`wpp` words per pod each, nullptr = not asked for), all zeroed by the host beforehand.
-struct DiagOut {
-  uint32_t* tally;
-  uint64_t* feasible;
-  uint64_t* unschedulable;
-  uint64_t* unresolvable;
-  int32_t wpp;
-};
-// class bitmap of a KE_CODE_* (nullptr: none, or not asked for) -- selects, not an indexed kernel argument
-__device__ __forceinline__ uint64_t* diag_bits(const DiagOut& dg, uint32_t status) {
-  return status == KE_CODE_SUCCESS                              ? dg.feasible
-         : status == KE_CODE_UNSCHEDULABLE                      ? dg.unschedulable
-         : status == KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE     ? dg.unresolvable
-                                                                : nullptr;
-}
 __device__ __forceinline__ int diag_class(uint32_t status) {
   return status == KE_CODE_SUCCESS                          ? DIAG_FEASIBLE
          : status == KE_CODE_UNSCHEDULABLE                  ? DIAG_UNSCHEDULABLE
          : status == KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE ? DIAG_UNRESOLVABLE
                                                             : DIAG_ERROR;
 }
-// One finished pair (k_numa_finish's diagnosis mode: few pairs, global atomics) into the pod's tallies and bitmap word.
-__device__ __forceinline__ void diag_add_pair(const DiagOut& dg, int p, int64_t i, uint32_t status, uint32_t reason) {
-  uint32_t* const row = dg.tally + (int64_t)p * DIAG_WORDS;
-  const int c = diag_class(status);
-  atomicAdd(&row[c], 1u);
-  atomicAdd(&row[c == DIAG_UNSCHEDULABLE || c == DIAG_UNRESOLVABLE ? (int)(reason & (KE_DIAG_REASONS - 1)) : 0], 1u);
-  uint64_t* const bits = diag_bits(dg, status);
-  if (bits)
-    atomicOr(reinterpret_cast<unsigned long long*>(bits + (int64_t)p * dg.wpp + (i >> 6)), 1ull << (i & 63));
-}
+struct DiagOut {
+  uint32_t* tally;
+  uint64_t* feasible;
+  uint64_t* unschedulable;
+  uint64_t* unresolvable;
+  int32_t wpp;
+  // class bitmap of a KE_CODE_* (nullptr: none, or not asked for) -- selects, not an indexed kernel argument
+  __device__ __forceinline__ uint64_t* bits_of(uint32_t status) const {
+    return status == KE_CODE_SUCCESS                          ? feasible
+           : status == KE_CODE_UNSCHEDULABLE                  ? unschedulable
+           : status == KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE ? unresolvable
+                                                              : nullptr;
+  }
+  // One finished pair (k_numa_finish: few pairs, global atomics) into the pod's tallies and bitmap word.
+  __device__ __forceinline__ void put(int p, int64_t i, const DevPod&, const EvalOut& o) const {
+    uint32_t* const row = tally + (int64_t)p * DIAG_WORDS;
+    const int c = diag_class(o.status);
+    atomicAdd(&row[c], 1u);
+    atomicAdd(&row[c == DIAG_UNSCHEDULABLE || c == DIAG_UNRESOLVABLE ? (int)(o.reason & (KE_DIAG_REASONS - 1)) : 0], 1u);
+    uint64_t* const bits = bits_of(o.status);
+    if (bits) atomicOr(reinterpret_cast<unsigned long long*>(bits + (int64_t)p * wpp + (i >> 6)), 1ull << (i & 63));
+  }
+};
 
 // ke_diagnose's fused Filter + reduction: k_eval_parity's geometry and classification (lane = node, the row loaded
-// once into registers, the block's pods looped wave-uniformly, the same eval_pair call behind the same node-set
-// gate), with nothing written per pair.  A wave's 64 lanes are nodes [64w, 64w + 64), so the ballot of a class is the
-// pod's bitmap word w: lane 0 stores it (plain 8-byte stores, no atomics; skipped for a bitmap not asked for).  The
+// once into registers, the block's pods looped wave-uniformly, classify_pair for every populated slot), with
+// nothing written per pair.  NS: 0 or NS_SETS (score table ids are not part of a diagnosis).
+// A wave's 64 lanes are nodes [64w, 64w + 64), so the ballot of a class is the pod's bitmap word w: lane 0 stores it (plain 8-byte stores, no atomics; skipped for a bitmap not asked for).  The
 // counts go through a per-workgroup LDS table [pod of the group][DIAG_WORDS]: per pod a wave adds its class
 // popcounts and peels the distinct reasons of its failing lanes (the first one's reason -> ballot of the lanes that
 // share it -> popcount; one to three rounds in practice), one LDS atomic each from lane 0; after the pod loop the
 // workgroup adds its non-zero bins to the global table.  Lanes past the last node, empty slots (DIAG_ABSENT alone)
-// and NUMA-deferred pairs (k_numa_finish_diag adds those) contribute to no ballot.
+// and NUMA-deferred pairs (k_numa_finish adds those through DiagOut::put) contribute to no ballot.
 template <bool NUMA, bool CPU, int NS = 0>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_diag_eval(SoA s, int n_nodes, const DevPod* __restrict__ pods,
                                                           int n_pods, KArgs k, DiagOut dg, uint64_t* defer_list,
@@ -3324,16 +3388,10 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_diag_eval(SoA s, int n_nodes, co
   for (int p = p0; p < p1; p++) {
     uint32_t status = KE_CODE_ERROR, reason = KE_REASON_NONE;
     bool deferred = false;
-    if (valid) {
-      if (NS && !ns_ok<NS>(s, s.ns_ids[p], i)) {
-        status = KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE;
-        reason = KE_REASON_NODE_SET;
-      } else {
-        const EvalOut o = eval_pair<true, NUMA, NUMA, false, CPU, true>(n, expired, pods[p], k, s, i, nv);
-        deferred = NUMA && o.status == STATUS_DEFERRED;
-        status = o.status;
-        reason = o.reason;
-      }
+    if (valid) {  // (an empty slot is DIAG_ABSENT whatever the pod's set says)
+      const EvalOut o = classify_pair<NUMA, CPU, NS>(s, n, expired, pods, p, k, i, nv, &deferred);
+      status = o.status;
+      reason = o.reason;
     }
     if (NUMA) defer_push(deferred, ((uint64_t)p << 32) | (uint32_t)i, defer_list, defer_cnt);
     const bool counted = valid && !deferred;
@@ -3798,10 +3856,10 @@ __global__ __launch_bounds__(64) void k_rsv_stage(const uint16_t* __restrict__ s
 }
 
 // The deferred BestEffort pairs of an eval launch: one wavefront per pair computes mergeFilteredHints
-// over the full provider lists (numa_best_effort_fallback's result), then lane 0 evaluates the pair
-// with it.  A DeviceShare pod's pair is deferred only on a node without a device cache (DeviceShare has
-// no hints there, Filter passes, Score is 0).  PARITY: write the parity matrices; else the batch score
-// (and for a DeviceShare singleton its raw score + 1 into `dsraw`, the max into `dsmax`).
+// over the full provider lists (numa_best_effort_fallback's result) into fb_out[w]; k_numa_finish evaluates
+// the pair with it.  A DeviceShare pod's pair is deferred only on a node without a device cache (DeviceShare
+// has no hints there, Filter passes, Score is 0).  The pods of the launch start at *batch_base (a zero word
+// for ke_eval and ke_diagnose).
 //   1. lanes split the 255 masks: hint lists L_cpu / L_mem (IterateBitMasks order) and hint scores;
 //   2. c* = the smallest popcount of a non-empty merged mask m1 & m2: only merged hints of that size
 //      can end as the best (the first one is narrower than anything before it, larger ones never
@@ -3812,14 +3870,10 @@ constexpr int FALLBACK_BLOCKS = 4096;
 constexpr int FB_ROWS = 16;  // rows of L_cpu per fold chunk (LDS: several pair-waves per CU)
 // CS: pods of the launch may bind CPUs — such a pair's lists come from the trimmed zones with the
 // cpuset-aware split, its hint scores from the amplified requests (eval_pair's binding branch).
-template <bool PARITY, bool CS = false>
+template <bool CS = false>
 __global__ __launch_bounds__(64) void k_numa_fallback(SoA s, const DevPod* __restrict__ pods,
                                                       const int32_t* __restrict__ batch_base, KArgs k,
                                                       const uint64_t* __restrict__ list, const uint32_t* __restrict__ cnt,
-                                                      uint16_t* __restrict__ scores, int64_t score_stride, int n_nodes,
-                                                      uint8_t* status, uint8_t* reason, int16_t* la, int16_t* numa,
-                                                      int16_t* ds, int16_t* total, uint32_t* dsmax,
-                                                      uint8_t* __restrict__ aff_out, uint16_t* __restrict__ dsraw,
                                                       uint32_t* __restrict__ fb_out) {
   __shared__ int32_t s_score[256];     // hint score by mask value
   __shared__ uint8_t s_list[2][256];   // L_cpu / L_mem masks in order
@@ -3828,7 +3882,7 @@ __global__ __launch_bounds__(64) void k_numa_fallback(SoA s, const DevPod* __res
   __shared__ uint64_t s_E[2][4];       // list membership by NUMA_ORDER index (LDS: read at runtime indices)
   const int lane = threadIdx.x;
   const uint32_t n = *cnt;
-  const int base = PARITY ? 0 : *batch_base;
+  const int base = *batch_base;
   for (uint32_t w = blockIdx.x; w < n; w += FALLBACK_BLOCKS) {
     const uint64_t it = list[w];
     const int p = (int)(it >> 32);
@@ -4016,20 +4070,16 @@ __global__ __launch_bounds__(64) void k_numa_fallback(SoA s, const DevPod* __res
 }
 
 // The deferred pairs evaluated with their merges (k_numa_fallback's fb_in), one lane per pair: the
-// Filter / Score of eval_pair with the Admit's outcome given.  PARITY: the parity matrices; else the
-// batch score (and for a binding batch the affinity, for a DeviceShare singleton its raw score).
+// Filter / Score of eval_pair with the Admit's outcome given.  Out, the sink the finished pair goes to: ParityOut
+// (ke_eval's matrices), BatchOut (a ke_schedule batch's scores) or DiagOut (ke_diagnose's tallies and bitmaps).
 constexpr int FINISH_BLOCKS = 256;
-template <bool PARITY, bool CS = false>
+template <class Out, bool CS = false>
 __global__ __launch_bounds__(64) void k_numa_finish(SoA s, const DevPod* __restrict__ pods,
                                                     const int32_t* __restrict__ batch_base, KArgs k,
                                                     const uint64_t* __restrict__ list, const uint32_t* __restrict__ cnt,
-                                                    uint16_t* __restrict__ scores, int64_t score_stride, int n_nodes,
-                                                    uint8_t* status, uint8_t* reason, int16_t* la, int16_t* numa,
-                                                    int16_t* ds, int16_t* total, uint32_t* dsmax,
-                                                    uint8_t* __restrict__ aff_out, uint16_t* __restrict__ dsraw,
-                                                    const uint32_t* __restrict__ fb_in) {
+                                                    const uint32_t* __restrict__ fb_in, Out out) {
   const uint32_t n = *cnt;
-  const int base = PARITY ? 0 : *batch_base;
+  const int base = *batch_base;
   for (uint32_t w = blockIdx.x * 64 + threadIdx.x; w < n; w += FINISH_BLOCKS * 64) {
     const uint64_t it = list[w];
     const int p = (int)(it >> 32);
@@ -4042,67 +4092,8 @@ __global__ __launch_bounds__(64) void k_numa_finish(SoA s, const DevPod* __restr
     prepare_row(nr);
     const bool expired = node_expired(nr, k);
     const EvalOut o = eval_pair<false, true, false, true, CS>(nr, expired, pod, k, s, i, nv, fb_in[w]);
-    if (PARITY) {
-      const int64_t o_idx = (int64_t)p * n_nodes + i;
-      status[o_idx] = o.status;
-      reason[o_idx] = o.reason;
-      la[o_idx] = o.la;
-      numa[o_idx] = o.numa;
-      ds[o_idx] = o.ds;
-      total[o_idx] = (int16_t)o.total;
-      if (o.total >= 0) atomicMax(&dsmax[p], (uint32_t)o.ds + 1);
-    } else {
-      scores[(int64_t)p * score_stride + i] = (uint16_t)(o.total + 1);
-      if (CS && aff_out) aff_out[i] = o.aff;
-      if (dsraw && (pod.flags & PF_DS)) {  // a DeviceShare singleton: its raw score (0 here) for the normalisation
-        dsraw[i] = o.total >= 0 ? (uint16_t)(o.ds + 1) : (uint16_t)0;
-        if (o.total >= 0) atomicMax(dsmax, (uint32_t)o.ds + 1);
-      }
-    }
+    out.put(p, i, pod, o);
   }
-}
-// k_numa_finish's third output mode as a kernel of its own, so that the two above stay what they are: ke_diagnose's
-// launch (its pods start at 0) evaluates the pair the same way, adds it to the pod's tallies and ORs its bit into the
-// pod's class bitmap word (`dg`); nothing else is written.
-template <bool CS>
-__global__ __launch_bounds__(64) void k_numa_finish_diag(SoA s, const DevPod* __restrict__ pods, KArgs k,
-                                                         const uint64_t* __restrict__ list,
-                                                         const uint32_t* __restrict__ cnt,
-                                                         const uint32_t* __restrict__ fb_in, DiagOut dg) {
-  const uint32_t n = *cnt;
-  for (uint32_t w = blockIdx.x * 64 + threadIdx.x; w < n; w += FINISH_BLOCKS * 64) {
-    const uint64_t it = list[w];
-    const int p = (int)(it >> 32);
-    const int64_t i = (int64_t)(uint32_t)it;
-    const DevPod pod = pods[p];
-    NumaNode nv;
-    numa_load(s, i, nv);
-    NodeRegs nr;
-    load_row(s, i, nr);
-    prepare_row(nr);
-    const bool expired = node_expired(nr, k);
-    const EvalOut o = eval_pair<false, true, false, true, CS>(nr, expired, pod, k, s, i, nv, fb_in[w]);
-    diag_add_pair(dg, p, i, o.status, o.reason);
-  }
-}
-
-// ---- wave-wide primitives (DPP reductions from the device library, ballots) ---------------------
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) { return __ockl_wfred_max_u32(v); }
-__device__ __forceinline__ int wave_sum(int v) { return __ockl_wfred_add_i32(v); }
-__device__ __forceinline__ int lanes_below(uint64_t m) {  // popcount of m over lanes < this lane
-  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-}
-// exclusive prefix over lanes of a small per-lane count c (0 <= c < 16) and the wave total
-__device__ __forceinline__ int lane_prefix16(int c, int* total) {
-  int pre = 0, tot = 0;
-#pragma unroll
-  for (int b = 0; b < 4; b++) {
-    const uint64_t m = __ballot((c >> b) & 1);
-    pre += lanes_below(m) << b;
-    tot += __popcll(m) << b;
-  }
-  *total = tot;
-  return pre;
 }
 
 // 8 consecutive u16 values starting at node i (i % 8 == 0), 0 beyond `end`
@@ -8116,11 +8107,12 @@ static auto with_ns(int ns, F&& f) {
   return with_ns_ext(ns, false, [&](auto NS, auto) { return f(NS); });
 }
 
+// NUMA x CPU x "the call carries ids" (node sets or score tables: the kernel reads a word's set half either way)
 using EvalParityFn = decltype(&k_eval_parity<false, false>);
 static EvalParityFn pick_eval_parity(bool numa, bool cpu, int ns) {
-  return with_ns(ns, [&](auto NS) {
+  return with_bool(ns != 0, [&](auto IDS) {
     return with_bool(numa, [&](auto NUMA) {
-      return with_bool(cpu, [&](auto CPU) -> EvalParityFn { return k_eval_parity<KV(NUMA), KV(CPU), KV(NS)>; });
+      return with_bool(cpu, [&](auto CPU) -> EvalParityFn { return k_eval_parity<KV(NUMA), KV(CPU), KV(IDS)>; });
     });
   });
 }
@@ -8183,25 +8175,21 @@ static auto pick_select(bool ds, bool resident) {
 static auto pick_argmax1(bool ds) {
   return with_bool(ds, [](auto DS) { return k_argmax1<KV(DS)>; });
 }
-static auto pick_numa_fallback(bool parity, bool cpu) {
-  return with_bool(parity, [&](auto P) { return cpu ? k_numa_fallback<KV(P), true> : k_numa_fallback<KV(P), false>; });
+// the NUMA deferral: CS, and for the finish the caller's sink (ParityOut, BatchOut or DiagOut)
+static auto pick_numa_fallback(bool cpu) { return cpu ? k_numa_fallback<true> : k_numa_fallback<false>; }
+template <class Out>
+static auto pick_numa_finish(bool cpu) {
+  return cpu ? k_numa_finish<Out, true> : k_numa_finish<Out, false>;
 }
-static auto pick_numa_finish(bool parity, bool cpu) {
-  return with_bool(parity, [&](auto P) { return cpu ? k_numa_finish<KV(P), true> : k_numa_finish<KV(P), false>; });
-}
-// ke_diagnose: NUMA x CPU x node sets (score table ids are not part of a diagnosis); its deferred pairs finish in
-// k_numa_finish_diag
+// ke_diagnose: NUMA x CPU x node sets (score table ids are not part of a diagnosis)
 using DiagEvalFn = decltype(&k_diag_eval<false, false>);
 static DiagEvalFn pick_diag_eval(bool numa, bool cpu, int ns) {
   if (ns == NS_SCORES) return nullptr;
-  return with_ns(ns, [&](auto NS) {
+  return with_bool(ns != 0, [&](auto SETS) {
     return with_bool(numa, [&](auto NUMA) {
-      return with_bool(cpu, [&](auto CPU) -> DiagEvalFn { return k_diag_eval<KV(NUMA), KV(CPU), KV(NS)>; });
+      return with_bool(cpu, [&](auto CPU) -> DiagEvalFn { return k_diag_eval<KV(NUMA), KV(CPU), KV(SETS) ? NS_SETS : 0>; });
     });
   });
-}
-static auto pick_diag_finish(bool cpu) {
-  return cpu ? k_numa_finish_diag<true> : k_numa_finish_diag<false>;
 }
 static auto pick_cpuset_reserve(bool ds, bool numa) {
   return with_bool(ds, [&](auto DS) { return numa ? k_cpuset_reserve<KV(DS), true> : k_cpuset_reserve<KV(DS), false>; });
@@ -8209,114 +8197,139 @@ static auto pick_cpuset_reserve(bool ds, bool numa) {
 #undef KV
 static int no_variant(const char* what) { return fail(KE_ERR_DEVICE, std::string("internal: no kernel variant for ") + what); }
 
-int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, uint8_t* status, uint8_t* reason,
-                int16_t* la, int16_t* numa, int16_t* ds, int16_t* total, int32_t* best) {
+// ---- the NUMA deferral (k_numa_fallback, k_numa_finish) on the host ------------------------------------------------------
+// Its buffers: the deferred-pair list, one merge word per pair behind it (both in DeviceState::d_defer) and the
+// pair counters (d_defer_cnt: one per batch of a ke_schedule, one for a ke_eval / ke_diagnose launch).
+struct DeferBufs {
+  uint64_t* list = nullptr;
+  uint32_t* fb = nullptr;
+  uint32_t* cnt = nullptr;
+};
+// room for at most `max_pairs` deferred pairs at a time and `n_counters` counters (the caller zeroes the counters)
+static int defer_ensure(DeviceState* d, int64_t max_pairs, int64_t n_counters, DeferBufs* out) {
+  int rc = ensure((void**)&d->d_defer, &d->defer_cap, (sizeof(uint64_t) + sizeof(uint32_t)) * max_pairs);
+  if (rc) return rc;
+  rc = ensure((void**)&d->d_defer_cnt, &d->defer_cnt_cap, sizeof(uint32_t) * n_counters);
+  if (rc) return rc;
+  *out = DeferBufs{d->d_defer, reinterpret_cast<uint32_t*>(d->d_defer + max_pairs), d->d_defer_cnt};
+  return KE_OK;
+}
+// The pairs an eval kernel left in df.list (*df.cnt of them; pods from *base): their merges, then each pair evaluated
+// with its merge into `out`.
+template <class Out>
+static int launch_numa_deferral(hipStream_t st, const SoA& soa, const DevPod* pods, const int32_t* base, const KArgs& k,
+                                const DeferBufs& df, bool cpu, const Out& out) {
+  hipLaunchKernelGGL(pick_numa_fallback(cpu), dim3(FALLBACK_BLOCKS), dim3(64), 0, st, soa, pods, base, k, df.list, df.cnt, df.fb);
+  HIP_OK(hipGetLastError());
+  hipLaunchKernelGGL(pick_numa_finish<Out>(cpu), dim3(FINISH_BLOCKS), dim3(64), 0, st, soa, pods, base, k, df.list, df.cnt,
+                     df.fb, out);
+  HIP_OK(hipGetLastError());
+  return KE_OK;
+}
+
+// ---- what ke_eval and ke_diagnose share around their kernels: one pass over every (pod, node) pair ------------------
+struct PairPass {
+  KArgs k;
+  bool cpu = false;   // a pod of the call binds CPUs
+  bool numa = false;  // the context has NUMA state: pairs may be deferred (defer is set when there are nodes)
+  DeferBufs defer;
+};
+// refresh, the call's node sets (ns) and score tables (ns == NS_SCORES), the pods, the error word, and the deferral's
+// buffers with a zeroed counter; nothing after the refresh for a call without pods
+static int pair_pass_begin(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, int ns, PairPass* pp) {
   DeviceState* d = ctx->dev;
   HIP_OK(hipSetDevice(d->device));
   int rc = device_refresh(ctx, now);
-  if (rc) return rc;
-  if (n_pods == 0) return KE_OK;
+  if (rc || n_pods == 0) return rc;
+  if (ns && (rc = node_sets_sync(ctx))) return rc;
+  if (ns == NS_SCORES && (rc = node_scores_sync(ctx))) return rc;
+  if ((rc = upload_pods(ctx, n_pods, pods))) return rc;
+  HIP_OK(hipMemsetAsync(d->soa.kerr, 0, sizeof(int32_t), d->stream));
+  pp->k = make_kargs(ctx, now);
+  for (const DevPod& q : d->call.host_pods) pp->cpu = pp->cpu || (q.flags & PF_CPUSET);
+  if (pp->cpu && !d->cpu_alloc) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
+  pp->numa = d->numa_alloc;
+  if (pp->numa && ctx->n_nodes > 0) {  // every pair may be deferred
+    if ((rc = defer_ensure(d, (int64_t)ctx->n_nodes * n_pods, 1, &pp->defer))) return rc;
+    HIP_OK(hipMemsetAsync(pp->defer.cnt, 0, sizeof(uint32_t), d->stream));
+  }
+  return KE_OK;
+}
+// behind the caller's own read-backs: the deferred-pair count and the error word, then the wait
+static int pair_pass_end(Context* ctx, const PairPass& pp) {
+  DeviceState* d = ctx->dev;
+  uint32_t deferred = 0;
+  if (pp.defer.cnt) HIP_OK(hipMemcpyAsync(&deferred, pp.defer.cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+  int32_t kerr = 0;
+  HIP_OK(hipMemcpyAsync(&kerr, d->soa.kerr, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+  HIP_OK(hipStreamSynchronize(d->stream));
+  if (kerr & KERR_HINT_ROUTE) return fail(KE_ERR_DEVICE, "internal: a hinted pod reached a kernel without the hint path");
+  ctx->kstat_numa_deferred = deferred;
+  return KE_OK;
+}
+
+int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, uint8_t* status, uint8_t* reason,
+                int16_t* la, int16_t* numa, int16_t* ds, int16_t* total, int32_t* best) {
+  DeviceState* d = ctx->dev;
   // pods with node sets (NS_SETS) or score tables (NS_SCORES, which reads the set table too: id 0 = its row 0)
   const int ns = ctx->nsc_call ? NS_SCORES : ctx->ns_call ? NS_SETS : 0;
-  if (ns) {
-    rc = node_sets_sync(ctx);
-    if (rc) return rc;
-  }
-  if (ns == NS_SCORES) {
-    rc = node_scores_sync(ctx);
-    if (rc) return rc;
-  }
-  rc = upload_pods(ctx, n_pods, pods);
-  if (rc) return rc;
+  PairPass pp;
+  int rc = pair_pass_begin(ctx, n_pods, pods, now, ns, &pp);
+  if (rc || n_pods == 0) return rc;
   const int64_t N = ctx->n_nodes, P = n_pods, M = N * P;
   // parity buffers: status u8, reason u8, la / numa / ds / total i16 = 10 B per pair
   rc = ensure(&d->d_parity, &d->parity_cap, std::max<int64_t>(M, 1) * 10 + 16);
   if (rc) return rc;
   rc = ensure((void**)&d->d_best, &d->best_cap, sizeof(uint32_t) * 2 * P);  // best key + dsmax per pod
   if (rc) return rc;
-  uint8_t* d_status = (uint8_t*)d->d_parity;
-  uint8_t* d_reason = d_status + M;
-  int16_t* d_la = (int16_t*)(d_reason + M + (M & 1));
-  int16_t* d_numa = d_la + M;
-  int16_t* d_ds = d_numa + M;
-  int16_t* d_total = d_ds + M;
-  uint32_t* d_dsmax = d->d_best + P;
+  ParityOut po{};
+  po.status = (uint8_t*)d->d_parity;
+  po.reason = po.status + M;
+  po.la = (int16_t*)(po.reason + M + (M & 1));
+  po.numa = po.la + M;
+  po.ds = po.numa + M;
+  po.total = po.ds + M;
+  po.dsmax = d->d_best + P;
+  po.n_nodes = (int32_t)N;
   HIP_OK(hipMemsetAsync(d->d_best, 0, sizeof(uint32_t) * 2 * P, d->stream));
-  HIP_OK(hipMemsetAsync(d->soa.kerr, 0, sizeof(int32_t), d->stream));
-  const KArgs k = make_kargs(ctx, now);
-  const int ppb = EVAL_PPB;
-  bool cpu = false;
-  for (const DevPod& q : d->call.host_pods) cpu = cpu || (q.flags & PF_CPUSET);
-  if (cpu && !d->cpu_alloc) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
   if (N > 0) {
-    dim3 grid((unsigned)((N + EVAL_BLOCK - 1) / EVAL_BLOCK), (unsigned)((P + ppb - 1) / ppb));
-    if (d->numa_alloc) {
-      rc = ensure((void**)&d->d_defer, &d->defer_cap, (sizeof(uint64_t) + sizeof(uint32_t)) * M);  // pairs, merges
-      if (rc) return rc;
-      rc = ensure((void**)&d->d_defer_cnt, &d->defer_cnt_cap, sizeof(uint32_t));
-      if (rc) return rc;
-      HIP_OK(hipMemsetAsync(d->d_defer_cnt, 0, sizeof(uint32_t), d->stream));
-      hipLaunchKernelGGL(pick_eval_parity(true, cpu, ns), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->call.d_pods, (int)P,
-                         ppb, k, d_status, d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, d->d_defer, d->d_defer_cnt);
-      HIP_OK(hipGetLastError());
-      uint32_t* fb = reinterpret_cast<uint32_t*>(d->d_defer + M);
-      hipLaunchKernelGGL(pick_numa_fallback(true, cpu), dim3(FALLBACK_BLOCKS),
-                         dim3(64), 0, d->stream, d->soa, d->call.d_pods,
-                         d->d_batch_base, k, d->d_defer, d->d_defer_cnt, d->d_scores, d->capacity, (int)N, d_status,
-                         d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, nullptr, nullptr, fb);
-      hipLaunchKernelGGL(pick_numa_finish(true, cpu), dim3(FINISH_BLOCKS),
-                         dim3(64), 0, d->stream, d->soa, d->call.d_pods,
-                         d->d_batch_base, k, d->d_defer, d->d_defer_cnt, d->d_scores, d->capacity, (int)N, d_status,
-                         d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, nullptr, nullptr, fb);
-    } else {
-      hipLaunchKernelGGL(pick_eval_parity(false, cpu, ns), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->call.d_pods, (int)P,
-                         ppb, k, d_status, d_reason, d_la, d_numa, d_ds, d_total, d_dsmax, nullptr, nullptr);
-    }
+    const dim3 grid((unsigned)((N + EVAL_BLOCK - 1) / EVAL_BLOCK), (unsigned)((P + EVAL_PPB - 1) / EVAL_PPB));
+    hipLaunchKernelGGL(pick_eval_parity(pp.numa, pp.cpu, ns), grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, d->call.d_pods,
+                       (int)P, EVAL_PPB, pp.k, po, pp.defer.list, pp.defer.cnt);
     HIP_OK(hipGetLastError());
+    if (pp.numa &&
+        (rc = launch_numa_deferral(d->stream, d->soa, d->call.d_pods, d->d_batch_base, pp.k, pp.defer, pp.cpu, po)))
+      return rc;
     dim3 grid2((unsigned)((N + EVAL_BLOCK - 1) / EVAL_BLOCK), (unsigned)P);
     hipLaunchKernelGGL(pick_parity_finalize(ns), grid2, dim3(EVAL_BLOCK), 0,
-                       d->stream, (int)N, k, d_ds, d_total, d_dsmax, d->d_best, d->soa);
+                       d->stream, (int)N, pp.k, po.ds, po.total, po.dsmax, d->d_best, d->soa);
     HIP_OK(hipGetLastError());
   }
-  if (status) HIP_OK(hipMemcpyAsync(status, d_status, M, hipMemcpyDeviceToHost, d->stream));
-  if (reason) HIP_OK(hipMemcpyAsync(reason, d_reason, M, hipMemcpyDeviceToHost, d->stream));
-  if (la) HIP_OK(hipMemcpyAsync(la, d_la, M * 2, hipMemcpyDeviceToHost, d->stream));
-  if (numa) HIP_OK(hipMemcpyAsync(numa, d_numa, M * 2, hipMemcpyDeviceToHost, d->stream));
-  if (ds) HIP_OK(hipMemcpyAsync(ds, d_ds, M * 2, hipMemcpyDeviceToHost, d->stream));
-  if (total) HIP_OK(hipMemcpyAsync(total, d_total, M * 2, hipMemcpyDeviceToHost, d->stream));
+  if (status) HIP_OK(hipMemcpyAsync(status, po.status, M, hipMemcpyDeviceToHost, d->stream));
+  if (reason) HIP_OK(hipMemcpyAsync(reason, po.reason, M, hipMemcpyDeviceToHost, d->stream));
+  if (la) HIP_OK(hipMemcpyAsync(la, po.la, M * 2, hipMemcpyDeviceToHost, d->stream));
+  if (numa) HIP_OK(hipMemcpyAsync(numa, po.numa, M * 2, hipMemcpyDeviceToHost, d->stream));
+  if (ds) HIP_OK(hipMemcpyAsync(ds, po.ds, M * 2, hipMemcpyDeviceToHost, d->stream));
+  if (total) HIP_OK(hipMemcpyAsync(total, po.total, M * 2, hipMemcpyDeviceToHost, d->stream));
   std::vector<uint32_t> bk((size_t)P);
   HIP_OK(hipMemcpyAsync(bk.data(), d->d_best, sizeof(uint32_t) * P, hipMemcpyDeviceToHost, d->stream));
-  uint32_t deferred = 0;
-  if (d->numa_alloc && N > 0)
-    HIP_OK(hipMemcpyAsync(&deferred, d->d_defer_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
-  int32_t kerr = 0;
-  HIP_OK(hipMemcpyAsync(&kerr, d->soa.kerr, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
-  HIP_OK(hipStreamSynchronize(d->stream));
-  if (kerr & KERR_HINT_ROUTE) return fail(KE_ERR_DEVICE, "internal: a hinted pod reached a kernel without the hint path");
-  ctx->kstat_numa_deferred = deferred;
+  if ((rc = pair_pass_end(ctx, pp))) return rc;
   if (best)
     for (int64_t p = 0; p < P; p++) best[p] = bk[p] ? key_node(bk[p]) + ctx->cfg.global_node_offset : -1;
   return KE_OK;
 }
 
-// ke_diagnose: ke_eval's classification of every (pod, node) pair reduced on the device -- refresh,
-// node set sync and pod upload as device_eval, then one zeroed block (the tallies, and the bitmaps only when asked
-// for), k_diag_eval (+ the NUMA deferral's two kernels), one copy back per output and the fold (ke_diag.h).  None of
-// the parity buffers is allocated.  bits[c] (DIAG_BIT_*): the caller's bitmap of words_per_pod words a pod, or nullptr.
+// ke_diagnose: ke_eval's classification of every (pod, node) pair reduced on the device -- the pass
+// begun as device_eval's, then one zeroed block (the tallies, and the bitmaps only when asked for), k_diag_eval (+ the
+// NUMA deferral into the same DiagOut), one copy back per output and the fold (ke_diag.h).  None of the parity
+// buffers is allocated.  bits[c] (DIAG_BIT_*): the caller's bitmap of words_per_pod words a pod, or nullptr.
 int device_diagnose(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, ke_pod_diagnosis* out,
                     int32_t words_per_pod, uint64_t* const* bits) {
   DeviceState* d = ctx->dev;
-  HIP_OK(hipSetDevice(d->device));
-  int rc = device_refresh(ctx, now);
-  if (rc) return rc;
-  if (n_pods == 0) return KE_OK;
   const int ns = ctx->ns_call ? NS_SETS : 0;  // (score table ids do not filter: ke_diagnose drops them)
-  if (ns) {
-    rc = node_sets_sync(ctx);
-    if (rc) return rc;
-  }
-  rc = upload_pods(ctx, n_pods, pods);
-  if (rc) return rc;
+  PairPass pp;
+  int rc = pair_pass_begin(ctx, n_pods, pods, now, ns, &pp);
+  if (rc || n_pods == 0) return rc;
   const int64_t N = ctx->n_nodes, P = n_pods;
   int n_bits = 0;
   for (int c = 0; c < DIAG_BITMAPS; c++) n_bits += bits[c] != nullptr;
@@ -8338,52 +8351,24 @@ int device_diagnose(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t no
   dg.unschedulable = d_bits[DIAG_BIT_UNSCHEDULABLE];
   dg.unresolvable = d_bits[DIAG_BIT_UNRESOLVABLE];
   HIP_OK(hipMemsetAsync(d->d_diag, 0, (size_t)(tally_bytes + n_bits * bits_bytes), d->stream));
-  HIP_OK(hipMemsetAsync(d->soa.kerr, 0, sizeof(int32_t), d->stream));
-  const KArgs k = make_kargs(ctx, now);
-  bool cpu = false;
-  for (const DevPod& q : d->call.host_pods) cpu = cpu || (q.flags & PF_CPUSET);
-  if (cpu && !d->cpu_alloc) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
-  const bool numa = d->numa_alloc;
   if (N > 0) {
-    const auto eval = pick_diag_eval(numa, cpu, ns);
+    const auto eval = pick_diag_eval(pp.numa, pp.cpu, ns);
     if (!eval) return no_variant("k_diag_eval");
     const int xcd = d->diag_xcd;
     const dim3 grid = xcd ? eval_grid((int)N, EVAL_BLOCK, (int)P, EVAL_PPB)
                           : dim3((unsigned)((N + EVAL_BLOCK - 1) / EVAL_BLOCK), (unsigned)((P + EVAL_PPB - 1) / EVAL_PPB));
-    const int64_t M = N * P;  // every pair may be deferred
-    if (numa) {
-      rc = ensure((void**)&d->d_defer, &d->defer_cap, (sizeof(uint64_t) + sizeof(uint32_t)) * M);  // pairs, merges
-      if (rc) return rc;
-      rc = ensure((void**)&d->d_defer_cnt, &d->defer_cnt_cap, sizeof(uint32_t));
-      if (rc) return rc;
-      HIP_OK(hipMemsetAsync(d->d_defer_cnt, 0, sizeof(uint32_t), d->stream));
-    }
-    hipLaunchKernelGGL(eval, grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->call.d_pods, (int)P, k, dg,
-                       numa ? d->d_defer : nullptr, numa ? d->d_defer_cnt : nullptr, xcd);
+    hipLaunchKernelGGL(eval, grid, dim3(EVAL_BLOCK), 0, d->stream, d->soa, (int)N, d->call.d_pods, (int)P, pp.k, dg,
+                       pp.defer.list, pp.defer.cnt, xcd);
     HIP_OK(hipGetLastError());
-    if (numa) {
-      uint32_t* fb = reinterpret_cast<uint32_t*>(d->d_defer + M);
-      hipLaunchKernelGGL(pick_numa_fallback(true, cpu), dim3(FALLBACK_BLOCKS), dim3(64), 0, d->stream, d->soa,
-                         d->call.d_pods, d->d_batch_base, k, d->d_defer, d->d_defer_cnt, d->d_scores, d->capacity, (int)N,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, fb);
-      HIP_OK(hipGetLastError());
-      hipLaunchKernelGGL(pick_diag_finish(cpu), dim3(FINISH_BLOCKS), dim3(64), 0, d->stream, d->soa, d->call.d_pods, k,
-                         d->d_defer, d->d_defer_cnt, fb, dg);
-      HIP_OK(hipGetLastError());
-    }
+    if (pp.numa &&
+        (rc = launch_numa_deferral(d->stream, d->soa, d->call.d_pods, d->d_batch_base, pp.k, pp.defer, pp.cpu, dg)))
+      return rc;
   }
   std::vector<uint32_t> raw((size_t)(DIAG_WORDS * P));
   HIP_OK(hipMemcpyAsync(raw.data(), dg.tally, (size_t)tally_bytes, hipMemcpyDeviceToHost, d->stream));
   for (int c = 0; c < DIAG_BITMAPS; c++)
     if (bits[c]) HIP_OK(hipMemcpyAsync(bits[c], d_bits[c], (size_t)bits_bytes, hipMemcpyDeviceToHost, d->stream));
-  uint32_t deferred = 0;
-  if (numa && N > 0)
-    HIP_OK(hipMemcpyAsync(&deferred, d->d_defer_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
-  int32_t kerr = 0;
-  HIP_OK(hipMemcpyAsync(&kerr, d->soa.kerr, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
-  HIP_OK(hipStreamSynchronize(d->stream));
-  if (kerr & KERR_HINT_ROUTE) return fail(KE_ERR_DEVICE, "internal: a hinted pod reached a kernel without the hint path");
-  ctx->kstat_numa_deferred = deferred;
+  if ((rc = pair_pass_end(ctx, pp))) return rc;
   for (int64_t p = 0; p < P; p++)
     if (!diag_fold(raw.data() + p * DIAG_WORDS, (int32_t)N, &out[p]))
       return fail(KE_ERR_DEVICE, "internal: the diagnosis tallies of a pod do not add up");
@@ -8595,6 +8580,7 @@ struct ScheduleCall {
           *d_rres = nullptr, *d_tlist = nullptr, *d_chosen = nullptr, *d_chosen_score = nullptr, *d_err = nullptr;
   uint32_t* d_tmx = nullptr;
   uint64_t *d_fst = nullptr, *d_st = nullptr, *d_pst = nullptr, *estamps = nullptr;  // (estamps: eval start of each batch)
+  DeferBufs defer;  // a NUMA context: the deferred-pair list of one batch (reused) + a counter per batch
   // progress
   bool rerun = false;      // the current serial batch is the remainder of a DeviceShare batch that stopped early
   int pre_b = -1;          // a serial batch whose eval + select is already enqueued (behind a DeviceShare cut check)
@@ -8702,11 +8688,9 @@ struct ScheduleCall {
       d->soa.vfo = d->d_vfo;
     }
     if (numa && !c.d_numaalloc) HIP_OK(hipMalloc(&c.d_numaalloc, sizeof(int64_t) * 16 * c.out_cap));
-    if (numa) {  // deferred-pair list of one batch (reused) + a counter per batch
-      if ((rc = ensure((void**)&d->d_defer, &d->defer_cap, (sizeof(uint64_t) + sizeof(uint32_t)) * MAX_BATCH * d->capacity)))
-        return rc;
-      if ((rc = ensure((void**)&d->d_defer_cnt, &d->defer_cnt_cap, sizeof(uint32_t) * n_batches))) return rc;
-      HIP_OK(fill_async(d->d_defer_cnt, 0, sizeof(uint32_t) * n_batches, d->stream));
+    if (numa) {
+      if ((rc = defer_ensure(d, (int64_t)MAX_BATCH * d->capacity, n_batches, &defer))) return rc;
+      HIP_OK(fill_async(defer.cnt, 0, sizeof(uint32_t) * n_batches, d->stream));
     }
     return KE_OK;
   }
@@ -8876,7 +8860,7 @@ struct ScheduleCall {
     // a singleton batch has one pod's worth of lanes: single-wave blocks spread it over every CU
     const int blk = bp == 1 ? 64 : EVAL_BLOCK;
     const dim3 grid = eval_grid(hi - lo, blk, bp, EVAL_PPB);
-    uint32_t* dcnt = numa ? d->d_defer_cnt + b : nullptr;
+    const DeferBufs df{defer.list, defer.fb, numa ? defer.cnt + b : nullptr};  // (the batch's own counter)
     if (plain_rec) {  // plain batch: the record-based evaluation
       hipLaunchKernelGGL(pick_eval_plain(ext, ns), grid, dim3(blk), 0, a.es, d->soa, lo, hi, c.d_pods, bbase, bp, k,
                          eb.scores, d->capacity, stamp, dwait, d_err);
@@ -8884,16 +8868,11 @@ struct ScheduleCall {
       const auto eval = pick_eval_batch(ds, numa, cpu, batches[b].hint, ext, ns);
       if (!eval) return no_variant("k_eval_batch with node sets and a DeviceShare / NUMA / cpuset batch");
       hipLaunchKernelGGL(eval, grid, dim3(blk), 0, a.es, d->soa, lo, hi, c.d_pods, bbase, bp, EVAL_PPB, k, eb.scores,
-                         d->capacity, d->d_dsraw, d->d_defer, dcnt, d->d_aff, d->d_dsmax, stamp);
+                         d->capacity, d->d_dsraw, d->d_defer, df.cnt, d->d_aff, d->d_dsmax, stamp);
     }
     if (numa) {  // a DeviceShare pod defers only on nodes without a device cache (no DeviceShare hints there)
-      uint32_t* fb = reinterpret_cast<uint32_t*>(d->d_defer + (int64_t)MAX_BATCH * d->capacity);
-      hipLaunchKernelGGL(pick_numa_fallback(false, cpu), dim3(FALLBACK_BLOCKS), dim3(64), 0, a.es, d->soa, c.d_pods, bbase,
-                         k, d->d_defer, dcnt, eb.scores, d->capacity, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                         nullptr, ds ? d->d_dsmax : nullptr, cpu ? d->d_aff : nullptr, ds ? d->d_dsraw : nullptr, fb);
-      hipLaunchKernelGGL(pick_numa_finish(false, cpu), dim3(FINISH_BLOCKS), dim3(64), 0, a.es, d->soa, c.d_pods, bbase,
-                         k, d->d_defer, dcnt, eb.scores, d->capacity, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                         nullptr, ds ? d->d_dsmax : nullptr, cpu ? d->d_aff : nullptr, ds ? d->d_dsraw : nullptr, fb);
+      const BatchOut bo{eb.scores, d->capacity, cpu ? d->d_aff : nullptr, ds ? d->d_dsraw : nullptr, ds ? d->d_dsmax : nullptr};
+      return launch_numa_deferral(a.es, d->soa, c.d_pods, bbase, k, df, cpu, bo);
     }
     return KE_OK;
   }

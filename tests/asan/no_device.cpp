@@ -11,6 +11,7 @@ int device_create(Context*) { return none(); }
 void device_destroy(Context*) {}
 int device_eval(Context*, int32_t, const ke_pod*, int64_t, uint8_t*, uint8_t*, int16_t*, int16_t*, int16_t*, int16_t*,
                 int32_t*) { return none(); }
+int device_diagnose(Context*, int32_t, const ke_pod*, int64_t, ke_pod_diagnosis*, int32_t, uint64_t* const*) { return none(); }
 int device_schedule(Context*, int32_t, const ke_pod*, int64_t, int32_t*, int32_t*) { return none(); }
 int device_rsv_result(Context*, int32_t*) { return none(); }
 int device_rsv_gate(const Context*) { return 0; }

@@ -11,6 +11,7 @@ import pytest
 from koordinator_amd import Evaluator, abi, reason_plugin, synth
 from koordinator_amd.evaluator import as_pod_array, unpack_node_sets
 from oracle.binding import Oracle
+from test_gpu_cpuset import NUMA_VARIANTS, numa_cpuset_both
 
 pytestmark = pytest.mark.gpu
 T0 = synth.T0
@@ -252,6 +253,18 @@ def test_cpuset(gpu):
     got, want = check(ev, o, pods, what="cpuset")
     worth_running(want, reasons=5)
     assert (want["n_feasible"] == 0).any()  # a pod with no feasible node
+
+
+# ---- 7b NUMA state and cpuset pods together: k_diag_eval<NUMA, CPU> and the cpuset finish into the diagnosis ----------
+def test_numa_cpuset(gpu):
+    """The cluster and pods of test_gpu_cpuset.py::test_numa_cpuset_eval_matrix_parity[mixed] (the `mixed` variant
+    defers pairs, so it is the one used)."""
+    ev, o = numa_cpuset_both(240, 401, **NUMA_VARIANTS["mixed"])
+    pods = synth.make_numa_cpuset_pods(72, synth.BASE_SEED + 403)
+    got, want = check(ev, o, pods, what="numa + cpuset")
+    worth_running(want)
+    ev.diagnose(pods, T0)
+    assert ev.numa_deferred() > 0  # the deferral ran with binding pods (its pairs are in the counts compared above)
 
 
 # ---- 8 NodeResourcesFit's Filter after a saturated queue -------------------------------------------------------------

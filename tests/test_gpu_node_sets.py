@@ -98,6 +98,49 @@ def test_eval_parity_deviceshare_normalises_over_the_set(gpu):
         assert (got["total"][np.ix_(grp, out)] == -1).all()
 
 
+def test_eval_empty_slots_under_node_sets(gpu):
+    """A pin of ke_eval at empty node slots in a call with node sets: the set gate comes ahead of the slot's own
+    validity test, so an empty slot outside the pod's set reports KE_REASON_NODE_SET and one inside it (or any with
+    id 0) KE_CODE_ERROR; ke_diagnose counts an empty slot as absent whatever the set says."""
+    n, cap = 200, 320
+    cl = synth.make_cluster(n, synth.BASE_SEED + 9221)
+    ev, o = both(synth.config(cap), cl, n)
+    gone = [0, 63, 64, 130, 199]
+    for h in (ev, o):
+        for i in gone:
+            h.delete_node(i)
+    assert ev.num_nodes == n
+    present = np.ones(n, bool)
+    present[gone] = False
+    sets = np.random.default_rng(synth.BASE_SEED + 9222).random((3, n)) < 0.5
+    sets[0, gone] = [True, False, True, False, True]   # every deleted node inside at least one set
+    sets[1, gone] = [False, True, False, True, False]  # ... and outside at least one
+    assert sets[:, gone].any(0).all() and not sets[:, gone].all(0).any()
+    pods = synth.make_pods(8, synth.BASE_SEED + 9223)
+    ids = np.array([0, 1, 2, 3, 0, 1, 2, 3])
+    ev.node_sets_load(sets)
+    el = eligibility(sets, ids)
+    got, want = ev.eval(pods, T0, node_sets=ids), o.eval(pods, T0)
+    # every pair outside the pod's set, the deleted columns included
+    assert (~el[:, gone]).any() and el[:, gone].any()
+    assert (got["status"][~el] == abi.CODE_UNSCHEDULABLE_AND_UNRESOLVABLE).all()
+    assert (got["reason"][~el] == abi.REASON_NODE_SET).all()
+    # a deleted column inside the set (or id 0): the empty slot itself
+    empty = el & ~present
+    assert (got["status"][empty] == abi.CODE_ERROR).all()
+    assert (got["reason"][empty] == abi.REASON_NONE).all()
+    for k in ("la", "numa", "ds"):
+        assert (got[k][:, gone] == 0).all() and (got[k][~el] == 0).all(), k
+    assert (got["total"][:, gone] == -1).all() and (got["total"][~el] == -1).all()
+    # the populated columns: the oracle
+    live = el & present
+    for k in EVAL_KEYS + ("ds",):
+        assert np.array_equal(got[k][live], want[k][live]), k
+    d = ev.diagnose(pods, T0, node_sets=ids)
+    assert (d["n_absent"] == len(gone)).all() and (d["n_nodes"] == n - len(gone)).all()
+    assert np.array_equal(d["reason_nodes"][:, abi.REASON_NODE_SET], (~el & present).sum(1))
+
+
 # ---- 3, 4: ke_schedule, disjoint sets: one oracle per sub-cluster ----------------------------------------------------
 def _partition(n, n_pods, seed):
     rng = np.random.default_rng(synth.BASE_SEED + seed)
