@@ -2681,6 +2681,92 @@ void flush_mirror_async(Context& c) {
   });
 }
 
+static void side_row_ds(const ke_config&, const NodeState& ns, int64_t* r) {
+  derive_ds_row(ns, r, reinterpret_cast<uint64_t*>(r + NUM_DS_FIELDS));
+  derive_dsx_row(ns, r + NUM_DS_FIELDS + NUM_DS_MASKS);
+}
+static void side_row_numa(const ke_config&, const NodeState& ns, int64_t* r) {
+  uint64_t mask;
+  derive_numa_row(ns, r, &mask);
+  r[NUM_NUMA_FIELDS] = (int64_t)mask;
+}
+static void side_row_ext(const ke_config& cfg, const NodeState& ns, int64_t* r) {
+  uint64_t mask;
+  derive_ext_row(cfg, ns, r, &mask);
+  r[NUM_XF] = (int64_t)mask;
+}
+static void side_row_cpu(const ke_config&, const NodeState& ns, int64_t* r) {
+  derive_cpu_rows(ns, reinterpret_cast<CpuRec*>(r), r + CPU_SLOTS);
+}
+static bool has_zones(const NodeState& ns) { return !ns.zones.empty(); }
+static bool any_node(const NodeState&) { return true; }
+static bool valid_node(const NodeState& ns) { return ns.valid; }
+const SideTableDesc& side_table(int t) {
+  static const SideTableDesc tables[N_SIDE_TABLES] = {
+    // DeviceShare (the device state is not time-dependent): a device cache entry marks its own node
+    {&Context::ds_enabled, DS_ROW_WORDS, side_row_ds, nullptr},
+    // NUMA topology: the rows derived before the NUMA SoA existed
+    {&Context::numa_enabled, NUMA_ROW_WORDS, side_row_numa, has_zones},
+    // NodeResourcesFitPlus / ScarceResourceAvoidance
+    {&Context::ext_enabled, XROW_WORDS, side_row_ext, any_node},
+    // CPU tables + summaries: every node needs its summary words once a cpuset pod is evaluated (the amplified-cpu
+    // filter of a binding pod reads the node's ratio even without a CPU table)
+    {&Context::cpu_enabled, CPU_ROW_WORDS, side_row_cpu, valid_node},
+  };
+  return tables[t];
+}
+
+void refresh_scan(Context& c, int64_t now, const bool (&exists)[N_SIDE_TABLES], RefreshBatch* out) {
+  // nothing marked dirty since every row was last clean, and no row expired: no scan over the nodes; no row
+  // expired and the same nodes: only the dirty list (the nodes marked since)
+  const bool no_expiry = now < c.min_valid_until && c.n_nodes == c.clean_n_nodes;
+  const bool all_clean = no_expiry && g_dirty_epoch.load(std::memory_order_relaxed) == c.clean_epoch;
+  if (all_clean) return;
+  const bool incremental = no_expiry;
+  mirror_join(c);  // a row may be derived: the host mirror on its thread first
+  if (!c.pending.empty()) {  // a row to derive needs the deferred host mirror first
+    bool any = false;
+    if (incremental)
+      for (int32_t i : c.dirty_list) any = any || (i < c.n_nodes && c.nodes[(size_t)i].dirty);
+    else
+      for (int32_t i = 0; i < c.n_nodes && !any; i++) any = c.nodes[(size_t)i].dirty || now >= c.nodes[(size_t)i].valid_until;
+    if (any) flush_mirror(c);
+  }
+  int64_t mvu = incremental ? c.min_valid_until : INT64_MAX;
+  std::vector<int32_t> visit;
+  if (incremental) visit.swap(c.dirty_list);  // (flush_mirror above may have appended; a repeated node is clean the 2nd time)
+  const int32_t n_visit = incremental ? (int32_t)visit.size() : c.n_nodes;
+  for (int32_t v = 0; v < n_visit; v++) {
+    const int32_t i = incremental ? visit[(size_t)v] : v;
+    if (i >= c.n_nodes) continue;
+    NodeState& ns = c.nodes[(size_t)i];
+    if (!ns.dirty && now < ns.valid_until) {
+      mvu = std::min(mvu, ns.valid_until);
+      continue;
+    }
+    Row r;
+    int64_t vu;
+    derive_row(c.cfg, ns, now, &r, &vu);
+    for (int t = 0; t < N_SIDE_TABLES; t++) {
+      if (!ns.dirty || !exists[t]) continue;
+      auto& side = out->side[t];
+      const size_t o = side.rows.size();
+      side.rows.resize(o + (size_t)side_table(t).row_words);
+      side_table(t).derive(c.cfg, ns, &side.rows[o]);
+      side.idx.push_back(i);
+    }
+    ns.valid_until = vu;
+    ns.dirty = false;
+    mvu = std::min(mvu, vu);
+    out->rows.push_back(r);
+    out->idx.push_back(i);
+  }
+  c.clean_epoch = g_dirty_epoch.load(std::memory_order_relaxed);
+  c.min_valid_until = mvu;
+  c.clean_n_nodes = c.n_nodes;
+  c.dirty_list.clear();  // every node < n_nodes is clean now
+}
+
 void host_assign(const ke_config& cfg, NodeState& ns, const ke_pod& pod, int64_t timestamp_ns, bool mark_dirty) {
   if (pod.is_terminated) return;  // pod_assign_cache.go:90
   AssignedPod info{};

@@ -438,6 +438,36 @@ void derive_cpu_rows(const NodeState& ns, CpuRec* recs, int64_t* cs);
 // NUMA nodes' single / shared status (node_allocation.go:111-156)
 void host_cpuset_reserve(NodeState& ns, const DevPod& dp, const uint64_t* set);
 
+// ---- device_refresh's host half ----------------------------------------------------------------------------------
+// The optional per-node tables beside the node rows, each described once: here what the host needs of it, in
+// ke_kernels.hip (side_dev, same index) its SoA arrays and scatter kernel.  A row is row_words int64 as its scatter
+// kernel reads them; the table's device arrays appear once `enabled` is set, and rows derived before that never
+// reached them, so that first refresh marks the nodes `first_dirty` names (nullptr: none) dirty.
+enum SideTable { ST_DS, ST_NUMA, ST_EXT, ST_CPU, N_SIDE_TABLES };
+constexpr int DS_ROW_WORDS = NUM_DS_FIELDS + NUM_DS_MASKS + NUM_DSX;  // device fields, masks, hint words
+constexpr int NUMA_ROW_WORDS = NUM_NUMA_FIELDS + 1;                   // int64 fields + the mask word
+constexpr int XROW_WORDS = NUM_XF + 1;                                // ext row: NUM_XF int64 + the mask
+constexpr int CPU_ROW_WORDS = CPU_SLOTS + NUM_CS_FIELDS;              // records (one int64 each) + summary
+struct SideTableDesc {
+  bool Context::*enabled;
+  int row_words;
+  void (*derive)(const ke_config& cfg, const NodeState& ns, int64_t* row);
+  bool (*first_dirty)(const NodeState& ns);
+};
+const SideTableDesc& side_table(int t);
+// What one refresh uploads: the node rows, and per side table its rows (row_words each) -- with the nodes they belong to
+struct RefreshBatch {
+  std::vector<Row> rows;
+  std::vector<int32_t> idx;
+  struct {
+    std::vector<int64_t> rows;
+    std::vector<int32_t> idx;
+  } side[N_SIDE_TABLES];
+};
+// The rows of the dirty / time-expired nodes re-derived for `now` (the host mirror applied first when one is), with
+// the side rows of the dirty ones for every table in `exists`; the nodes are clean afterwards.
+void refresh_scan(Context& c, int64_t now, const bool (&exists)[N_SIDE_TABLES], RefreshBatch* out);
+
 // Release of one placement from its node (ke_pod_release): podAssignCache.unAssign, NodeInfo.RemovePod
 // (Requested, the FitPlus requested when `ext`), resourceManager.Release, DeviceShare updateCacheUsed(false)
 void host_release_node(const ke_config& cfg, bool ext, NodeState& ns, const ke_pod& pod, const ke_pod_allocation& a,

@@ -46,6 +46,12 @@ extern "C" __device__ int32_t __ockl_wfred_add_i32(int32_t);
     }                                                                                \
   } while (0)
 
+// a call that returns a ke status: passed on when it is not KE_OK
+#define RC_OK(expr)                  \
+  do {                               \
+    if (int _rc = (expr)) return _rc; \
+  } while (0)
+
 constexpr int EVAL_BLOCK = 256;
 // k_eval_batch grid: node tiles padded to a multiple of the 8 XCDs (x) x pod groups (y)
 inline dim3 eval_grid(int n_nodes, int block, int pods, int ppb) {
@@ -7048,8 +7054,11 @@ struct PinnedVec {
   T* p = nullptr;
   size_t n = 0, cap = 0;
   PinnedVec() = default;
-  PinnedVec(const PinnedVec&) = delete;
-  PinnedVec& operator=(const PinnedVec&) = delete;
+  PinnedVec(PinnedVec&& o) noexcept : p(o.p), n(o.n), cap(o.cap) { o.p = nullptr, o.n = o.cap = 0; }
+  PinnedVec& operator=(PinnedVec&& o) noexcept {
+    std::swap(p, o.p), std::swap(n, o.n), std::swap(cap, o.cap);
+    return *this;
+  }
   ~PinnedVec() {
     if (p) (void)hipHostFree(p);
   }
@@ -7077,78 +7086,122 @@ struct PinnedVec {
   const T& operator[](size_t i) const { return p[i]; }
   T* begin() { return p; }
   T* end() { return p + n; }
-  void swap(PinnedVec& o) {
-    std::swap(p, o.p);
-    std::swap(n, o.n);
-    std::swap(cap, o.cap);
-  }
   const T* begin() const { return p; }
   const T* end() const { return p + n; }
+};
+
+// The owner of one device allocation of `cap` elements (move-only, freed with it); reads as its pointer.  Every
+// device pointer of DeviceState and CallBufs is one: whoever frees the owner has waited for the streams first
+// (device_destroy), and nothing else in this file allocates or frees device memory.
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p), std::swap(cap, o.cap);
+    return *this;
+  }
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  // room for n elements; contents not kept when it grows (the old allocation is freed first)
+  int reserve(size_t n) {
+    if (cap >= n) return KE_OK;
+    if (p) HIP_OK(hipFree(p));
+    p = nullptr;
+    cap = 0;
+    HIP_OK(hipMalloc((void**)&p, sizeof(T) * n));
+    cap = n;
+    return KE_OK;
+  }
+  // ... and an allocation made here starts as zero bytes, filled on stream `s`
+  int reserve_zeroed(size_t n, hipStream_t s) {
+    if (cap >= n) return KE_OK;
+    const int rc = reserve(n);
+    if (rc) return rc;
+    HIP_OK(hipMemsetAsync(p, 0, sizeof(T) * n, s));
+    return KE_OK;
+  }
+  operator T*() const { return p; }
+  T* get() const { return p; }
 };
 
 // What each of two calls in flight (ke_schedule_submit) needs of its own: `call` is the set of the call being
 // enqueued, `alt` the other one's; device_swap_call_buffers swaps them whole.
 struct CallBufs {
   PinnedVec<DevPod> host_pods;  // the uploaded queue (batch segmentation), page-locked
-  DevPod* d_pods = nullptr;     // ... on the device, the call's id words and batch bases behind the records
-  int64_t pods_cap = 0;
+  DevBuf<DevPod> d_pods;        // ... on the device, the call's id words and batch bases behind the records
   // ke_schedule's read-back block (OutLayout): scores, placements, the call's error word, fixup stamps and the
   // batch stamps, contiguous in the order the completion reads them, so one copy brings them to h_out
-  uint8_t* d_out = nullptr;
-  uint64_t* d_devalloc = nullptr;  // [n_pods] device minors allocated per pod
-  int64_t* d_numaalloc = nullptr;  // [n_pods][16] per-zone allocation of each pod
-  int64_t out_cap = 0;             // pods (d_out, d_devalloc, d_numaalloc)
-  uint64_t* d_cpusets = nullptr;   // [n_pods][4] cpuset of each pod
-  int64_t cpusets_cap = 0;         // bytes
-  int32_t* d_sched = nullptr;      // ke_schedule bookkeeping (SchedLayout): hand-off flags, the T helpers' lists
-  int64_t sched_cap = 0;           // bytes
-  PinnedVec<uint8_t> h_out;        // the read-back staging (HostOutLayout)
-  std::vector<hipEvent_t> tev;     // the call's events (pool): span, the call's end per stream, samples
-  void swap(CallBufs& o) {
-    host_pods.swap(o.host_pods);
-    h_out.swap(o.h_out);
-    tev.swap(o.tev);
-    std::swap(d_pods, o.d_pods), std::swap(pods_cap, o.pods_cap);
-    std::swap(d_out, o.d_out), std::swap(d_devalloc, o.d_devalloc), std::swap(d_numaalloc, o.d_numaalloc);
-    std::swap(out_cap, o.out_cap), std::swap(d_cpusets, o.d_cpusets), std::swap(cpusets_cap, o.cpusets_cap);
-    std::swap(d_sched, o.d_sched), std::swap(sched_cap, o.sched_cap);
-  }
+  DevBuf<uint8_t> d_out;
+  DevBuf<uint64_t> d_devalloc;   // [n_pods] device minors allocated per pod
+  DevBuf<int64_t> d_numaalloc;   // [n_pods][16] per-zone allocation of each pod (NUMA contexts)
+  DevBuf<uint64_t> d_cpusets;    // [n_pods][4] cpuset of each pod
+  DevBuf<int32_t> d_sched;       // ke_schedule bookkeeping (SchedLayout): hand-off flags, the T helpers' lists
+  PinnedVec<uint8_t> h_out;      // the read-back staging (HostOutLayout)
+  std::vector<hipEvent_t> tev;   // the call's events (pool): span, the call's end per stream, samples
+};
+
+// The device half of a side table's description (its host half: side_table, ke_host.h): the SoA arrays it owns (the
+// member's offset in SoA -- each a plain pointer -- and its bytes per node), and its scatter kernel with the launch
+// geometry.  ST_BASE, the node rows themselves, is staged
+// and deferred like a side table; its arrays exist from device_create and its scatter takes KArgs (scatter_launch).
+constexpr int ST_BASE = N_SIDE_TABLES;
+constexpr int SIDE_ARRAYS = 3;
+using ScatterFn = void (*)(SoA, const int64_t*, const int32_t*, int, const int32_t*);
+struct SideTableDev {
+  struct {
+    size_t soa_offset, node_bytes;  // node_bytes 0: no such array
+  } arr[SIDE_ARRAYS];
+  ScatterFn scatter;
+  int block, nodes_per_block;
+};
+static const SideTableDev& side_dev(int t);
+// one table's scatter of a refresh: n rows (and their node indices) staged on the device
+struct Scatter {
+  int table;  // SideTable, or ST_BASE
+  const int64_t* rows;
+  const int32_t* idx;
+  int n;
 };
 
 struct DeviceState {
   int device = 0;
   hipStream_t stream = nullptr;
-  SoA soa{};
+  SoA soa{};  // what the kernels get: raw pointers into the buffers below
   int64_t capacity = 0;
-  // staging for row uploads
-  Row* d_rows = nullptr;
-  int32_t* d_idx = nullptr;
-  int64_t staging_cap = 0;
+  DevBuf<int64_t> d_f;       // soa.f
+  DevBuf<uint32_t> d_flags;  // soa.flags
+  DevBuf<int64_t> d_rec;     // soa.rec
+  DevBuf<int32_t> d_kerr;    // soa.kerr
+  DevBuf<int64_t> d_qt;      // soa.qt (ElasticQuota, from the first tree)
+  DevBuf<int32_t> d_qm;      // soa.qm
+  DevBuf<uint64_t> d_pt;     // soa.pt (GPU partition tables; the pool only grows)
+  // the side tables' SoA arrays (side_dev(t).arr; a table exists when its first array does) and, per table and for
+  // the node rows (ST_BASE), the device staging of a refresh: the rows, their node indices behind them
+  DevBuf<uint8_t> side[N_SIDE_TABLES][SIDE_ARRAYS];
+  DevBuf<int64_t> d_stage[N_SIDE_TABLES + 1];
+  bool has(SideTable t) const { return side[t][0] != nullptr; }
   CallBufs call, alt;
-  DevPodHint* d_ph = nullptr;  // the hinted pods' records of the current call
-  int64_t ph_cap = 0;
+  DevBuf<DevPodHint> d_ph;  // the hinted pods' records of the current call
   // node eligibility sets: rows 0 .. ns_n of capacity / 64 words (row 0 all ones); a call's set ids
   // lie behind its DevPod records in d_pods (one per buffer set), staged alike behind host_pods (upload_pods)
-  uint64_t* d_ns_tbl = nullptr;
-  int64_t ns_tbl_cap = 0;
+  DevBuf<uint64_t> d_ns_tbl;
   // node score offsets: rows 0 .. nsc_n of `capacity` uint16 entries (row 0 all zero)
-  uint16_t* d_nsc_tbl = nullptr;
-  int64_t nsc_tbl_cap = 0;
-  int8_t* d_vfo = nullptr;     // [n_pods][2][DS_MINORS] VF ranks of the Reserves
-  int64_t vfo_cap = 0;
+  DevBuf<uint16_t> d_nsc_tbl;
+  DevBuf<int8_t> d_vfo;     // [n_pods][2][DS_MINORS] VF ranks of the Reserves
   // batch buffers
-  uint16_t* d_scores = nullptr;  // [MAX_BATCH][capacity]
-  uint32_t* d_cand = nullptr;    // [MAX_BATCH][KMAX]
-  int32_t* d_cand_cnt = nullptr;
-  int32_t* d_batch_base = nullptr;  // a zero word (batch base of the parity / bench launches)
+  DevBuf<uint16_t> d_scores;  // [MAX_BATCH][capacity]
+  DevBuf<uint32_t> d_cand;    // [MAX_BATCH][KMAX]
+  DevBuf<int32_t> d_cand_cnt;
+  DevBuf<int32_t> d_batch_base;  // a zero word (batch base of the parity / bench launches)
   // parity outputs
-  void* d_parity = nullptr;
-  int64_t parity_cap = 0;
-  uint32_t* d_best = nullptr;
-  int64_t best_cap = 0;
+  DevBuf<uint8_t> d_parity;
+  DevBuf<uint32_t> d_best;
   // ke_diagnose: the raw tallies [pods][DIAG_WORDS] u32, then the bitmaps asked for ([pods][words_per_pod] u64 each)
-  void* d_diag = nullptr;
-  int64_t diag_cap = 0;
+  DevBuf<uint8_t> d_diag;
   bool diag_xcd = true;  // k_diag_eval's XCD-aware block mapping (KOORDEVAL_DIAG_XCD=0: the plain one, an A/B; §4q)
   int profile_every = 0;
   // node sharding (ke_shard_init): this rank evaluates/selects nodes shard_range(rank); the per-shard
@@ -7159,36 +7212,21 @@ struct DeviceState {
   // ke_shard_init_host: the caller's host collective carries the all-gather / all-reduces instead of RCCL
   ke_host_collective host_fn = nullptr;
   void* host_user = nullptr;
-  uint32_t* d_gath = nullptr;  // [world][GATH_WORDS]
-  uint32_t* d_split = nullptr; // [MAX_WORLD][GATH_WORDS]: the part lists of a split k_select (unsharded)
+  DevBuf<uint32_t> d_gath;   // [world][GATH_WORDS]
+  DevBuf<uint32_t> d_split;  // [MAX_WORLD][GATH_WORDS]: the part lists of a split k_select (unsharded)
   // DeviceShare
-  bool ds_alloc = false;         // soa.ds / soa.dsm allocated
-  size_t pt_words = 0;           // soa.pt capacity (uint64 words)
-  uint16_t* d_dsraw = nullptr;   // [capacity] raw DeviceShare score + 1 of the batch's DeviceShare pod
-  uint32_t* d_dsmax = nullptr;   // 1 + max raw score over the feasible nodes of the batch's pod
-  int64_t* d_dsrows = nullptr;   // staging for DeviceShare row uploads
-  int64_t ds_staging_cap = 0;
+  DevBuf<uint16_t> d_dsraw;  // [capacity] raw DeviceShare score + 1 of the batch's DeviceShare pod
+  DevBuf<uint32_t> d_dsmax;  // 1 + max raw score over the feasible nodes of the batch's pod
   PinnedVec<int64_t> h_refresh[2];  // device_refresh's row staging (every table's rows + indices), two in turn
   PinnedVec<uint8_t> h_rsv;       // a matched pod's RsvPair / RsvOvr uploads
   PinnedVec<int32_t> h_rsv_out;   // k_rsv_pick's result words, read back by the call's own copies
   PinnedVec<int32_t> h_cut;       // a DeviceShare batch's cut word (async read-back, the next batch enqueued behind)
   std::vector<DevPodHint> host_ph;  // its hinted pods' records (the async upload reads them)
-  // NUMA topology
-  bool numa_alloc = false;         // soa.nf / soa.nm allocated
-  int64_t* d_numarows = nullptr;   // staging for NUMA row uploads
-  int64_t numa_staging_cap = 0;
-  bool ext_alloc = false;          // soa.xf / soa.xm allocated (NodeResourcesFitPlus / ScarceResourceAvoidance)
-  int64_t* d_xrows = nullptr;      // staging for ext row uploads
-  int64_t ext_staging_cap = 0;
-  uint64_t* d_defer = nullptr;     // deferred BestEffort pairs of one eval launch (k_numa_fallback)
-  int64_t defer_cap = 0;           // bytes
-  uint32_t* d_defer_cnt = nullptr; // one counter per batch of a ke_schedule (or the ke_eval launch)
-  int64_t defer_cnt_cap = 0;       // bytes
-  // CPU tables (cpuset pods)
-  bool cpu_alloc = false;          // soa.cs / soa.cpu allocated
-  int64_t* d_cpurows = nullptr;    // staging for CPU table uploads
-  int64_t cpu_staging_cap = 0;     // nodes
-  uint8_t* d_aff = nullptr;        // [capacity] NUMA affinity per node of a singleton batch's eval
+  // NUMA topology: the deferred BestEffort pairs of one eval launch (k_numa_fallback), their merge words behind
+  // them, and one counter per batch of a ke_schedule (or the ke_eval launch)
+  DevBuf<uint64_t> d_defer;
+  DevBuf<uint32_t> d_defer_cnt;
+  DevBuf<uint8_t> d_aff;  // [capacity] NUMA affinity per node of a singleton batch's eval
   // pipelined schedule: eval + select run on `estream` one batch ahead of the Reserve chain on `stream`
   hipStream_t estream = nullptr;
   // a second eval stream with its own score matrix / part lists: consecutive batches of a stale-list run
@@ -7196,15 +7234,15 @@ struct DeviceState {
   // double the score matrix)
   hipStream_t estream2 = nullptr;
   hipEvent_t ev_sel2 = nullptr;
-  uint16_t* d_scores2 = nullptr;
-  uint32_t* d_split2 = nullptr;
-  uint32_t* d_stale = nullptr;      // [2][MAX_BATCH][KSTALE] stale-snapshot candidate lists
-  uint32_t* d_pre = nullptr;        // [2][MAX_BATCH][KSTALE2] select-ahead lists before k_fixlist (+ counts after)
-  uint32_t* d_chg = nullptr;        // changed-node bitmap of the replay when node ids exceed its LDS copy
-  int64_t* d_trows = nullptr;       // [MAX_BATCH][NUM_RW] records the last resolved batch changed (node in RW_PAD)
-  int32_t* d_tcnt = nullptr;        // their count
-  int32_t* d_parts_done = nullptr;  // [MAX_BATCH] parts of each pod a split k_select finished (zero between launches)
-  int32_t* d_stale_cnt = nullptr;   // [2][MAX_BATCH]
+  DevBuf<uint16_t> d_scores2;
+  DevBuf<uint32_t> d_split2;
+  DevBuf<uint32_t> d_stale;       // [2][MAX_BATCH][KSTALE] stale-snapshot candidate lists
+  DevBuf<uint32_t> d_pre;         // [2][MAX_BATCH][KSTALE2] select-ahead lists before k_fixlist (+ counts after)
+  DevBuf<uint32_t> d_chg;         // changed-node bitmap of the replay when node ids exceed its LDS copy
+  DevBuf<int64_t> d_trows;        // [MAX_BATCH][NUM_RW] records the last resolved batch changed (node in RW_PAD)
+  DevBuf<int32_t> d_tcnt;         // their count
+  DevBuf<int32_t> d_parts_done;   // [MAX_BATCH] parts of each pod a split k_select finished (zero between launches)
+  DevBuf<int32_t> d_stale_cnt;    // [2][MAX_BATCH]
   static constexpr int EV_RING = 8;
   hipEvent_t ev_res[EV_RING] = {};  // a batch's Reserve done (stream)
   hipEvent_t ev_sel[EV_RING] = {};  // a batch's candidate lists done (estream)
@@ -7214,8 +7252,11 @@ struct DeviceState {
   hipEvent_t ev_refresh[2] = {};  // the copies out of h_refresh[i] done
   bool refresh_pending[2] = {};
   int refresh_cur = 0;
-  std::vector<std::function<void(const int32_t*)>> deferred;  // device_refresh(defer): its scatters, gated
-  int32_t* d_rsv_gate = nullptr;    // k_rsv_check's word: a fused matched pod's speculation failed (1)
+  // device_refresh(defer): its scatters, launched (gated) by device_refresh_flush; deferred_k: the node rows' KArgs
+  Scatter deferred[N_SIDE_TABLES + 1];
+  int n_deferred = 0;
+  KArgs deferred_k{};
+  DevBuf<int32_t> d_rsv_gate;       // k_rsv_check's word: a fused matched pod's speculation failed (1)
   bool pipeline = true;             // ke_set_pipeline
   bool pipe_fixup = false;          // ke_set_pipeline(2): exact lists from k_fixup for every run (else quota runs only)
   // dynamic LDS of the eval streams' LDS-free kernels: more than what a Reserve workgroup (ResLds) leaves free of
@@ -7228,29 +7269,12 @@ struct DeviceState {
   int t_helpers = 4;                // T-row helper workgroups of a stale-list run (THelp; KOORDEVAL_T_HELPERS)
   int t_help_ignore = 0;            // test hook (KOORDEVAL_T_HELPERS_IGNORE): the replay's own T rows every batch
   // the Reservation plugin of a singleton batch (k_rsv_pick): its pairs and result words
-  RsvPair* d_rsv = nullptr;
-  int64_t rsv_cap = 0;              // bytes
-  void* d_rsv_views = nullptr;      // k_rsv_views: views, outputs, the pod
-  int64_t rsv_views_cap = 0;
-  void* d_ds_views = nullptr;       // k_ds_views: views, outputs, the pod
-  int64_t ds_views_cap = 0;
-  void* d_numa_views = nullptr;     // k_numa_views: views, outputs, the pod
-  int64_t numa_views_cap = 0;
-  RsvOvr* d_rovr = nullptr;         // the segment's allocate-from-reservation decisions (SoA::rovr)
-  int64_t rovr_cap = 0;
-  int32_t* d_rsv_out = nullptr;     // [4]
-  RsvPickSt* d_rsv_st = nullptr;    // k_rsv_stage's words (node-sharded contexts)
+  DevBuf<RsvPair> d_rsv;
+  DevBuf<uint8_t> d_views;          // k_rsv_views / k_ds_views / k_numa_views (launch_views): views, outputs, the pod
+  DevBuf<RsvOvr> d_rovr;            // the segment's allocate-from-reservation decisions (SoA::rovr)
+  DevBuf<int32_t> d_rsv_out;        // [4]
+  DevBuf<RsvPickSt> d_rsv_st;       // k_rsv_stage's words (node-sharded contexts)
 };
-
-static int ensure(void** p, int64_t* cap, int64_t bytes) {
-  if (*cap >= bytes) return KE_OK;
-  if (*p) HIP_OK(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  HIP_OK(hipMalloc(p, (size_t)bytes));
-  *cap = bytes;
-  return KE_OK;
-}
 
 int device_available() {
   int n = 0;
@@ -7286,135 +7310,108 @@ int device_create(Context* ctx) {
   HIP_OK(hipEventCreateWithFlags(&d->ev_start, hipEventDisableTiming));
   for (hipEvent_t& e : d->ev_refresh) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   d->capacity = ((int64_t)ctx->cfg.node_capacity + 255) & ~255LL;
+  const size_t cap = (size_t)d->capacity;
   d->soa.stride = d->capacity;
-  HIP_OK(hipMalloc(&d->soa.f, sizeof(int64_t) * NUM_I64_FIELDS * d->capacity));
-  HIP_OK(hipMalloc(&d->soa.flags, sizeof(uint32_t) * d->capacity));
-  HIP_OK(hipMemsetAsync(d->soa.f, 0, sizeof(int64_t) * NUM_I64_FIELDS * d->capacity, d->stream));
-  HIP_OK(hipMemsetAsync(d->soa.flags, 0, sizeof(uint32_t) * d->capacity, d->stream));
-  HIP_OK(hipMalloc(&d->d_scores, sizeof(uint16_t) * MAX_BATCH * d->capacity));
+  RC_OK(d->d_f.reserve_zeroed(NUM_I64_FIELDS * cap, d->stream));
+  RC_OK(d->d_flags.reserve_zeroed(cap, d->stream));
+  RC_OK(d->d_scores.reserve(MAX_BATCH * cap));
   if (d->capacity <= (1 << 20)) {  // <= 128 MB for the second score matrix
     HIP_OK(hipStreamCreateWithPriority(&d->estream2, hipStreamNonBlocking, prio_lo));
     HIP_OK(hipEventCreateWithFlags(&d->ev_sel2, hipEventDisableTiming));
-    HIP_OK(hipMalloc(&d->d_scores2, sizeof(uint16_t) * MAX_BATCH * d->capacity));
-    HIP_OK(hipMalloc(&d->d_split2, sizeof(uint32_t) * GATH_WORDS_MAX * MAX_WORLD));
+    RC_OK(d->d_scores2.reserve(MAX_BATCH * cap));
+    RC_OK(d->d_split2.reserve((size_t)GATH_WORDS_MAX * MAX_WORLD));
   }
-  HIP_OK(hipMalloc(&d->d_cand, sizeof(uint32_t) * MAX_BATCH * KMAX));
-  HIP_OK(hipMalloc(&d->d_cand_cnt, sizeof(int32_t) * MAX_BATCH));
-  HIP_OK(hipMalloc(&d->d_batch_base, sizeof(int32_t)));
-  HIP_OK(hipMemsetAsync(d->d_batch_base, 0, sizeof(int32_t), d->stream));
-  HIP_OK(hipMalloc(&d->d_stale, sizeof(uint32_t) * 2 * MAX_BATCH * KSTALE));
-  HIP_OK(hipMalloc(&d->d_pre, sizeof(uint32_t) * 2 * MAX_BATCH * (KSTALE2 + 1)));
-  HIP_OK(hipMalloc(&d->d_stale_cnt, sizeof(int32_t) * 2 * MAX_BATCH));
-  HIP_OK(hipMalloc(&d->d_trows, sizeof(int64_t) * MAX_BATCH * NUM_RW));
-  HIP_OK(hipMalloc(&d->soa.rec, sizeof(int64_t) * NUM_RW * d->capacity));
-  HIP_OK(hipMalloc(&d->soa.kerr, sizeof(int32_t)));
-  HIP_OK(hipMemsetAsync(d->soa.kerr, 0, sizeof(int32_t), d->stream));
-  HIP_OK(hipMemsetAsync(d->soa.rec, 0, sizeof(int64_t) * NUM_RW * d->capacity, d->stream));
-  HIP_OK(hipMalloc(&d->d_tcnt, sizeof(int32_t)));
-  HIP_OK(hipMalloc(&d->d_parts_done, sizeof(int32_t) * 2 * MAX_BATCH));  // (one half per eval stream)
-  HIP_OK(hipMemset(d->d_parts_done, 0, sizeof(int32_t) * 2 * MAX_BATCH));
-  if (d->capacity > (int64_t)CHG_LDS_WORDS * 32) {  // zero between batches (each replay clears its bits)
-    HIP_OK(hipMalloc(&d->d_chg, sizeof(uint32_t) * (d->capacity + 31) / 32));
-    HIP_OK(hipMemsetAsync(d->d_chg, 0, sizeof(uint32_t) * (d->capacity + 31) / 32, d->stream));
-  }
-  HIP_OK(hipMalloc(&d->d_dsraw, sizeof(uint16_t) * MAX_BATCH * d->capacity));  // per pod of a DeviceShare batch
-  HIP_OK(hipMalloc(&d->d_dsmax, sizeof(uint32_t) * DSB_WORDS));
+  RC_OK(d->d_cand.reserve((size_t)MAX_BATCH * KMAX));
+  RC_OK(d->d_cand_cnt.reserve(MAX_BATCH));
+  RC_OK(d->d_batch_base.reserve_zeroed(1, d->stream));
+  RC_OK(d->d_stale.reserve((size_t)2 * MAX_BATCH * KSTALE));
+  RC_OK(d->d_pre.reserve((size_t)2 * MAX_BATCH * (KSTALE2 + 1)));
+  RC_OK(d->d_stale_cnt.reserve(2 * MAX_BATCH));
+  RC_OK(d->d_trows.reserve((size_t)MAX_BATCH * NUM_RW));
+  RC_OK(d->d_rec.reserve_zeroed(NUM_RW * cap, d->stream));
+  RC_OK(d->d_kerr.reserve_zeroed(1, d->stream));
+  RC_OK(d->d_tcnt.reserve(1));
+  RC_OK(d->d_parts_done.reserve_zeroed(2 * MAX_BATCH, d->stream));  // (one half per eval stream)
+  if (d->capacity > (int64_t)CHG_LDS_WORDS * 32)  // zero between batches (each replay clears its bits)
+    RC_OK(d->d_chg.reserve_zeroed((cap + 31) / 32, d->stream));
+  RC_OK(d->d_dsraw.reserve(MAX_BATCH * cap));  // per pod of a DeviceShare batch
+  RC_OK(d->d_dsmax.reserve(DSB_WORDS));
+  RC_OK(d->d_aff.reserve(cap));
+  RC_OK(d->d_split.reserve((size_t)GATH_WORDS_MAX * MAX_WORLD));
+  RC_OK(d->d_rsv_out.reserve(4));
+  RC_OK(d->d_rsv_st.reserve(1));
+  d->soa.f = d->d_f;
+  d->soa.flags = d->d_flags;
+  d->soa.rec = d->d_rec;
+  d->soa.kerr = d->d_kerr;
   d->soa.dsb = d->d_dsmax;
   d->soa.dsraw = d->d_dsraw;
-  HIP_OK(hipMalloc(&d->d_aff, d->capacity));
-  HIP_OK(hipMalloc(&d->d_split, sizeof(uint32_t) * GATH_WORDS_MAX * MAX_WORLD));
-  HIP_OK(hipMalloc(&d->d_rsv_out, sizeof(int32_t) * 4));
-  HIP_OK(hipMalloc(&d->d_rsv_st, sizeof(RsvPickSt)));
   HIP_OK(hipStreamSynchronize(d->stream));
   return KE_OK;
 }
 
 int device_refresh(Context* ctx, int64_t now, bool defer = false);
 int device_refresh_flush(Context* ctx, const int32_t* gate);
-// k_rsv_views for one KE_RSV_MATCHED pod: the allocate-from-reservation trials `views` on the current device
-// state (synchronous; the segment's device_schedule follows)
 static KArgs make_kargs(const Context* ctx, int64_t now);
+// One view kernel (one workgroup a view) for one pod on the current device state, synchronous: the refresh (the rows /
+// CPU tables as the segment will see them), `pre` (what the device state must hold: its complaint, or nullptr) and
+// `check` of every view (false: `bad_view`), then the views and the pod up, the launch, the outputs back.  The three
+// kinds of view share d_views: each call waits for its own work before it returns.
+template <class View, class Out, class Pre, class Check>
+static int launch_views(Context* ctx, const ke_pod& pod, int64_t now, const std::vector<View>& views, std::vector<Out>& out,
+                        void (*kernel)(SoA, const DevPod*, const View*, Out*, KArgs), Pre pre, Check check,
+                        const char* bad_view) {
+  DeviceState* d = ctx->dev;
+  out.assign(views.size(), Out{});
+  if (views.empty()) return KE_OK;
+  HIP_OK(hipSetDevice(d->device));
+  RC_OK(device_refresh(ctx, now));
+  if (const char* missing = pre(d->soa)) return fail(KE_ERR_DEVICE, missing);
+  for (const View& v : views)
+    if (!check(v)) return fail(KE_ERR_DEVICE, bad_view);
+  const DevPod dp = make_dev_pod(ctx->cfg, pod, pod_hints(*ctx, pod), &ctx->tmpl);
+  const KArgs k = make_kargs(ctx, now);
+  const size_t vb = sizeof(View) * views.size(), ob = sizeof(Out) * views.size();
+  RC_OK(d->d_views.reserve(vb + ob + sizeof(DevPod)));
+  uint8_t* base = d->d_views;
+  HIP_OK(hipMemcpyAsync(base, views.data(), vb, hipMemcpyHostToDevice, d->stream));
+  HIP_OK(hipMemcpyAsync(base + vb + ob, &dp, sizeof(DevPod), hipMemcpyHostToDevice, d->stream));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)views.size()), dim3(64), 0, d->stream, d->soa, (const DevPod*)(base + vb + ob),
+                     (const View*)base, (Out*)(base + vb), k);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(out.data(), base + vb, ob, hipMemcpyDeviceToHost, d->stream));
+  HIP_OK(hipStreamSynchronize(d->stream));
+  return KE_OK;
+}
+
+// k_rsv_views for one KE_RSV_MATCHED pod: the allocate-from-reservation trials `views` (the segment's
+// device_schedule follows)
 int device_rsv_views(Context* ctx, const ke_pod& pod, int64_t now, const std::vector<RsvView>& views,
                      std::vector<RsvViewOut>& out) {
-  DeviceState* d = ctx->dev;
-  out.assign(views.size(), RsvViewOut{});
-  if (views.empty()) return KE_OK;
-  HIP_OK(hipSetDevice(d->device));
-  int rc = device_refresh(ctx, now);  // the rows / CPU tables as the segment will see them
-  if (rc) return rc;
-  for (const RsvView& v : views)
-    if (v.node < 0 || v.node >= ctx->n_nodes) return fail(KE_ERR_DEVICE, "reservation view node out of range");
-  const DevPod dp = make_dev_pod(ctx->cfg, pod, pod_hints(*ctx, pod), &ctx->tmpl);
-  const KArgs k = make_kargs(ctx, now);
-  const size_t vb = sizeof(RsvView) * views.size(), ob = sizeof(RsvViewOut) * views.size();
-  rc = ensure((void**)&d->d_rsv_views, &d->rsv_views_cap, (int64_t)(vb + ob + sizeof(DevPod)));
-  if (rc) return rc;
-  uint8_t* base = (uint8_t*)d->d_rsv_views;
-  HIP_OK(hipMemcpyAsync(base, views.data(), vb, hipMemcpyHostToDevice, d->stream));
-  HIP_OK(hipMemcpyAsync(base + vb + ob, &dp, sizeof(DevPod), hipMemcpyHostToDevice, d->stream));
-  hipLaunchKernelGGL(k_rsv_views, dim3((unsigned)views.size()), dim3(64), 0, d->stream, d->soa,
-                     (const DevPod*)(base + vb + ob), (const RsvView*)base, (RsvViewOut*)(base + vb), k);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out.data(), base + vb, ob, hipMemcpyDeviceToHost, d->stream));
-  HIP_OK(hipStreamSynchronize(d->stream));
-  return KE_OK;
+  const int32_t N = ctx->n_nodes;
+  return launch_views(
+      ctx, pod, now, views, out, k_rsv_views, [](const SoA&) -> const char* { return nullptr; },
+      [N](const RsvView& v) { return v.node >= 0 && v.node < N; }, "reservation view node out of range");
 }
 
-// k_ds_views for one reservation-matched / -ignored DeviceShare pod: its views on the current device state
-// (synchronous, like device_rsv_views)
+// k_ds_views for one reservation-matched / -ignored DeviceShare pod
 int device_ds_views(Context* ctx, const ke_pod& pod, int64_t now, const std::vector<DsView>& views,
                     std::vector<DsViewOut>& out) {
-  DeviceState* d = ctx->dev;
-  out.assign(views.size(), DsViewOut{});
-  if (views.empty()) return KE_OK;
-  HIP_OK(hipSetDevice(d->device));
-  int rc = device_refresh(ctx, now);  // the rows as the segment will see them
-  if (rc) return rc;
-  if (!d->soa.ds) return fail(KE_ERR_DEVICE, "DeviceShare views without a device SoA");
-  for (const DsView& v : views)
-    if (v.node < 0 || v.node >= ctx->n_nodes) return fail(KE_ERR_DEVICE, "DeviceShare view node out of range");
-  const DevPod dp = make_dev_pod(ctx->cfg, pod, pod_hints(*ctx, pod), &ctx->tmpl);
-  const KArgs k = make_kargs(ctx, now);
-  const size_t vb = sizeof(DsView) * views.size(), ob = sizeof(DsViewOut) * views.size();
-  rc = ensure((void**)&d->d_ds_views, &d->ds_views_cap, (int64_t)(vb + ob + sizeof(DevPod)));
-  if (rc) return rc;
-  uint8_t* base = (uint8_t*)d->d_ds_views;
-  HIP_OK(hipMemcpyAsync(base, views.data(), vb, hipMemcpyHostToDevice, d->stream));
-  HIP_OK(hipMemcpyAsync(base + vb + ob, &dp, sizeof(DevPod), hipMemcpyHostToDevice, d->stream));
-  hipLaunchKernelGGL(k_ds_views, dim3((unsigned)views.size()), dim3(64), 0, d->stream, d->soa,
-                     (const DevPod*)(base + vb + ob), (const DsView*)base, (DsViewOut*)(base + vb), k);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out.data(), base + vb, ob, hipMemcpyDeviceToHost, d->stream));
-  HIP_OK(hipStreamSynchronize(d->stream));
-  return KE_OK;
+  const int32_t N = ctx->n_nodes;
+  return launch_views(
+      ctx, pod, now, views, out, k_ds_views,
+      [](const SoA& s) { return s.ds ? nullptr : "DeviceShare views without a device SoA"; },
+      [N](const DsView& v) { return v.node >= 0 && v.node < N; }, "DeviceShare view node out of range");
 }
 
+// k_numa_views for one reservation-matched pod
 int device_numa_views(Context* ctx, const ke_pod& pod, int64_t now, const std::vector<NumaRsvView>& views,
                       std::vector<NumaRsvOut>& out) {
-  DeviceState* d = ctx->dev;
-  out.assign(views.size(), NumaRsvOut{});
-  if (views.empty()) return KE_OK;
-  HIP_OK(hipSetDevice(d->device));
-  int rc = device_refresh(ctx, now);  // the rows as the segment will see them
-  if (rc) return rc;
-  if (!d->soa.nf) return fail(KE_ERR_DEVICE, "NUMA views without a NUMA SoA");
-  for (const NumaRsvView& v : views)
-    if (v.node < 0 || v.node >= ctx->n_nodes || v.n < 0 || v.n > NV_MAX)
-      return fail(KE_ERR_DEVICE, "NUMA view node / trial count out of range");
-  const DevPod dp = make_dev_pod(ctx->cfg, pod, pod_hints(*ctx, pod), &ctx->tmpl);
-  const KArgs k = make_kargs(ctx, now);
-  const size_t vb = sizeof(NumaRsvView) * views.size(), ob = sizeof(NumaRsvOut) * views.size();
-  rc = ensure((void**)&d->d_numa_views, &d->numa_views_cap, (int64_t)(vb + ob + sizeof(DevPod)));
-  if (rc) return rc;
-  uint8_t* base = (uint8_t*)d->d_numa_views;
-  HIP_OK(hipMemcpyAsync(base, views.data(), vb, hipMemcpyHostToDevice, d->stream));
-  HIP_OK(hipMemcpyAsync(base + vb + ob, &dp, sizeof(DevPod), hipMemcpyHostToDevice, d->stream));
-  hipLaunchKernelGGL(k_numa_views, dim3((unsigned)views.size()), dim3(64), 0, d->stream, d->soa,
-                     (const DevPod*)(base + vb + ob), (const NumaRsvView*)base, (NumaRsvOut*)(base + vb), k);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out.data(), base + vb, ob, hipMemcpyDeviceToHost, d->stream));
-  HIP_OK(hipStreamSynchronize(d->stream));
-  return KE_OK;
+  const int32_t N = ctx->n_nodes;
+  return launch_views(
+      ctx, pod, now, views, out, k_numa_views, [](const SoA& s) { return s.nf ? nullptr : "NUMA views without a NUMA SoA"; },
+      [N](const NumaRsvView& v) { return v.node >= 0 && v.node < N && v.n >= 0 && v.n <= NV_MAX; },
+      "NUMA view node / trial count out of range");
 }
 
 // k_rsv_pick's result of the last device_schedule (a segment of one KE_RSV_MATCHED pod)
@@ -7432,42 +7429,24 @@ int device_rsv_gate(const Context* ctx) {
   return d->h_rsv_out.size() >= 5 ? d->h_rsv_out[4] : 0;
 }
 
+// every stream of the context drained before any buffer is freed (~DeviceState: each DevBuf / PinnedVec its own)
 void device_destroy(Context* ctx) {
   DeviceState* d = ctx->dev;
   if (!d) return;
   (void)hipSetDevice(d->device);
-  if (d->stream) (void)hipStreamSynchronize(d->stream);
+  for (hipStream_t s : {d->stream, d->estream, d->estream2})
+    if (s) (void)hipStreamSynchronize(s);
   if (d->comm) (void)ncclCommDestroy(d->comm);
-  void* ptrs[] = {d->soa.f,     d->soa.flags, d->d_rows,      d->d_idx,          d->d_scores,
-                  d->d_cand,    d->d_cand_cnt, d->d_batch_base,
-                  d->d_parity, d->d_best,      d->d_gath,    d->d_split,         d->soa.ds,   d->soa.dsm,
-                  d->d_dsraw,   d->d_dsmax,  d->d_dsrows,       d->soa.nf,   d->soa.nm,
-                  d->d_numarows, d->d_defer, d->d_defer_cnt, d->soa.cs, d->soa.cpu,
-                  d->d_cpurows, d->d_aff, d->soa.qt, d->soa.qm, d->d_stale,
-                  d->d_stale_cnt, d->d_pre, d->d_trows, d->d_tcnt, d->d_parts_done, d->d_scores2, d->d_split2, d->d_chg, d->soa.rec, d->soa.pt, d->soa.kerr,
-                  d->soa.xf, d->soa.xm, d->d_xrows, d->soa.dsx, d->d_ph, d->d_vfo, d->d_rsv, d->d_rsv_out, d->d_rsv_st,
-                  d->d_rsv_views, d->d_ds_views, d->d_numa_views, d->d_rovr, d->d_rsv_gate, d->d_ns_tbl, d->d_nsc_tbl,
-                  d->d_diag};
-  if (d->estream) (void)hipStreamSynchronize(d->estream);
-  if (d->estream2) (void)hipStreamSynchronize(d->estream2);
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
   for (int e = 0; e < DeviceState::EV_RING; e++) {
     if (d->ev_res[e]) (void)hipEventDestroy(d->ev_res[e]);
     if (d->ev_sel[e]) (void)hipEventDestroy(d->ev_sel[e]);
   }
-  if (d->ev_start) (void)hipEventDestroy(d->ev_start);
-  for (hipEvent_t e : d->ev_refresh)
+  for (hipEvent_t e : {d->ev_start, d->ev_refresh[0], d->ev_refresh[1], d->ev_sel2})
     if (e) (void)hipEventDestroy(e);
-  if (d->estream) (void)hipStreamDestroy(d->estream);
-  if (d->estream2) (void)hipStreamDestroy(d->estream2);
-  if (d->ev_sel2) (void)hipEventDestroy(d->ev_sel2);
-  for (CallBufs* c : {&d->call, &d->alt}) {
-    for (auto& e : c->tev) (void)hipEventDestroy(e);
-    for (void* p : {(void*)c->d_pods, (void*)c->d_out, (void*)c->d_devalloc, (void*)c->d_numaalloc, (void*)c->d_cpusets, (void*)c->d_sched})
-      if (p) (void)hipFree(p);
-  }
-  if (d->stream) (void)hipStreamDestroy(d->stream);
+  for (CallBufs* c : {&d->call, &d->alt})
+    for (hipEvent_t e : c->tev) (void)hipEventDestroy(e);
+  for (hipStream_t s : {d->stream, d->estream, d->estream2})
+    if (s) (void)hipStreamDestroy(s);
   delete d;
   ctx->dev = nullptr;
 }
@@ -7475,10 +7454,10 @@ void device_destroy(Context* ctx) {
 // ElasticQuota table -> device (when the host tree changed since the last upload)
 static int device_quota_upload(Context* ctx) {
   DeviceState* d = ctx->dev;
-  if (!d->soa.qt) {
-    HIP_OK(hipMalloc(&d->soa.qt, sizeof(int64_t) * NUM_QF * QT_STRIDE));
-    HIP_OK(hipMalloc(&d->soa.qm, sizeof(int32_t) * QT_STRIDE));
-  }
+  RC_OK(d->d_qt.reserve((size_t)NUM_QF * QT_STRIDE));
+  RC_OK(d->d_qm.reserve(QT_STRIDE));
+  d->soa.qt = d->d_qt;
+  d->soa.qm = d->d_qm;
   std::vector<int64_t> t((size_t)NUM_QF * QT_STRIDE, 0);
   std::vector<int32_t> m(QT_STRIDE, 0xFFFF);  // parent -1, no keys
   for (size_t i = 0; i < ctx->quotas.size(); i++) {
@@ -7544,7 +7523,7 @@ int device_shard_init(Context* ctx, int rank, int world, const uint8_t* id) {
   }
   d->host_fn = nullptr;
   d->host_user = nullptr;
-  if (!d->d_gath) HIP_OK(hipMalloc(&d->d_gath, sizeof(uint32_t) * GATH_WORDS_MAX * MAX_WORLD));
+  RC_OK(d->d_gath.reserve((size_t)GATH_WORDS_MAX * MAX_WORLD));
   HIP_OK(hipMemsetAsync(d->d_gath, 0, sizeof(uint32_t) * GATH_WORDS_MAX * MAX_WORLD, d->stream));
   HIP_OK(hipStreamSynchronize(d->stream));
   d->world = world;
@@ -7617,7 +7596,6 @@ static KArgs make_kargs(const Context* ctx, int64_t now) {
   return k;
 }
 
-constexpr int DS_ROW_WORDS = NUM_DS_FIELDS + NUM_DS_MASKS + NUM_DSX;  // device fields, masks, hint words
 __global__ void k_scatter_ds(SoA s, const int64_t* __restrict__ rows, const int32_t* __restrict__ idx, int n,
                              const int32_t* __restrict__ gate) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -7629,21 +7607,6 @@ __global__ void k_scatter_ds(SoA s, const int64_t* __restrict__ rows, const int3
   for (int w = 0; w < NUM_DSX; w++) s.dsx[w * s.stride + i] = r[NUM_DS_FIELDS + NUM_DS_MASKS + w];
 }
 
-static int ensure_ds(Context* ctx) {
-  DeviceState* d = ctx->dev;
-  if (d->ds_alloc || !ctx->ds_enabled) return KE_OK;
-  HIP_OK(hipMalloc(&d->soa.ds, sizeof(int64_t) * NUM_DS_FIELDS * d->capacity));
-  HIP_OK(hipMalloc(&d->soa.dsm, sizeof(uint64_t) * NUM_DS_MASKS * d->capacity));
-  HIP_OK(hipMemsetAsync(d->soa.ds, 0, sizeof(int64_t) * NUM_DS_FIELDS * d->capacity, d->stream));
-  HIP_OK(hipMemsetAsync(d->soa.dsm, 0, sizeof(uint64_t) * NUM_DS_MASKS * d->capacity, d->stream));
-  HIP_OK(hipMalloc(&d->soa.dsx, sizeof(int64_t) * NUM_DSX * d->capacity));
-  HIP_OK(hipMemsetAsync(d->soa.dsx, 0, sizeof(int64_t) * NUM_DSX * d->capacity, d->stream));
-  d->ds_alloc = true;
-  return KE_OK;
-}
-
-constexpr int NUMA_ROW_WORDS = NUM_NUMA_FIELDS + 1;  // int64 fields + the mask word
-
 __global__ void k_scatter_numa(SoA s, const int64_t* __restrict__ rows, const int32_t* __restrict__ idx, int n,
                              const int32_t* __restrict__ gate) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -7653,21 +7616,6 @@ __global__ void k_scatter_numa(SoA s, const int64_t* __restrict__ rows, const in
   for (int f = 0; f < NUM_NUMA_FIELDS; f++) s.nf[f * s.stride + i] = r[f];
   s.nm[i] = (uint64_t)r[NUM_NUMA_FIELDS];
 }
-
-static int ensure_numa(Context* ctx) {
-  DeviceState* d = ctx->dev;
-  if (d->numa_alloc || !ctx->numa_enabled) return KE_OK;
-  HIP_OK(hipMalloc(&d->soa.nf, sizeof(int64_t) * NUM_NUMA_FIELDS * d->capacity));
-  HIP_OK(hipMalloc(&d->soa.nm, sizeof(uint64_t) * d->capacity));
-  HIP_OK(hipMemsetAsync(d->soa.nf, 0, sizeof(int64_t) * NUM_NUMA_FIELDS * d->capacity, d->stream));
-  HIP_OK(hipMemsetAsync(d->soa.nm, 0, sizeof(uint64_t) * d->capacity, d->stream));
-  d->numa_alloc = true;
-  for (int32_t i = 0; i < ctx->n_nodes; i++)  // rows derived before the NUMA SoA existed
-    if (!ctx->nodes[i].zones.empty()) ctx->nodes[i].dirty = true;
-  return KE_OK;
-}
-
-constexpr int XROW_WORDS = NUM_XF + 1;  // ext row: NUM_XF int64 + the mask
 
 __global__ void k_scatter_ext(SoA s, const int64_t* __restrict__ rows, const int32_t* __restrict__ idx, int n,
                              const int32_t* __restrict__ gate) {
@@ -7679,20 +7627,6 @@ __global__ void k_scatter_ext(SoA s, const int64_t* __restrict__ rows, const int
   s.xm[i] = (uint64_t)r[NUM_XF];
 }
 
-static int ensure_ext(Context* ctx) {
-  DeviceState* d = ctx->dev;
-  if (d->ext_alloc || !ctx->ext_enabled) return KE_OK;
-  HIP_OK(hipMalloc(&d->soa.xf, sizeof(int64_t) * NUM_XF * d->capacity));
-  HIP_OK(hipMalloc(&d->soa.xm, sizeof(uint64_t) * d->capacity));
-  HIP_OK(hipMemsetAsync(d->soa.xf, 0, sizeof(int64_t) * NUM_XF * d->capacity, d->stream));
-  HIP_OK(hipMemsetAsync(d->soa.xm, 0, sizeof(uint64_t) * d->capacity, d->stream));
-  d->ext_alloc = true;
-  for (int32_t i = 0; i < ctx->n_nodes; i++) ctx->nodes[i].dirty = true;
-  return KE_OK;
-}
-
-constexpr int CPU_ROW_WORDS = CPU_SLOTS + NUM_CS_FIELDS;  // records (one int64 each) + summary
-
 __global__ void k_scatter_cpu(SoA s, const int64_t* __restrict__ rows, const int32_t* __restrict__ idx, int n,
                               const int32_t* __restrict__ gate) {
   const int t = blockIdx.x;
@@ -7703,135 +7637,80 @@ __global__ void k_scatter_cpu(SoA s, const int64_t* __restrict__ rows, const int
   if (threadIdx.x < NUM_CS_FIELDS) s.cs[threadIdx.x * s.stride + i] = r[CPU_SLOTS + threadIdx.x];
 }
 
-// The CPU SoA: every node needs its summary words once a cpuset pod is evaluated (the amplified-cpu
-// filter of a binding pod reads the node's ratio even without a CPU table).
-static int ensure_cpu(Context* ctx) {
+static const SideTableDev& side_dev(int t) {
+#define ARR(field, per_node) {offsetof(SoA, field), sizeof(*SoA::field) * (per_node)}
+  static const SideTableDev tables[N_SIDE_TABLES] = {
+    {{ARR(ds, NUM_DS_FIELDS), ARR(dsm, NUM_DS_MASKS), ARR(dsx, NUM_DSX)}, k_scatter_ds, 64, 64},
+    {{ARR(nf, NUM_NUMA_FIELDS), ARR(nm, 1), {}}, k_scatter_numa, 64, 64},
+    {{ARR(xf, NUM_XF), ARR(xm, 1), {}}, k_scatter_ext, 64, 64},
+    {{ARR(cs, NUM_CS_FIELDS), ARR(cpu, CPU_SLOTS), {}}, k_scatter_cpu, CPU_SLOTS, 1},
+  };
+#undef ARR
+  return tables[t];
+}
+
+// The arrays of every side table the context has enabled since the last refresh, zeroed; the rows derived before
+// they existed are marked dirty (before the refresh decides what to scan).
+static int ensure_side_tables(Context* ctx) {
   DeviceState* d = ctx->dev;
-  if (d->cpu_alloc || !ctx->cpu_enabled) return KE_OK;
-  HIP_OK(hipMalloc(&d->soa.cs, sizeof(int64_t) * NUM_CS_FIELDS * d->capacity));
-  HIP_OK(hipMalloc(&d->soa.cpu, sizeof(CpuRec) * CPU_SLOTS * d->capacity));
-  HIP_OK(hipMemsetAsync(d->soa.cs, 0, sizeof(int64_t) * NUM_CS_FIELDS * d->capacity, d->stream));
-  HIP_OK(hipMemsetAsync(d->soa.cpu, 0, sizeof(CpuRec) * CPU_SLOTS * d->capacity, d->stream));
-  d->cpu_alloc = true;
-  for (int32_t i = 0; i < ctx->n_nodes; i++)
-    if (ctx->nodes[i].valid) ctx->nodes[i].dirty = true;
+  for (int t = 0; t < N_SIDE_TABLES; t++) {
+    if (d->has((SideTable)t) || !(ctx->*side_table(t).enabled)) continue;
+    for (int a = 0; a < SIDE_ARRAYS; a++) {
+      const auto& arr = side_dev(t).arr[a];
+      if (!arr.node_bytes) continue;
+      RC_OK(d->side[t][a].reserve_zeroed(arr.node_bytes * (size_t)d->capacity, d->stream));
+      void* const p = d->side[t][a];
+      std::memcpy(reinterpret_cast<char*>(&d->soa) + arr.soa_offset, &p, sizeof(p));
+    }
+    if (const auto first_dirty = side_table(t).first_dirty)
+      for (int32_t i = 0; i < ctx->n_nodes; i++)
+        if (first_dirty(ctx->nodes[i])) ctx->nodes[i].dirty = true;
+  }
   return KE_OK;
+}
+
+static void scatter_launch(DeviceState* d, const Scatter& sc, const int32_t* gate) {
+  if (sc.table == ST_BASE) {
+    hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)((sc.n + 255) / 256)), dim3(256), 0, d->stream, d->soa,
+                       reinterpret_cast<const Row*>(sc.rows), sc.idx, sc.n, d->deferred_k, gate);
+    return;
+  }
+  const SideTableDev& t = side_dev(sc.table);
+  hipLaunchKernelGGL(t.scatter, dim3((unsigned)((sc.n + t.nodes_per_block - 1) / t.nodes_per_block)), dim3(t.block), 0,
+                     d->stream, d->soa, sc.rows, sc.idx, sc.n, gate);
 }
 
 // Re-derive rows of dirty / time-expired nodes and scatter them into the SoA.
 int device_refresh(Context* ctx, int64_t now, bool defer) {
   DeviceState* d = ctx->dev;
-  d->deferred.clear();
-  int rc = ensure_ds(ctx);  // (first use marks the nodes dirty: before the checks below)
-  if (rc) return rc;
-  rc = ensure_numa(ctx);
-  if (rc) return rc;
-  rc = ensure_cpu(ctx);
-  if (rc) return rc;
-  rc = ensure_ext(ctx);
-  if (rc) return rc;
-  // nothing marked dirty since every row was last clean, and no row expired: no scan over the nodes; no row
-  // expired and the same nodes: only the dirty list (the nodes marked since)
-  const bool no_expiry = now < ctx->min_valid_until && ctx->n_nodes == ctx->clean_n_nodes;
-  const bool all_clean = no_expiry && g_dirty_epoch.load(std::memory_order_relaxed) == ctx->clean_epoch;
-  const bool incremental = !all_clean && no_expiry;
-  if (!all_clean) mirror_join(*ctx);  // a row may be derived: the host mirror on its thread first
-  if (!all_clean && !ctx->pending.empty()) {  // a row to derive needs the deferred host mirror first
-    bool any = false;
-    if (incremental)
-      for (int32_t i : ctx->dirty_list) any = any || (i < ctx->n_nodes && ctx->nodes[i].dirty);
-    else
-      for (int32_t i = 0; i < ctx->n_nodes && !any; i++) any = ctx->nodes[i].dirty || now >= ctx->nodes[i].valid_until;
-    if (any) flush_mirror(*ctx);
-  }
+  d->n_deferred = 0;
+  RC_OK(ensure_side_tables(ctx));
   if (ctx->ptab_dirty) {  // GPU partition tables (ke_node_gpu_partitions); the pool only grows
-    if (d->pt_words < ctx->ptab.size()) {
-      if (d->soa.pt) HIP_OK(hipFree(d->soa.pt));
-      const size_t cap = std::max(ctx->ptab.size(), (size_t)16 * PT_WORDS);
-      HIP_OK(hipMalloc(&d->soa.pt, sizeof(uint64_t) * cap));
-      d->pt_words = cap;
-    }
-    HIP_OK(hipMemcpyAsync(d->soa.pt, ctx->ptab.data(), sizeof(uint64_t) * ctx->ptab.size(), hipMemcpyHostToDevice,
+    RC_OK(d->d_pt.reserve(std::max(ctx->ptab.size(), (size_t)16 * PT_WORDS)));
+    d->soa.pt = d->d_pt;
+    HIP_OK(hipMemcpyAsync(d->d_pt, ctx->ptab.data(), sizeof(uint64_t) * ctx->ptab.size(), hipMemcpyHostToDevice,
                           d->stream));
     HIP_OK(hipStreamSynchronize(d->stream));
     ctx->ptab_dirty = false;
   }
-  std::vector<int64_t> crows;  // CPU tables + summaries of the dirty nodes
-  std::vector<int32_t> cidx;
-  std::vector<Row> rows;
-  std::vector<int32_t> idx;
-  std::vector<int64_t> dsrows;  // DeviceShare rows of the dirty nodes (the device state is not time-dependent)
-  std::vector<int32_t> dsidx;
-  std::vector<int64_t> nrows;  // NUMA rows of the dirty nodes
-  std::vector<int32_t> nidx;
-  std::vector<int64_t> xrows;  // ext rows of the dirty nodes
-  std::vector<int32_t> xidx;
-  int64_t mvu = incremental ? ctx->min_valid_until : INT64_MAX;
-  std::vector<int32_t> visit;
-  if (incremental) {
-    visit.swap(ctx->dirty_list);  // (flush_mirror above may have appended; a repeated node is clean the 2nd time)
-  }
-  const int32_t n_visit = all_clean ? 0 : incremental ? (int32_t)visit.size() : ctx->n_nodes;
-  for (int32_t v = 0; v < n_visit; v++) {
-    const int32_t i = incremental ? visit[(size_t)v] : v;
-    if (i >= ctx->n_nodes) continue;
-    NodeState& ns = ctx->nodes[i];
-    if (!ns.dirty && now < ns.valid_until) {
-      mvu = std::min(mvu, ns.valid_until);
-      continue;
-    }
-    Row r;
-    int64_t vu;
-    derive_row(ctx->cfg, ns, now, &r, &vu);
-    if (ns.dirty && d->ds_alloc) {
-      const size_t o = dsrows.size();
-      dsrows.resize(o + DS_ROW_WORDS);
-      derive_ds_row(ns, &dsrows[o], reinterpret_cast<uint64_t*>(&dsrows[o + NUM_DS_FIELDS]));
-      derive_dsx_row(ns, &dsrows[o + NUM_DS_FIELDS + NUM_DS_MASKS]);
-      dsidx.push_back(i);
-    }
-    if (ns.dirty && d->numa_alloc) {
-      const size_t o = nrows.size();
-      nrows.resize(o + NUMA_ROW_WORDS);
-      uint64_t mask;
-      derive_numa_row(ns, &nrows[o], &mask);
-      nrows[o + NUM_NUMA_FIELDS] = (int64_t)mask;
-      nidx.push_back(i);
-    }
-    if (ns.dirty && d->ext_alloc) {
-      const size_t o = xrows.size();
-      xrows.resize(o + XROW_WORDS);
-      uint64_t mask;
-      derive_ext_row(ctx->cfg, ns, &xrows[o], &mask);
-      xrows[o + NUM_XF] = (int64_t)mask;
-      xidx.push_back(i);
-    }
-    if (ns.dirty && d->cpu_alloc) {
-      const size_t o = crows.size();
-      crows.resize(o + CPU_ROW_WORDS);
-      derive_cpu_rows(ns, reinterpret_cast<CpuRec*>(&crows[o]), &crows[o + CPU_SLOTS]);
-      cidx.push_back(i);
-    }
-    ns.valid_until = vu;
-    ns.dirty = false;
-    mvu = std::min(mvu, vu);
-    rows.push_back(r);
-    idx.push_back(i);
-  }
-  if (!all_clean) {
-    ctx->clean_epoch = g_dirty_epoch.load(std::memory_order_relaxed);
-    ctx->min_valid_until = mvu;
-    ctx->clean_n_nodes = ctx->n_nodes;
-    ctx->dirty_list.clear();  // every node < n_nodes is clean now
-  }
+  bool exists[N_SIDE_TABLES];
+  for (int t = 0; t < N_SIDE_TABLES; t++) exists[t] = d->has((SideTable)t);
+  RefreshBatch batch;
+  refresh_scan(*ctx, now, exists, &batch);
   // every table's rows and indices go through one page-locked staging area: async copies and scatters on the
-  // stream, one synchronisation at the end (the staging is reused by the next refresh)
+  // stream, no synchronisation (the staging is reused by the refresh after the next)
   static_assert(sizeof(Row) % sizeof(int64_t) == 0, "Row staged in int64 words");
   auto words = [](size_t bytes) { return (bytes + sizeof(int64_t) - 1) / sizeof(int64_t); };
-  const size_t total = dsrows.size() + words(sizeof(int32_t) * dsidx.size()) + nrows.size() +
-                       words(sizeof(int32_t) * nidx.size()) + xrows.size() + words(sizeof(int32_t) * xidx.size()) +
-                       crows.size() + words(sizeof(int32_t) * cidx.size()) + words(sizeof(Row) * rows.size()) +
-                       words(sizeof(int32_t) * idx.size());
+  struct Up {
+    const void* rows;
+    size_t row_words;
+    const std::vector<int32_t>* idx;
+  } up[N_SIDE_TABLES + 1];  // the side tables, then the node rows: the order of their copies and scatters
+  for (int t = 0; t < N_SIDE_TABLES; t++)
+    up[t] = {batch.side[t].rows.data(), (size_t)side_table(t).row_words, &batch.side[t].idx};
+  up[ST_BASE] = {batch.rows.data(), sizeof(Row) / sizeof(int64_t), &batch.idx};
+  size_t total = 0;
+  for (const Up& u : up) total += u.row_words * u.idx->size() + words(sizeof(int32_t) * u.idx->size());
   if (total == 0) return KE_OK;
   // the staging of the refresh before the previous one: its copies are done before it is reused (two refreshes in a
   // row -- a fused matched pod's -- do not wait for each other)
@@ -7842,88 +7721,21 @@ int device_refresh(Context* ctx, int64_t now, bool defer) {
   }
   PinnedVec<int64_t>& hstage = d->h_refresh[cur];
   if (!hstage.resize(total)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the row staging");
-  size_t at = 0;
-  auto stage = [&](const void* src, size_t bytes) {  // -> the staged copy
-    void* dst = hstage.data() + at;
-    if (bytes) std::memcpy(dst, src, bytes);
-    at += words(bytes);
-    return dst;
-  };
-  // one table: rows (row_words int64 per node) + indices into its device staging buffer, then its scatter
-  auto table = [&](int64_t** dbuf, int64_t* cap, const std::vector<int64_t>& hrows, const std::vector<int32_t>& hidx,
-                   int64_t row_words, int32_t** didx) -> int {
-    const int64_t n = (int64_t)hidx.size();
-    if (*cap < n) {
-      if (*dbuf) HIP_OK(hipFree(*dbuf));
-      HIP_OK(hipMalloc(dbuf, sizeof(int64_t) * row_words * n + sizeof(int32_t) * n));
-      *cap = n;
-    }
-    *didx = reinterpret_cast<int32_t*>(*dbuf + row_words * n);
-    HIP_OK(hipMemcpyAsync(*dbuf, stage(hrows.data(), sizeof(int64_t) * hrows.size()), sizeof(int64_t) * hrows.size(),
-                          hipMemcpyHostToDevice, d->stream));
-    HIP_OK(hipMemcpyAsync(*didx, stage(hidx.data(), sizeof(int32_t) * n), sizeof(int32_t) * n, hipMemcpyHostToDevice,
-                          d->stream));
-    return KE_OK;
-  };
-  int32_t* didx = nullptr;
-  if (!dsidx.empty()) {
-    const int n = (int)dsidx.size();
-    rc = table(&d->d_dsrows, &d->ds_staging_cap, dsrows, dsidx, DS_ROW_WORDS, &didx);
-    if (rc) return rc;
-    const int64_t* rows = d->d_dsrows;
-    d->deferred.push_back([=](const int32_t* gate) {
-      hipLaunchKernelGGL(k_scatter_ds, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, d->stream, d->soa, rows, didx, n, gate);
-    });
-  }
-  if (!nidx.empty()) {
-    const int n = (int)nidx.size();
-    rc = table(&d->d_numarows, &d->numa_staging_cap, nrows, nidx, NUMA_ROW_WORDS, &didx);
-    if (rc) return rc;
-    const int64_t* rows = d->d_numarows;
-    d->deferred.push_back([=](const int32_t* gate) {
-      hipLaunchKernelGGL(k_scatter_numa, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, d->stream, d->soa, rows, didx, n, gate);
-    });
-  }
-  if (!xidx.empty()) {
-    const int n = (int)xidx.size();
-    rc = table(&d->d_xrows, &d->ext_staging_cap, xrows, xidx, XROW_WORDS, &didx);
-    if (rc) return rc;
-    const int64_t* rows = d->d_xrows;
-    d->deferred.push_back([=](const int32_t* gate) {
-      hipLaunchKernelGGL(k_scatter_ext, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, d->stream, d->soa, rows, didx, n, gate);
-    });
-  }
-  if (!cidx.empty()) {
-    const int n = (int)cidx.size();
-    rc = table(&d->d_cpurows, &d->cpu_staging_cap, crows, cidx, CPU_ROW_WORDS, &didx);
-    if (rc) return rc;
-    const int64_t* rows = d->d_cpurows;
-    d->deferred.push_back([=](const int32_t* gate) {
-      hipLaunchKernelGGL(k_scatter_cpu, dim3((unsigned)n), dim3(CPU_SLOTS), 0, d->stream, d->soa, rows, didx, n, gate);
-    });
-  }
-  if (!rows.empty()) {
-    HIP_OK(hipSetDevice(d->device));
-    const int64_t n = (int64_t)rows.size();
-    if (d->staging_cap < n) {
-      if (d->d_rows) HIP_OK(hipFree(d->d_rows));
-      if (d->d_idx) HIP_OK(hipFree(d->d_idx));
-      HIP_OK(hipMalloc(&d->d_rows, sizeof(Row) * n));
-      HIP_OK(hipMalloc(&d->d_idx, sizeof(int32_t) * n));
-      d->staging_cap = n;
-    }
-    HIP_OK(hipMemcpyAsync(d->d_rows, stage(rows.data(), sizeof(Row) * n), sizeof(Row) * n, hipMemcpyHostToDevice,
-                          d->stream));
-    HIP_OK(hipMemcpyAsync(d->d_idx, stage(idx.data(), sizeof(int32_t) * n), sizeof(int32_t) * n, hipMemcpyHostToDevice,
-                          d->stream));
-    const Row* rows_d = d->d_rows;
-    const int32_t* idx_d = d->d_idx;
-    const KArgs ka = make_kargs(ctx, now);
-    const int nn = (int)n;
-    d->deferred.push_back([=](const int32_t* gate) {
-      hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, d->stream, d->soa, rows_d, idx_d,
-                         nn, ka, gate);
-    });
+  int64_t* at = hstage.data();
+  d->deferred_k = make_kargs(ctx, now);
+  for (int t = 0; t <= ST_BASE; t++) {
+    const Up& u = up[t];
+    const size_t n = u.idx->size(), rw = u.row_words * n, iw = words(sizeof(int32_t) * n);
+    if (!n) continue;
+    // its rows and, behind them, their node indices: staged alike on the host and in the table's device buffer
+    DevBuf<int64_t>& dbuf = d->d_stage[t];
+    RC_OK(dbuf.reserve(rw + iw));
+    std::memcpy(at, u.rows, sizeof(int64_t) * rw);
+    std::memcpy(at + rw, u.idx->data(), sizeof(int32_t) * n);
+    HIP_OK(hipMemcpyAsync(dbuf, at, sizeof(int64_t) * rw, hipMemcpyHostToDevice, d->stream));
+    HIP_OK(hipMemcpyAsync(dbuf + rw, at + rw, sizeof(int32_t) * n, hipMemcpyHostToDevice, d->stream));
+    at += rw + iw;
+    d->deferred[d->n_deferred++] = Scatter{t, dbuf, reinterpret_cast<const int32_t*>(dbuf + rw), (int)n};
   }
   // defer (a fused reservation-matched pod): the copies are on the stream, the scatters wait for
   // device_refresh_flush -- behind the segment's plain pods, gated by their k_rsv_check
@@ -7933,9 +7745,9 @@ int device_refresh(Context* ctx, int64_t now, bool defer) {
 
 int device_refresh_flush(Context* ctx, const int32_t* gate) {
   DeviceState* d = ctx->dev;
-  if (d->deferred.empty()) return KE_OK;
-  for (auto& f : d->deferred) f(gate);
-  d->deferred.clear();
+  if (!d->n_deferred) return KE_OK;
+  for (int i = 0; i < d->n_deferred; i++) scatter_launch(d, d->deferred[i], gate);
+  d->n_deferred = 0;
   HIP_OK(hipGetLastError());
   // no host wait: the staging is reused only after ev_refresh (above), and the kernels reading the rows run on
   // `stream` after the scatters or wait for an event recorded there after them (device_schedule_enqueue's ev_start)
@@ -7944,81 +7756,63 @@ int device_refresh_flush(Context* ctx, const int32_t* gate) {
   return KE_OK;
 }
 
-// The device copy of the node-set table brought up to date for a call that carries set ids: rows
-// 0 .. ns_n of capacity / 64 words -- row 0 all ones (id 0: every node), row s the words of set s below the node
-// capacity, zero beyond words_per_set -- so a kernel's lookup of any (id, node < capacity) is in bounds without a
-// branch.  A reload uploads the table, ke_node_set_bits' patches their word columns.  The table only changes with
-// no call in flight (the entry points that change it complete them first).
-static int node_sets_sync(Context* ctx) {
-  DeviceState* d = ctx->dev;
-  const int64_t W = d->capacity / 64, wps = ctx->ns_wps, cw = std::min<int64_t>(W, wps);
-  const int64_t rows = (int64_t)ctx->ns_n + 1;
-  if (ctx->ns_dirty || !d->d_ns_tbl) {
-    std::vector<uint64_t> t((size_t)(rows * W), 0ull);
-    std::fill(t.begin(), t.begin() + W, ~0ull);
-    for (int64_t r = 0; r + 1 < rows; r++)
-      std::copy(ctx->ns_bits.begin() + r * wps, ctx->ns_bits.begin() + r * wps + cw, t.begin() + (r + 1) * W);
-    const int rc = ensure((void**)&d->d_ns_tbl, &d->ns_tbl_cap, (int64_t)sizeof(uint64_t) * rows * W);
-    if (rc) return rc;
-    HIP_OK(hipMemcpyAsync(d->d_ns_tbl, t.data(), sizeof(uint64_t) * t.size(), hipMemcpyHostToDevice, d->stream));
+// The device copy of a per-pod id table brought up to date (`tbl`): rows 0 .. n_src of `stride` elements -- row 0
+// `row0` throughout (id 0), row r the first min(stride, src_stride) elements of the host table's row r - 1 (src_stride
+// a row), zero beyond -- so a kernel's lookup of any (id, column < stride) is in bounds without a branch.  `reload`
+// (or no device copy yet) uploads the table; else the columns in `dirty_cols` go up as one strided copy each.  Such a
+// table only changes with no call in flight (the entry points that change it complete them first).
+template <typename T>
+static int id_table_sync(DeviceState* d, DevBuf<T>& tbl, int64_t n_src, int64_t stride, T row0, const std::vector<T>& src,
+                         int64_t src_stride, bool reload, std::vector<int32_t>& dirty_cols) {
+  const int64_t rows = n_src + 1, cols = std::min(stride, src_stride);
+  if (reload || !tbl) {
+    std::vector<T> t((size_t)(rows * stride), T(0));
+    std::fill(t.begin(), t.begin() + stride, row0);
+    for (int64_t r = 0; r < n_src; r++)
+      std::copy(src.begin() + r * src_stride, src.begin() + r * src_stride + cols, t.begin() + (r + 1) * stride);
+    RC_OK(tbl.reserve(t.size()));
+    HIP_OK(hipMemcpyAsync(tbl, t.data(), sizeof(T) * t.size(), hipMemcpyHostToDevice, d->stream));
     HIP_OK(hipStreamSynchronize(d->stream));
-  } else if (!ctx->ns_dirty_words.empty() && rows > 1) {
-    std::vector<int32_t>& dw = ctx->ns_dirty_words;
-    std::sort(dw.begin(), dw.end());
-    dw.erase(std::unique(dw.begin(), dw.end()), dw.end());
-    std::vector<uint64_t> col((size_t)(rows - 1) * dw.size());
+  } else if (!dirty_cols.empty() && n_src > 0) {
+    std::sort(dirty_cols.begin(), dirty_cols.end());
+    dirty_cols.erase(std::unique(dirty_cols.begin(), dirty_cols.end()), dirty_cols.end());
+    std::vector<T> col((size_t)n_src * dirty_cols.size());
     size_t q = 0;
-    for (int32_t w : dw) {
-      if (w >= cw) continue;
-      uint64_t* cq = col.data() + (q++) * (size_t)(rows - 1);
-      for (int64_t r = 0; r + 1 < rows; r++) cq[r] = ctx->ns_bits[(size_t)(r * wps + w)];
-      HIP_OK(hipMemcpy2DAsync(d->d_ns_tbl + W + w, sizeof(uint64_t) * W, cq, sizeof(uint64_t), sizeof(uint64_t),
-                              (size_t)(rows - 1), hipMemcpyHostToDevice, d->stream));
+    for (int32_t c : dirty_cols) {
+      if (c >= cols) continue;
+      T* cq = col.data() + (q++) * (size_t)n_src;
+      for (int64_t r = 0; r < n_src; r++) cq[r] = src[(size_t)(r * src_stride + c)];
+      HIP_OK(hipMemcpy2DAsync(tbl + stride + c, sizeof(T) * stride, cq, sizeof(T), sizeof(T), (size_t)n_src,
+                              hipMemcpyHostToDevice, d->stream));
     }
     HIP_OK(hipStreamSynchronize(d->stream));
   }
+  dirty_cols.clear();
+  return KE_OK;
+}
+
+// The node-set table for a call that carries set ids: capacity / 64 words a row, row 0 all ones (id 0:
+// every node), row s the words of set s.  A reload uploads the table, ke_node_set_bits' patches their word columns.
+static int node_sets_sync(Context* ctx) {
+  DeviceState* d = ctx->dev;
+  const int64_t W = d->capacity / 64;
+  RC_OK(id_table_sync(d, d->d_ns_tbl, ctx->ns_n, W, ~(uint64_t)0, ctx->ns_bits, ctx->ns_wps, ctx->ns_dirty, ctx->ns_dirty_words));
   ctx->ns_dirty = false;
-  ctx->ns_dirty_words.clear();
   d->soa.ns_tbl = d->d_ns_tbl;
   d->soa.ns_wps = (int32_t)W;
   return KE_OK;
 }
 
-// The device copy of the score offset table brought up to date for a call that carries table ids:
-// rows 0 .. nsc_n of `capacity` uint16 entries (a multiple of 256, so a wave's 64 entries are 128 aligned bytes) --
-// row 0 all zero (id 0: no offset), row t the entries of table t below the node capacity, zero at and beyond the
-// table's n_nodes -- so a lookup of any (id, node < capacity) is in bounds without a branch.  A reload uploads the
-// table, ke_node_scores_set's patches one strided column copy per node.  As the set table, it only changes with no
-// call in flight.
+// The score offset table for a call that carries table ids: `capacity` uint16 entries a row (a
+// multiple of 256, so a wave's 64 entries are 128 aligned bytes), row 0 all zero (id 0: no offset), row t the entries
+// of table t, zero at and beyond the table's n_nodes.  A reload uploads the table, ke_node_scores_set's patches one
+// strided column copy per node.
 static int node_scores_sync(Context* ctx) {
   DeviceState* d = ctx->dev;
-  const int64_t S = d->capacity, nn = ctx->nsc_nodes, cn = std::min<int64_t>(S, nn);
-  const int64_t rows = (int64_t)ctx->nsc_n + 1;
-  if (ctx->nsc_dirty || !d->d_nsc_tbl) {
-    std::vector<uint16_t> t((size_t)(rows * S), (uint16_t)0);
-    for (int64_t r = 0; r + 1 < rows; r++)
-      std::copy(ctx->nsc_vals.begin() + r * nn, ctx->nsc_vals.begin() + r * nn + cn, t.begin() + (r + 1) * S);
-    const int rc = ensure((void**)&d->d_nsc_tbl, &d->nsc_tbl_cap, (int64_t)sizeof(uint16_t) * rows * S);
-    if (rc) return rc;
-    HIP_OK(hipMemcpyAsync(d->d_nsc_tbl, t.data(), sizeof(uint16_t) * t.size(), hipMemcpyHostToDevice, d->stream));
-    HIP_OK(hipStreamSynchronize(d->stream));
-  } else if (!ctx->nsc_dirty_nodes.empty() && rows > 1) {
-    std::vector<int32_t>& dn = ctx->nsc_dirty_nodes;
-    std::sort(dn.begin(), dn.end());
-    dn.erase(std::unique(dn.begin(), dn.end()), dn.end());
-    std::vector<uint16_t> col((size_t)(rows - 1) * dn.size());
-    size_t q = 0;
-    for (int32_t i : dn) {
-      if (i >= cn) continue;
-      uint16_t* cq = col.data() + (q++) * (size_t)(rows - 1);
-      for (int64_t r = 0; r + 1 < rows; r++) cq[r] = ctx->nsc_vals[(size_t)(r * nn + i)];
-      HIP_OK(hipMemcpy2DAsync(d->d_nsc_tbl + S + i, sizeof(uint16_t) * S, cq, sizeof(uint16_t), sizeof(uint16_t),
-                              (size_t)(rows - 1), hipMemcpyHostToDevice, d->stream));
-    }
-    HIP_OK(hipStreamSynchronize(d->stream));
-  }
+  const int64_t S = d->capacity;
+  RC_OK(id_table_sync(d, d->d_nsc_tbl, ctx->nsc_n, S, (uint16_t)0, ctx->nsc_vals, ctx->nsc_nodes, ctx->nsc_dirty,
+                      ctx->nsc_dirty_nodes));
   ctx->nsc_dirty = false;
-  ctx->nsc_dirty_nodes.clear();
   d->soa.nsc_tbl = d->d_nsc_tbl;
   d->soa.nsc_stride = (int32_t)S;
   return KE_OK;
@@ -8056,8 +7850,8 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t
     }
   }
   const int64_t bytes = sizeof(DevPod) * (int64_t)n_pods + sizeof(int32_t) * (ns_words + tail_words);
-  int rc = ensure((void**)&d->call.d_pods, &d->call.pods_cap, std::max<int64_t>(bytes, (int64_t)sizeof(DevPod)));
-  if (rc) return rc;
+  // (whole records: the id and tail words round up)
+  RC_OK(d->call.d_pods.reserve((size_t)std::max<int64_t>((bytes + (int64_t)sizeof(DevPod) - 1) / (int64_t)sizeof(DevPod), 1)));
   int32_t* const h_words = reinterpret_cast<int32_t*>(dp.data() + n_pods);
   d->soa.ns_ids = nullptr;
   if (ns || sc) {
@@ -8072,8 +7866,7 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t
     if (copies) ++*copies;
   }
   if (!ph.empty()) {
-    rc = ensure((void**)&d->d_ph, &d->ph_cap, sizeof(DevPodHint) * (int64_t)ph.size());
-    if (rc) return rc;
+    RC_OK(d->d_ph.reserve(ph.size()));
     HIP_OK(hipMemcpyAsync(d->d_ph, ph.data(), sizeof(DevPodHint) * ph.size(), hipMemcpyHostToDevice, d->stream));
     if (copies) ++*copies;
   }
@@ -8207,10 +8000,8 @@ struct DeferBufs {
 };
 // room for at most `max_pairs` deferred pairs at a time and `n_counters` counters (the caller zeroes the counters)
 static int defer_ensure(DeviceState* d, int64_t max_pairs, int64_t n_counters, DeferBufs* out) {
-  int rc = ensure((void**)&d->d_defer, &d->defer_cap, (sizeof(uint64_t) + sizeof(uint32_t)) * max_pairs);
-  if (rc) return rc;
-  rc = ensure((void**)&d->d_defer_cnt, &d->defer_cnt_cap, sizeof(uint32_t) * n_counters);
-  if (rc) return rc;
+  RC_OK(d->d_defer.reserve((size_t)(max_pairs + (max_pairs + 1) / 2)));  // a pair, and its uint32 merge word
+  RC_OK(d->d_defer_cnt.reserve((size_t)n_counters));
   *out = DeferBufs{d->d_defer, reinterpret_cast<uint32_t*>(d->d_defer + max_pairs), d->d_defer_cnt};
   return KE_OK;
 }
@@ -8247,8 +8038,8 @@ static int pair_pass_begin(Context* ctx, int32_t n_pods, const ke_pod* pods, int
   HIP_OK(hipMemsetAsync(d->soa.kerr, 0, sizeof(int32_t), d->stream));
   pp->k = make_kargs(ctx, now);
   for (const DevPod& q : d->call.host_pods) pp->cpu = pp->cpu || (q.flags & PF_CPUSET);
-  if (pp->cpu && !d->cpu_alloc) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
-  pp->numa = d->numa_alloc;
+  if (pp->cpu && !d->has(ST_CPU)) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
+  pp->numa = d->has(ST_NUMA);
   if (pp->numa && ctx->n_nodes > 0) {  // every pair may be deferred
     if ((rc = defer_ensure(d, (int64_t)ctx->n_nodes * n_pods, 1, &pp->defer))) return rc;
     HIP_OK(hipMemsetAsync(pp->defer.cnt, 0, sizeof(uint32_t), d->stream));
@@ -8278,12 +8069,10 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
   if (rc || n_pods == 0) return rc;
   const int64_t N = ctx->n_nodes, P = n_pods, M = N * P;
   // parity buffers: status u8, reason u8, la / numa / ds / total i16 = 10 B per pair
-  rc = ensure(&d->d_parity, &d->parity_cap, std::max<int64_t>(M, 1) * 10 + 16);
-  if (rc) return rc;
-  rc = ensure((void**)&d->d_best, &d->best_cap, sizeof(uint32_t) * 2 * P);  // best key + dsmax per pod
-  if (rc) return rc;
+  RC_OK(d->d_parity.reserve((size_t)(std::max<int64_t>(M, 1) * 10 + 16)));
+  RC_OK(d->d_best.reserve((size_t)(2 * P)));  // best key + dsmax per pod
   ParityOut po{};
-  po.status = (uint8_t*)d->d_parity;
+  po.status = d->d_parity;
   po.reason = po.status + M;
   po.la = (int16_t*)(po.reason + M + (M & 1));
   po.numa = po.la + M;
@@ -8336,14 +8125,13 @@ int device_diagnose(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t no
   const int64_t wpp = n_bits ? words_per_pod : 0;
   static_assert(sizeof(uint32_t) * DIAG_WORDS % sizeof(uint64_t) == 0, "the bitmaps behind the tallies are 8-byte aligned");
   const int64_t tally_bytes = (int64_t)sizeof(uint32_t) * DIAG_WORDS * P, bits_bytes = (int64_t)sizeof(uint64_t) * P * wpp;
-  rc = ensure(&d->d_diag, &d->diag_cap, tally_bytes + n_bits * bits_bytes);
-  if (rc) return rc;
+  RC_OK(d->d_diag.reserve((size_t)(tally_bytes + n_bits * bits_bytes)));
   DiagOut dg{};
-  dg.tally = (uint32_t*)d->d_diag;
+  dg.tally = reinterpret_cast<uint32_t*>(d->d_diag.get());
   dg.wpp = (int32_t)wpp;
   uint64_t* d_bits[DIAG_BITMAPS] = {nullptr, nullptr, nullptr};
   {
-    uint64_t* next = reinterpret_cast<uint64_t*>((uint8_t*)d->d_diag + tally_bytes);
+    uint64_t* next = reinterpret_cast<uint64_t*>(d->d_diag + tally_bytes);
     for (int c = 0; c < DIAG_BITMAPS; c++)
       if (bits[c]) d_bits[c] = next, next += P * wpp;
   }
@@ -8379,7 +8167,7 @@ int device_diagnose(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t no
 // outputs, stamps, hand-off words, readback staging and events are per call).
 void device_swap_call_buffers(Context* ctx) {
   DeviceState* d = ctx->dev;
-  d->call.swap(d->alt);
+  std::swap(d->call, d->alt);
 }
 
 // a failed enqueue may have left part of its launches on the streams: wait for every stream of the context
@@ -8404,7 +8192,7 @@ bool device_refresh_pending(const Context* ctx, int64_t now) {
 // host round trip between its launches: it may be submitted behind a call in flight
 bool device_async_ok(const Context* ctx, int32_t n_pods) {
   const DeviceState* d = ctx->dev;
-  if (!d || d->world > 1 || d->comm || d->host_fn || !d->pipeline || d->numa_alloc || !ctx->quotas.empty() || ctx->n_nodes <= 0)
+  if (!d || d->world > 1 || d->comm || d->host_fn || !d->pipeline || d->has(ST_NUMA) || !ctx->quotas.empty() || ctx->n_nodes <= 0)
     return false;
   if (ctx->n_bind_nodes > 0 || !ctx->rsv_pairs.empty() || ctx->rsv_affinity || !ctx->rsv_ovr.empty()) return false;
   if ((int64_t)ctx->staged.size() != n_pods) return false;
@@ -8594,7 +8382,7 @@ struct ScheduleCall {
 
   ScheduleCall(Context* ctx_, int32_t n, const ke_pod* p, bool ws)
       : ctx(ctx_), d(ctx_->dev), c(d->call), n_pods(n), pods(p), want_score(ws), N(ctx_->n_nodes), fused(ctx_->rsv_fused),
-        numa(d->numa_alloc), quota(!ctx_->quotas.empty()), sharded(d->world > 1 || d->comm || d->host_fn),
+        numa(d->has(ST_NUMA)), quota(!ctx_->quotas.empty()), sharded(d->world > 1 || d->comm || d->host_fn),
         matched(!ctx_->rsv_pairs.empty() || ctx_->rsv_affinity),
         ns(ctx_->nsc_call ? NS_SCORES : ctx_->ns_call ? NS_SETS : 0) {}
 
@@ -8628,7 +8416,7 @@ struct ScheduleCall {
     ctx->last_ds_cuts = 0;
     batches = plan_batches(c.host_pods.data(), n_pods, ctx->cfg.pod_batch, !sharded && !numa && N > 0, fused);
     for (const Batch& b : batches) any_cpu = any_cpu || b.cpu;
-    if (any_cpu && !d->cpu_alloc) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
+    if (any_cpu && !d->has(ST_CPU)) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
     n_batches = (int)batches.size();
     bases = plan_bases(batches);
     run_end = plan_runs(batches, d->pipeline, N, numa, fused);
@@ -8657,18 +8445,10 @@ struct ScheduleCall {
   // the call's output buffers, grown when needed, and what only some calls have (VF ranks, NUMA allocations)
   int buffers() {
     int rc;
-    if (c.out_cap < n_pods) {
-      if (c.d_out) HIP_OK(hipFree(c.d_out));
-      if (c.d_devalloc) HIP_OK(hipFree(c.d_devalloc));
-      if (c.d_numaalloc) HIP_OK(hipFree(c.d_numaalloc));
-      c.d_out = nullptr;
-      c.d_devalloc = nullptr;
-      c.d_numaalloc = nullptr;
-      c.out_cap = 0;
-      HIP_OK(hipMalloc(&c.d_out, OutLayout((size_t)n_pods, (size_t)n_pods).total));  // (n_batches <= n_pods)
-      HIP_OK(hipMalloc(&c.d_devalloc, sizeof(uint64_t) * n_pods));
-      c.out_cap = n_pods;
-    }
+    const size_t np = (size_t)n_pods;
+    RC_OK(c.d_out.reserve(OutLayout(np, np).total));  // (n_batches <= n_pods)
+    RC_OK(c.d_devalloc.reserve(np));
+    if (numa) RC_OK(c.d_numaalloc.reserve(16 * np));
     d_chosen = reinterpret_cast<int32_t*>(c.d_out + ol.chosen);
     d_chosen_score = reinterpret_cast<int32_t*>(c.d_out + ol.score);
     d_err = reinterpret_cast<int32_t*>(c.d_out + ol.err);
@@ -8678,16 +8458,15 @@ struct ScheduleCall {
     estamps = reinterpret_cast<uint64_t*>(c.d_out + ol.est);
     // (every singleton batch's k_cpuset_reserve writes its pod's entry; the table is read back, and so zeroed by
     // k_call_begin, only in a call with a cpuset pod)
-    if ((rc = ensure((void**)&c.d_cpusets, &c.cpusets_cap, sizeof(uint64_t) * 4 * (int64_t)n_pods))) return rc;
+    RC_OK(c.d_cpusets.reserve(4 * np));
     bool any_hint = false;
     for (const DevPod& q : c.host_pods) any_hint = any_hint || (q.flags & PF_DS_HINT);
     d->soa.vfo = nullptr;
     if (any_hint) {  // the VF ranks the hinted pods' Reserves take
-      if ((rc = ensure((void**)&d->d_vfo, &d->vfo_cap, 2 * DS_MINORS * (int64_t)n_pods))) return rc;
+      RC_OK(d->d_vfo.reserve(2 * DS_MINORS * np));
       HIP_OK(fill_async(d->d_vfo, 0xFF, 2 * DS_MINORS * (size_t)n_pods, d->stream));
       d->soa.vfo = d->d_vfo;
     }
-    if (numa && !c.d_numaalloc) HIP_OK(hipMalloc(&c.d_numaalloc, sizeof(int64_t) * 16 * c.out_cap));
     if (numa) {
       if ((rc = defer_ensure(d, (int64_t)MAX_BATCH * d->capacity, n_batches, &defer))) return rc;
       HIP_OK(fill_async(defer.cnt, 0, sizeof(uint32_t) * n_batches, d->stream));
@@ -8705,14 +8484,14 @@ struct ScheduleCall {
       if (n_pods != 1 && !fused) return fail(KE_ERR_UNSUPPORTED, "matched reservations need a singleton segment");
       for (const RsvPair& q : ctx->rsv_pairs)
         if (q.node < 0 || q.node >= N) return fail(KE_ERR_DEVICE, "reservation pair node out of range");
-      if ((rc = ensure((void**)&d->d_rsv, &d->rsv_cap, (int64_t)sizeof(RsvPair) * (int64_t)ctx->rsv_pairs.size()))) return rc;
+      RC_OK(d->d_rsv.reserve(ctx->rsv_pairs.size()));
     }
     if (fused || matched) {
       if (!d->h_rsv_out.resize(5)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the reservation staging");
       for (int i = 0; i < 4; i++) d->h_rsv_out[i] = -1;
       d->h_rsv_out[4] = 0;  // the fused pod's gate (k_rsv_check)
     }
-    if (fused && !d->d_rsv_gate) HIP_OK(hipMalloc(&d->d_rsv_gate, sizeof(int32_t)));
+    if (fused) RC_OK(d->d_rsv_gate.reserve(1));
     const size_t rsv_bytes = sizeof(RsvPair) * ctx->rsv_pairs.size(), ovr_bytes = sizeof(RsvOvr) * ctx->rsv_ovr.size();
     if (rsv_bytes + ovr_bytes && !d->h_rsv.resize(rsv_bytes + ovr_bytes))
       return fail(KE_ERR_DEVICE, "hipHostMalloc of the reservation staging");
@@ -8725,7 +8504,7 @@ struct ScheduleCall {
     }
     d->soa.n_rovr = 0;  // a matched pod's allocate-from-reservation decisions (NF_RSV_CS rows read them)
     if (!ctx->rsv_ovr.empty()) {
-      if ((rc = ensure((void**)&d->d_rovr, &d->rovr_cap, (int64_t)sizeof(RsvOvr) * (int64_t)ctx->rsv_ovr.size()))) return rc;
+      RC_OK(d->d_rovr.reserve(ctx->rsv_ovr.size()));
       std::memcpy(d->h_rsv.data() + rsv_bytes, ctx->rsv_ovr.data(), ovr_bytes);
       HIP_OK(copy_async(d->d_rovr, d->h_rsv.data() + rsv_bytes, ovr_bytes, hipMemcpyHostToDevice, d->stream));
       d->soa.rovr = d->d_rovr;
@@ -8741,8 +8520,7 @@ struct ScheduleCall {
 
   // the bookkeeping words, the one copy of everything the call uploads, the call's events, and k_call_begin
   int begin() {
-    int rc;
-    if ((rc = ensure((void**)&c.d_sched, &c.sched_cap, (int64_t)sizeof(int32_t) * sl.total))) return rc;
+    RC_OK(c.d_sched.reserve((size_t)sl.total));
     d_bases = reinterpret_cast<int32_t*>(c.d_pods + n_pods) + (ns ? n_pods : 0);
     d_ready = c.d_sched + sl.ready, d_done = c.d_sched + sl.done, d_tready = c.d_sched + sl.tready;
     d_sstart = c.d_sched + sl.sstart, d_rres = c.d_sched + sl.rres, d_tlist = c.d_sched + sl.tlist;
@@ -8767,8 +8545,8 @@ struct ScheduleCall {
     const int64_t nw_out = (int64_t)(ol.st - ol.err) / 4, nw_cs = any_cpu ? 8 * (int64_t)n_pods : 0;
     const int64_t nw = std::max(std::max(sl.words, nw_out), nw_cs);
     hipLaunchKernelGGL(k_call_begin, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, d->stream,
-                       reinterpret_cast<uint32_t*>(c.d_sched), sl.words, reinterpret_cast<uint32_t*>(d_err), nw_out,
-                       reinterpret_cast<uint32_t*>(c.d_cpusets), nw_cs, d_st);
+                       reinterpret_cast<uint32_t*>(c.d_sched.get()), sl.words, reinterpret_cast<uint32_t*>(d_err), nw_out,
+                       reinterpret_cast<uint32_t*>(c.d_cpusets.get()), nw_cs, d_st);
     HIP_OK(hipEventRecord(d->ev_start, d->stream));
     HIP_OK(hipStreamWaitEvent(d->estream, d->ev_start, 0));
     return KE_OK;
@@ -9279,9 +9057,8 @@ int device_check_records(Context* ctx, int64_t now, int64_t* bad) {
   HIP_OK(hipSetDevice(d->device));
   int rc = device_refresh(ctx, now);
   if (rc) return rc;
-  unsigned long long* dbad = nullptr;
-  HIP_OK(hipMalloc(&dbad, sizeof(unsigned long long)));
-  HIP_OK(hipMemsetAsync(dbad, 0, sizeof(unsigned long long), d->stream));
+  DevBuf<unsigned long long> dbad;  // (freed on every way out, after the wait below or hipFree's own)
+  RC_OK(dbad.reserve_zeroed(1, d->stream));
   const int N = ctx->n_nodes;
   if (N > 0)
     hipLaunchKernelGGL(k_check_records, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, d->stream, d->soa, N,
@@ -9289,7 +9066,6 @@ int device_check_records(Context* ctx, int64_t now, int64_t* bad) {
   unsigned long long h = 0;
   HIP_OK(hipMemcpyAsync(&h, dbad, sizeof(h), hipMemcpyDeviceToHost, d->stream));
   HIP_OK(hipStreamSynchronize(d->stream));
-  HIP_OK(hipFree(dbad));
   *bad = (int64_t)h;
   return KE_OK;
 }
@@ -9297,13 +9073,12 @@ int device_check_records(Context* ctx, int64_t now, int64_t* bad) {
 int device_debug_rows(Context* ctx, int32_t n, Row* out) {
   DeviceState* d = ctx->dev;
   HIP_OK(hipSetDevice(d->device));
-  Row* tmp = nullptr;
-  HIP_OK(hipMalloc(&tmp, sizeof(Row) * std::max(n, 1)));
+  DevBuf<Row> tmp;
+  RC_OK(tmp.reserve((size_t)std::max(n, 1)));
   hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d->stream, d->soa, tmp, n);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(out, tmp, sizeof(Row) * n, hipMemcpyDeviceToHost, d->stream));
   HIP_OK(hipStreamSynchronize(d->stream));
-  HIP_OK(hipFree(tmp));
   return KE_OK;
 }
 

@@ -248,3 +248,71 @@ def test_pod_latency_definition(gpu):
     assert lat.max() <= wall + 1e-6
     assert lat[0] >= per_batch[0] - 1e-6
     assert lat[-1] > lat[0]
+
+
+def _rows_consistent(ev):
+    dev, host = ev.debug_rows(synth.T0, device=True)
+    assert np.array_equal(dev, host), np.flatnonzero(dev != host)[:5].tolist()
+    assert np.array_equal(ev.debug_rows(synth.T0, device=False)[1], host)
+    assert ev.check_records(synth.T0) == 0
+
+
+def _schedule_all_equal(ev, o, pods):
+    """placements, scores, cpusets, NUMA allocations and device allocations of one queue against the oracle"""
+    assert_schedule_equal(ev, o, pods, synth.T0)
+    assert np.array_equal(ev.last_numa_allocations, o.last_numa_allocations)
+    assert np.array_equal(ev.last_device_allocations, o.last_device_allocations)
+
+
+def test_side_tables_appear_after_rows_are_on_the_device(gpu):
+    """130 nodes (two full waves and a tail below the padded capacity of 256) whose rows are uploaded and clean
+    before the first NUMA zones, CPU tables and device cache entries arrive on a third of them: the NUMA, CPU and
+    DeviceShare tables are allocated by the next refresh, each with its own rule for which of the already clean
+    nodes it must derive again, and the queue mixing NUMA-policy, cpuset, DeviceShare and plain pods stays bit-exact
+    with an oracle fed the same events in the same order."""
+    n = 130
+    ev, o, cl = _plain(n, 1161)
+    _schedule_all_equal(ev, o, synth.make_pods(16, synth.BASE_SEED + 1162))
+    _rows_consistent(ev)
+    zones, tabs = synth.make_numa_cpus(cl, synth.BASE_SEED + 1163)  # (its node labels are not loaded: rows stay as are)
+    devs = synth.make_devices(n, synth.BASE_SEED + 1164, no_cache_fraction=0.0)
+    late = np.arange(0, n, 3)  # node 129, the last of the tail, among them
+    assert late[-1] == n - 1
+    for h in (ev, o):
+        for i in late:
+            h.set_numa(int(i), zones[i])
+            h.set_cpus(int(i), tabs[i][0], tabs[i][1])
+            h.set_devices(int(i), devs[i])
+    mixed = np.concatenate([
+        synth.make_numa_cpuset_pods(10, synth.BASE_SEED + 1165, cpuset_fraction=0.6, policy_fraction=0.5),
+        synth.make_ds_pods(10, synth.BASE_SEED + 1166, device_fraction=0.8),
+        synth.make_pods(4, synth.BASE_SEED + 1167, key_base=8_600_000_000)])
+    np.random.default_rng(1168).shuffle(mixed)
+    _schedule_all_equal(ev, o, mixed)
+    a = ev.last_allocations()
+    assert a["cpuset"].any() and ev.last_numa_allocations.any() and ev.last_device_allocations.any()
+    assert np.isin(a["node"][a["cpuset"].any(axis=1)], late).all()
+    _rows_consistent(ev)
+
+
+def test_refresh_staging_growth_and_alternation(gpu):
+    """Four refreshes in a row over 130 nodes, dirtying 3, 70, 129 and 5 of them (NodeInfo.Requested moved, a pod
+    assigned on every other one): the row staging grows twice, is then reused below its capacity, and the two
+    page-locked staging areas take turns.  After each refresh and the 4-pod queue behind it the placements equal the
+    oracle's, the device rows equal the host derivation and the replay records are consistent."""
+    n = 130
+    ev, o, cl = _plain(n, 1171)
+    rng = np.random.default_rng(1172)
+    extra = synth.make_pods(n, synth.BASE_SEED + 1173, key_base=8_700_000_000)
+    for step, k in enumerate((3, 70, 129, 5)):
+        for i in rng.choice(n, k, replace=False):
+            req = _node_now(ev, o, i).requested
+            for h in (ev, o):
+                h.set_requested(int(i), int(req[0]) + 100 * (step + 1), int(req[1]) + (step + 1) * 2**20)
+                if i % 2:
+                    h.assign(int(i), abi.Pod.from_buffer_copy(extra[int(i):int(i) + 1].tobytes()), synth.T0 - (step + 1) * 10**9)
+        pods = synth.make_pods(4, synth.BASE_SEED + 1174 + step, key_base=8_800_000_000 + 10 * step)
+        c1, s1 = ev.schedule(pods, synth.T0)
+        c0, s0 = o.schedule(pods, synth.T0)
+        assert np.array_equal(c1, c0) and np.array_equal(s1, s0), (step, k)
+        _rows_consistent(ev)
