@@ -951,6 +951,47 @@ int ke_node_scores_set(ke_ctx* ctx, int32_t node, int32_t n_tables, const uint16
  * call with a different n_pods, or after the table was replaced by a smaller one, is KE_ERR_INVALID.  Does not
  * wait for calls in flight. */
 int ke_pod_node_scores(ke_ctx* ctx, int32_t n_pods, const int32_t* table_ids);
+/* ---- spread groups: per-node pod caps that follow every Reserve (additive: KE_ABI_VERSION stays 14) ---
+ * Node sets and score offsets are static for a call.  Required pod anti-affinity on kubernetes.io/hostname and
+ * "at most k replicas of this workload per node" are not: whether a node is eligible for pod j depends on where
+ * pods 0 .. j-1 of the same call went.  A spread group g (1..n_groups) has a cap max_per_node[g-1] >= 1 and a
+ * uint16 count per node, seeded by the caller from the pods its informers see; a pod of a call may name one
+ * group (id 0 = none).
+ *  - Filter: a node with count[g][node] >= max_per_node[g] is filtered for the pod as if an earlier in-tree Filter
+ *    plugin had failed there, and reports exactly like a pair outside the pod's node set:
+ *    KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE, KE_REASON_NODE_SET (KE_PLUGIN_NODE_SET: the caller's in-tree
+ *    filters), plugin scores 0, total -1; it is outside best[] and DeviceShare's NormalizeScore maximum.  The test
+ *    follows the node-set test and precedes every koordinator filter.
+ *  - Reserve: ke_schedule / ke_schedule_submit placing a pod of group g on node n do count[g][n] += 1; every later
+ *    pod -- of the same batch, of later batches, of later calls -- sees it.  A pod without an eligible feasible
+ *    node gets -1 and changes nothing.  Bit-exact with one pod at a time for every pod_batch, pipelined or not,
+ *    submitted ahead or not.
+ *  - ke_eval and ke_diagnose read the counts and change nothing.
+ *  - ke_unreserve and ke_pod_release do NOT touch the counts: the caller undoes a placement's increment with
+ *    ke_spread_group_add(ctx, group, node, -1).
+ * Only the hostname topology is covered (a zone-level count would change eligibility on nodes nobody Reserved).
+ * A ke_schedule / ke_schedule_submit call with a non-zero group id must be a plain queue exactly as one with a
+ * non-zero node set id (above); anything else is KE_ERR_UNSUPPORTED before any state changes ("spread groups:
+ * ...", or the node sets' / node scores' message when a set or table id of the call is non-zero too).  ke_eval and
+ * ke_diagnose take group ids wherever they take set ids.  Group ids, set ids and table ids may all be staged for
+ * one call.  Without a table, or with every id 0, every call behaves as before. */
+#define KE_MAX_SPREAD_GROUPS 1024
+/* Replace the whole table: group g's counts are n_nodes uint16 at counts + (g-1)*n_nodes (counts NULL = all zero),
+ * its cap max_per_node[g-1] >= 1.  Nodes at or beyond n_nodes have count 0.  n_groups = 0 drops the table (both
+ * arrays may be NULL).  Completes calls in flight first. */
+int ke_spread_groups_load(ke_ctx* ctx, int32_t n_groups, int32_t n_nodes, const uint16_t* counts,
+                          const uint16_t* max_per_node);
+/* count[group][node] += delta (an informer pod add / delete event, or the undo of a placement); a count clamps at
+ * 0, a count that would pass 65535 is KE_ERR_INVALID and changes nothing.  group in 1..n_groups, node a node
+ * index of the context (KE_ERR_NOT_FOUND otherwise).  Completes calls in flight first. */
+int ke_spread_group_add(ke_ctx* ctx, int32_t group, int32_t node, int32_t delta);
+/* The current counts of one group, every Reserve included: counts[0 .. n_nodes).  Completes calls in flight first. */
+int ke_spread_groups_get(ke_ctx* ctx, int32_t group, int32_t n_nodes, uint16_t* counts);
+/* Group id per pod for the NEXT ke_eval / ke_diagnose / ke_schedule / ke_schedule_submit of exactly n_pods pods;
+ * 0 = none.  Consumed by that call whether it succeeds or not.  An id outside 0..n_groups is KE_ERR_INVALID here;
+ * a following call with a different n_pods, or after the table was replaced by a smaller one, is KE_ERR_INVALID.
+ * Does not wait for calls in flight. */
+int ke_pod_spread_groups(ke_ctx* ctx, int32_t n_pods, const int32_t* group_ids);
 /* ---- FitError diagnosis of unschedulable pods (additive: KE_ABI_VERSION stays 14) -------------------
  * A pod ke_schedule left at chosen = -1 must go back to the queue with a framework.FitError.  The reference reads
  * three parts of it, all reductions of the Filter status map (framework.NodeToStatusMap) findNodesThatFitPod fills:
@@ -1360,6 +1401,9 @@ int ke_debug_call_boundary(ke_ctx* ctx, int64_t* out4);
 /* Number of nodes whose replay record (the Reserve replay's row-major copy of the node-only terms)
  * differs from one derived from the node's current device row (0 = consistent). */
 int ke_debug_check_records(ke_ctx* ctx, int64_t now_ns, int64_t* mismatched_nodes);
+/* Number of (group, node) entries of the device's spread group table that differ from the host's copy (which
+ * ke_spread_groups_get answers from; 0 = consistent, also without a table). */
+int ke_debug_spread_groups_check(ke_ctx* ctx, int64_t* mismatched);
 /* Launch the batch eval kernel `iters` times back to back over the current node SoA for `n_pods`
  * (<= 64) pods and return the HIP-event average milliseconds per launch (roofline measurement). */
 int ke_bench_eval_kernel(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns, int32_t iters,

@@ -34,6 +34,8 @@ int device_set_profiling(Context* ctx, int32_t every);
 int device_set_pipeline(Context* ctx, int32_t on);
 int device_replay_phases(Context* ctx, int which, double* cyc8);
 int device_check_records(Context* ctx, int64_t now, int64_t* bad);
+// (weak: a host-only build of this file, without ke_kernels.hip, links without it -- there is no device copy to check)
+int device_spread_groups_check(Context* ctx, int64_t* bad) __attribute__((weak));
 int device_bench_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, int32_t iters, double* avg_ms);
 int device_comm_unique_id(uint8_t* id);
 int device_shard_init(Context* ctx, int rank, int world, const uint8_t* id);
@@ -711,29 +713,97 @@ int ke_pod_node_scores(ke_ctx* ctx, int32_t n_pods, const int32_t* table_ids) {
   return KE_OK;
 }
 
-// The ke_pod_node_sets and ke_pod_node_scores ids of this call, both consumed whether it goes on or not;
-// Context::ns_call / nsc_call = the ids of a kind when any of them is non-zero (the device entry points then run the
-// node-set / score-offset kernels).  Such a call is refused here, before any state changes, where those kernels are
-// not built: node-sharded contexts, and for ke_schedule (`sched`) anything but a plain queue (ke_schedule_submit's
-// sense, with device_async_ok's conditions).  The message names the sets when a set id is non-zero, else the scores.
+// ---- spread groups (include/koord_eval.h): the node sets' lifecycle ----
+int ke_spread_groups_load(ke_ctx* ctx, int32_t n_groups, int32_t n_nodes, const uint16_t* counts,
+                          const uint16_t* max_per_node) {
+  if (ctx) async_drain(ctx);
+  if (!ctx || n_groups < 0 || n_nodes < 0) return fail(KE_ERR_INVALID, "ke_spread_groups_load arguments");
+  if (n_groups > KE_MAX_SPREAD_GROUPS) return fail(KE_ERR_INVALID, "ke_spread_groups_load: more than KE_MAX_SPREAD_GROUPS groups");
+  if (n_nodes > MAX_SHARD_NODES) return fail(KE_ERR_INVALID, "ke_spread_groups_load: n_nodes");
+  if (n_groups > 0 && !max_per_node) return fail(KE_ERR_INVALID, "ke_spread_groups_load: max_per_node");
+  for (int32_t g = 0; g < n_groups; g++)
+    if (max_per_node[g] < 1) return fail(KE_ERR_INVALID, "ke_spread_groups_load: a cap below 1");
+  Context& c = ctx->c;
+  c.sg_n = n_groups;
+  c.sg_nodes = n_groups > 0 ? n_nodes : 0;
+  // (a Reserve may land on any node of the context: the host copy has an entry for each, zero beyond n_nodes)
+  c.sg_stride = n_groups > 0 ? std::max<int64_t>(n_nodes, c.cfg.node_capacity) : 0;
+  c.sg_cnt.assign((size_t)n_groups * (size_t)c.sg_stride, 0);
+  if (counts)
+    for (int32_t g = 0; g < n_groups; g++)
+      std::copy(counts + (size_t)g * (size_t)n_nodes, counts + (size_t)(g + 1) * (size_t)n_nodes,
+                c.sg_cnt.begin() + (int64_t)g * c.sg_stride);
+  c.sg_cap.assign(max_per_node, max_per_node + n_groups);
+  c.sg_dirty = true;
+  c.sg_dirty_cells.clear();
+  return KE_OK;
+}
+
+int ke_spread_group_add(ke_ctx* ctx, int32_t group, int32_t node, int32_t delta) {
+  if (ctx) async_drain(ctx);
+  if (!ctx) return fail(KE_ERR_INVALID, "ke_spread_group_add arguments");
+  Context& c = ctx->c;
+  if (group < 1 || group > c.sg_n) return fail(KE_ERR_NOT_FOUND, "ke_spread_group_add: group outside 1..n_groups");
+  if (node < 0 || (int64_t)node >= c.sg_stride) return fail(KE_ERR_NOT_FOUND, "ke_spread_group_add: node index beyond the table");
+  uint16_t& v = c.sg_cnt[(size_t)(group - 1) * (size_t)c.sg_stride + (size_t)node];
+  const int64_t nv = std::max<int64_t>((int64_t)v + delta, 0);
+  if (nv > 65535) return fail(KE_ERR_INVALID, "ke_spread_group_add: the count would pass 65535");
+  v = (uint16_t)nv;
+  if (!c.sg_dirty) c.sg_dirty_cells.push_back({group, node});  // (the next call with a non-zero id uploads the entry)
+  return KE_OK;
+}
+
+int ke_spread_groups_get(ke_ctx* ctx, int32_t group, int32_t n_nodes, uint16_t* counts) {
+  if (ctx) async_drain(ctx);
+  if (!ctx || n_nodes < 0 || (n_nodes > 0 && !counts)) return fail(KE_ERR_INVALID, "ke_spread_groups_get arguments");
+  const Context& c = ctx->c;
+  if (group < 1 || group > c.sg_n) return fail(KE_ERR_NOT_FOUND, "ke_spread_groups_get: group outside 1..n_groups");
+  const uint16_t* row = c.sg_cnt.data() + (size_t)(group - 1) * (size_t)c.sg_stride;
+  for (int32_t i = 0; i < n_nodes; i++) counts[i] = (int64_t)i < c.sg_stride ? row[i] : (uint16_t)0;
+  return KE_OK;
+}
+
+int ke_pod_spread_groups(ke_ctx* ctx, int32_t n_pods, const int32_t* group_ids) {
+  if (!ctx || n_pods < 0 || (n_pods > 0 && !group_ids)) return fail(KE_ERR_INVALID, "ke_pod_spread_groups arguments");
+  Context& c = ctx->c;
+  for (int32_t p = 0; p < n_pods; p++)
+    if (group_ids[p] < 0 || group_ids[p] > c.sg_n)
+      return fail(KE_ERR_INVALID, "ke_pod_spread_groups: group id outside 0..n_groups");
+  c.sg_staged.assign(group_ids, group_ids + n_pods);
+  c.sg_staged_on = true;
+  return KE_OK;
+}
+
+// The ke_pod_node_sets, ke_pod_node_scores and ke_pod_spread_groups ids of this call, all consumed whether it goes on
+// or not; Context::ns_call / nsc_call / sg_call = the ids of a kind when any of them is non-zero (the device entry
+// points then run the node-set / score-offset / spread-group kernels).  Such a call is refused here, before any state
+// changes, where those kernels are not built: node-sharded contexts, and for ke_schedule (`sched`) anything but a
+// plain queue (ke_schedule_submit's sense, with device_async_ok's conditions).  The message names the sets when a
+// set id is non-zero, else the scores when a table id is, else the spread groups.
 static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool sched) {
   Context& c = ctx->c;
   c.ns_call = nullptr;
   c.nsc_call = nullptr;
-  const bool sets_on = c.ns_staged_on, scores_on = c.nsc_staged_on;
-  if (!sets_on && !scores_on) return KE_OK;
-  c.ns_staged_on = c.nsc_staged_on = false;
+  c.sg_call = nullptr;
+  const bool sets_on = c.ns_staged_on, scores_on = c.nsc_staged_on, groups_on = c.sg_staged_on;
+  if (!sets_on && !scores_on && !groups_on) return KE_OK;
+  c.ns_staged_on = c.nsc_staged_on = c.sg_staged_on = false;
   c.ns_call_ids.clear();
   c.nsc_call_ids.clear();
+  c.sg_call_ids.clear();
   if (sets_on) c.ns_call_ids.swap(c.ns_staged);
   if (scores_on) c.nsc_call_ids.swap(c.nsc_staged);
+  if (groups_on) c.sg_call_ids.swap(c.sg_staged);
   c.ns_staged.clear();
   c.nsc_staged.clear();
+  c.sg_staged.clear();
   if (sets_on && (int32_t)c.ns_call_ids.size() != n_pods)
     return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_node_sets ids'");
   if (scores_on && (int32_t)c.nsc_call_ids.size() != n_pods)
     return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_node_scores ids'");
-  bool any = false, any_sc = false;
+  if (groups_on && (int32_t)c.sg_call_ids.size() != n_pods)
+    return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_spread_groups ids'");
+  bool any = false, any_sc = false, any_sg = false;
   for (int32_t id : c.ns_call_ids) {
     if (id < 0 || id > c.ns_n) return fail(KE_ERR_INVALID, "a staged node set id is outside the table loaded since");
     any = any || id != 0;
@@ -742,11 +812,15 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
     if (id < 0 || id > c.nsc_n) return fail(KE_ERR_INVALID, "a staged node score table id is outside the table loaded since");
     any_sc = any_sc || id != 0;
   }
-  if (!any && !any_sc) return KE_OK;
+  for (int32_t id : c.sg_call_ids) {
+    if (id < 0 || id > c.sg_n) return fail(KE_ERR_INVALID, "a staged spread group id is outside the table loaded since");
+    any_sg = any_sg || id != 0;
+  }
+  if (!any && !any_sc && !any_sg) return KE_OK;
   int rc = check_pods(pods, n_pods, &c, sched);
   if (rc) return rc;
-  auto no = [any](const char* what) {
-    return fail(KE_ERR_UNSUPPORTED, std::string(any ? "node sets: " : "node scores: ") + what);
+  auto no = [any, any_sc](const char* what) {
+    return fail(KE_ERR_UNSUPPORTED, std::string(any ? "node sets: " : any_sc ? "node scores: " : "spread groups: ") + what);
   };
   if (c.cfg.global_node_offset != 0 || (c.dev && device_sharded(&c))) return no("a node-sharded context");
   if (sched) {
@@ -765,6 +839,7 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
   }
   if (any) c.ns_call = c.ns_call_ids.data();
   if (any_sc) c.nsc_call = c.nsc_call_ids.data();
+  if (any_sg) c.sg_call = c.sg_call_ids.data();
   return KE_OK;
 }
 
@@ -1698,6 +1773,14 @@ int ke_debug_check_records(ke_ctx* ctx, int64_t now_ns, int64_t* mismatched_node
   int rc = require_device(ctx);
   if (rc) return rc;
   return device_check_records(&ctx->c, now_ns, mismatched_nodes);
+}
+
+int ke_debug_spread_groups_check(ke_ctx* ctx, int64_t* mismatched) {
+  if (ctx) async_drain(ctx);
+  if (!ctx || !mismatched) return fail(KE_ERR_INVALID, "ke_debug_spread_groups_check arguments");
+  *mismatched = 0;
+  if (!ctx->c.dev || !device_spread_groups_check) return KE_OK;  // (no device copy yet)
+  return device_spread_groups_check(&ctx->c, mismatched);
 }
 
 int ke_set_pipeline(ke_ctx* ctx, int32_t on) {

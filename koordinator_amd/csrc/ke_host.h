@@ -247,6 +247,21 @@ struct Context {
   bool nsc_staged_on = false;
   std::vector<int32_t> nsc_call_ids;
   const int32_t* nsc_call = nullptr;
+  // Spread groups (ke_spread_groups_load), with the node sets' lifecycle: the host copy of the table
+  // (sg_n rows of sg_stride counts, group g = row g - 1; sg_stride covers the loaded n_nodes and the node capacity, so
+  // every Reserve has an entry) and the caps; a call's completion applies its placements' increments here -- the
+  // device does the same arithmetic, no read-back.  What of the device copy is stale: all of it, or the
+  // (row, node) entries ke_spread_group_add patched.  The ke_pod_spread_groups staging for the next call and the
+  // group ids of the call in progress (nullptr: no non-zero id, the call runs the kernels it ran without them).
+  int32_t sg_n = 0, sg_nodes = 0;
+  int64_t sg_stride = 0;
+  std::vector<uint16_t> sg_cnt, sg_cap;
+  bool sg_dirty = false;
+  std::vector<std::pair<int32_t, int32_t>> sg_dirty_cells;
+  std::vector<int32_t> sg_staged;
+  bool sg_staged_on = false;
+  std::vector<int32_t> sg_call_ids;
+  const int32_t* sg_call = nullptr;
   // the KE_RSV_MATCHED pod of the current segment: its nodes with matched reservations, their
   // (node, ScoreReservation of the nominated one, smallest order) for the device pick, the nominated index
   std::vector<int32_t> rsv_nodes;

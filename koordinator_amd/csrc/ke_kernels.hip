@@ -101,16 +101,30 @@ struct SoA {
   // table id packs (table id << 16) | set id into its ns_ids words and runs the NS == NS_SCORES instantiations.
   int32_t nsc_stride;
   const uint16_t* nsc_tbl;
+  // spread groups: rows 0 .. n_groups of sg_stride (= the node capacity) uint16 pod counts, row 0 all
+  // zero, and the caps of rows 0 .. n_groups (row 0: 65535, so group id 0 needs no branch); the current call's group
+  // id per pod, parallel to its DevPod array.  Read only by the NS_GROUPS instantiations; the one-wave replay of a
+  // grouped batch increments the count of every (group, node) it Reserves.
+  int32_t sg_stride;
+  uint16_t* sg_cnt;
+  const uint16_t* sg_cap;
+  const int32_t* sg_ids;
 };
 // NS, the template mode of every kernel that makes a score or key: 0 = the call has no per-pod ids, NS_SETS = its
-// ns_ids words are node set ids, NS_SCORES = they are (score table id << 16) | node set id
-constexpr int NS_SETS = 1, NS_SCORES = 2;
+// ns_ids words are node set ids, NS_SCORES = they are (score table id << 16) | node set id, NS_GROUPS = NS_SCORES and
+// the pods' spread groups (sg_ids) besides
+constexpr int NS_SETS = 1, NS_SCORES = 2, NS_GROUPS = 3;
 // node `node` is in the set of id word `idw` (NS instantiations; every node < 64 * ns_wps is in bounds, the ids
 // checked by the host)
 template <int NS>
 __device__ __forceinline__ bool ns_ok(const SoA& s, int idw, int node) {
   if constexpr (!NS) return true;
-  else return (s.ns_tbl[(int64_t)(NS == NS_SCORES ? idw & 0xffff : idw) * s.ns_wps + (node >> 6)] >> (node & 63)) & 1ull;
+  else return (s.ns_tbl[(int64_t)(NS >= NS_SCORES ? idw & 0xffff : idw) * s.ns_wps + (node >> 6)] >> (node & 63)) & 1ull;
+}
+// the spread group of a pod has reached its cap on `node` (NS_GROUPS; node < sg_stride; group 0: never).  A plain
+// load, for the eval kernels: the counts change only in the one-wave replay of an earlier launch on their stream
+__device__ __forceinline__ bool sg_capped(const SoA& s, int gid, int node) {
+  return s.sg_cnt[(int64_t)gid * s.sg_stride + node] >= s.sg_cap[gid];
 }
 // a fresh key of (pod with set `sid`, node): 0 (filtered) outside the set
 template <int NS>
@@ -121,14 +135,14 @@ __device__ __forceinline__ uint32_t ns_key(const SoA& s, int sid, int node, uint
 // the score offset of (pod with id word `idw`, node): 0 unless NS_SCORES; node < nsc_stride
 template <int NS>
 __device__ __forceinline__ int32_t ns_off(const SoA& s, int idw, int node) {
-  if constexpr (NS != NS_SCORES) return 0;
+  if constexpr (NS < NS_SCORES) return 0;
   else return s.nsc_tbl[(int64_t)((uint32_t)idw >> 16) * s.nsc_stride + node];
 }
 // a fresh key of (pod with id word `idw`, node) from the plugins' total: the offset goes into a feasible total
 // before the key is packed (both table reads are issued before either is used); 0 outside the set
 template <int NS>
 __device__ __forceinline__ uint32_t ns_mkkey(const SoA& s, int idw, int node, int32_t total) {
-  if constexpr (NS != NS_SCORES) {
+  if constexpr (NS < NS_SCORES) {
     const uint32_t key = make_key(total, node);
     return ns_key<NS>(s, idw, node, key);
   } else {
@@ -3263,13 +3277,18 @@ struct BatchOut {
 
 // The classification ke_eval and ke_diagnose share, of (pod p, node i) in the first pass: the pod's node set ahead of
 // every other filter (NS: the call carries ids; a pair outside the set is KE_REASON_NODE_SET -- scores 0, total -1,
-// never deferred, and not part of the pod's DeviceShare normalisation max), then eval_pair; *deferred: the pair is
+// never deferred, and not part of the pod's DeviceShare normalisation max), with NS_GROUPS the pod's spread group cap
+// right behind it (same report), then eval_pair; *deferred: the pair is
 // left to k_numa_fallback / k_numa_finish (o.status == STATUS_DEFERRED).
 template <bool NUMA, bool CPU, int NS>
 __device__ __forceinline__ EvalOut classify_pair(const SoA& s, const NodeRegs& n, bool expired, const DevPod* pods, int p,
                                                  const KArgs& k, int i, const NumaNode& nv, bool* deferred) {
   *deferred = false;
-  if (NS && !ns_ok<NS>(s, s.ns_ids[p], i)) {  // (one table word a wave: the lanes' addresses are equal)
+  bool out_of_set = NS && !ns_ok<NS>(s, s.ns_ids[p], i);  // (one table word a wave: the lanes' addresses are equal)
+  // NS_GROUPS: a node where the pod's spread group has reached its cap reports as one outside the set (the lanes read
+  // 64 consecutive counts of a wave-uniform row)
+  if constexpr (NS == NS_GROUPS) out_of_set = out_of_set || sg_capped(s, s.sg_ids[p], i);
+  if (out_of_set) {
     EvalOut o;
     o.status = KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE;
     o.reason = KE_REASON_NODE_SET;
@@ -3286,8 +3305,8 @@ __device__ __forceinline__ EvalOut classify_pair(const SoA& s, const NodeRegs& n
 // parity mode: the full status / score matrices of `out`, every pair classified by classify_pair (an empty slot by
 // eval_pair's own NF_VALID test, behind the node-set gate).
 // IDS: the call carries per-pod ids (SoA::ns_ids): the low half of a word is the pod's node set (the high half, a
-// score table id, is k_parity_finalize's).
-template <bool NUMA, bool CPU, bool IDS = false>
+// score table id, is k_parity_finalize's).  GRP: it carries spread group ids too (NS_GROUPS).
+template <bool NUMA, bool CPU, bool IDS = false, bool GRP = false>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, const DevPod* __restrict__ pods, int n_pods,
                                                             int pods_per_block, KArgs k, ParityOut out,
                                                             uint64_t* defer_list, uint32_t* defer_cnt) {
@@ -3308,7 +3327,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, const DevPod*
     uint32_t m = 0;
     bool deferred = false;
     if (live) {
-      const EvalOut o = classify_pair<NUMA, CPU, IDS ? NS_SCORES : 0>(s, n, expired, pods, p, k, i, nv, &deferred);
+      const EvalOut o = classify_pair<NUMA, CPU, GRP ? NS_GROUPS : IDS ? NS_SCORES : 0>(s, n, expired, pods, p, k, i, nv, &deferred);
       out.store(p, i, o);
       m = o.total >= 0 ? (uint32_t)o.ds + 1 : 0u;
     }
@@ -3353,7 +3372,8 @@ struct DiagOut {
 
 // ke_diagnose's fused Filter + reduction: k_eval_parity's geometry and classification (lane = node, the row loaded
 // once into registers, the block's pods looped wave-uniformly, classify_pair for every populated slot), with
-// nothing written per pair.  NS: 0 or NS_SETS (score table ids are not part of a diagnosis).
+// nothing written per pair.  NS: 0, NS_SETS or NS_GROUPS (score table ids are not part of a diagnosis: with
+// NS_GROUPS the words' table halves are zero and unread).
 // A wave's 64 lanes are nodes [64w, 64w + 64), so the ballot of a class is the pod's bitmap word w: lane 0 stores it (plain 8-byte stores, no atomics; skipped for a bitmap not asked for).  The
 // counts go through a per-workgroup LDS table [pod of the group][DIAG_WORDS]: per pod a wave adds its class
 // popcounts and peels the distinct reasons of its failing lanes (the first one's reason -> ballot of the lanes that
@@ -3475,7 +3495,8 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_parity_finalize(int n_nodes, KAr
 // Nodes [lo, hi) of the SoA (this rank's shard); scores stay indexed by the global node index.
 // DS: the batch's pod is a DeviceShare pod (the DeviceShare path stays out of plain batches' code).
 // NS (plain batches only): a node outside the pod's node set (SoA::ns_ids) is filtered (score 0); NS_SCORES: a
-// feasible total takes the pod's score offset of the node (SoA::nsc_tbl) before the store.
+// feasible total takes the pod's score offset of the node (SoA::nsc_tbl) before the store; NS_GROUPS: besides, a node
+// where the pod's spread group (SoA::sg_ids) has reached its cap is filtered.
 template <bool DS, bool NUMA, bool CPU, bool EXT = false, bool H = false, int NS = 0>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_batch(SoA s, int lo, int hi, const DevPod* __restrict__ pods,
                                                            const int32_t* __restrict__ batch_base, int batch_pods,
@@ -3510,7 +3531,8 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_batch(SoA s, int lo, int hi
       if (EXT && tot >= 0 && (k.flags & AF_FIT_FILTER) && fit_filter_row(s, i, n, pod, k)) tot = -1;
       if (EXT && tot >= 0) tot += ext_score(s, i, pod, k);  // FitPlus / SRA / Fit: its own variant
       if (NS && !ns_ok<NS>(s, s.ns_ids[base + p], i)) tot = -1;  // (wave-uniform word address)
-      if constexpr (NS == NS_SCORES) tot = tot >= 0 ? tot + ns_off<NS>(s, s.ns_ids[base + p], i) : tot;
+      if constexpr (NS >= NS_SCORES) tot = tot >= 0 ? tot + ns_off<NS>(s, s.ns_ids[base + p], i) : tot;
+      if constexpr (NS == NS_GROUPS) tot = sg_capped(s, s.sg_ids[base + p], i) ? -1 : tot;  // (wave-uniform row)
       scores[(int64_t)p * score_stride + i] = (uint16_t)(tot + 1);
       continue;
     }
@@ -3537,6 +3559,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_batch(SoA s, int lo, int hi
 // Records are written sc1 by the Reserve kernels, so a pipelined eval sees them like the SoA rows.
 // NS: the pods' node sets (SoA::ns_ids) -- the block's table words (one a wave and pod, the tile starts at a
 // multiple of 64: lo = 0, set calls are unsharded) are staged in LDS with the pods, a node outside is filtered.
+// NS_GROUPS (a grouped batch): a node where a pod's spread group has reached its cap is filtered too.
 template <bool EXT, int NS = 0>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi, const DevPod* __restrict__ pods,
                                                            const int32_t* __restrict__ batch_base, int batch_pods,
@@ -3567,13 +3590,21 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
   // aligned bytes of a wave-uniform row; the rows cover the node capacity, so i < hi is in bounds), four to a
   // register pair so that the loop's wave-uniform q picks one without an indexed register file
   uint64_t off[2] = {0ull, 0ull};
-  if constexpr (NS == NS_SCORES) {
+  if constexpr (NS >= NS_SCORES) {
     static_assert(EVAL_PPB == 8, "two words of four offsets");
 #pragma unroll
     for (int q = 0; q < EVAL_PPB; q++) {
       const uint16_t v = q < np && i < hi ? s.nsc_tbl[(int64_t)((uint32_t)s.ns_ids[base + p0 + q] >> 16) * s.nsc_stride + i] : (uint16_t)0;
       off[q >> 2] |= (uint64_t)v << ((q & 3) * 16);
     }
+  }
+  // NS_GROUPS: bit q = the spread group of the group's pod q has reached its cap on this lane's node, read the same
+  // way (64 consecutive counts of a wave-uniform row per pod, the row and its cap found by scalar loads)
+  uint32_t capped = 0;
+  if constexpr (NS == NS_GROUPS) {
+#pragma unroll
+    for (int q = 0; q < EVAL_PPB; q++)
+      if (q < np && i < hi && sg_capped(s, s.sg_ids[base + p0 + q], i)) capped |= 1u << q;
   }
   if ((int)threadIdx.x < 4 * np) {
     const int q = threadIdx.x >> 2, c = threadIdx.x & 3;
@@ -3582,7 +3613,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
       static_assert(EVAL_BLOCK / 64 == 4, "one table word per wave of the block");
       const int w = ((lo + tile * (int)blockDim.x) >> 6) + c;
       const int idw = s.ns_ids[base + p0 + q];
-      s_ns[q][c] = w < s.ns_wps ? s.ns_tbl[(int64_t)(NS == NS_SCORES ? idw & 0xffff : idw) * s.ns_wps + w] : 0ull;
+      s_ns[q][c] = w < s.ns_wps ? s.ns_tbl[(int64_t)(NS >= NS_SCORES ? idw & 0xffff : idw) * s.ns_wps + w] : 0ull;
     }
     s_pd[q][c] = (double)(c < 2 ? pp.est[c] : pp.req[c - 2]);
     if (!EXT && c < 3) s_pi[q][c] = c < 2 ? pp.est[c] : pp.req[0];
@@ -3608,8 +3639,9 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
       pl.req[0] = s_pi[q][2];
       t = fast_total<false>(f, pl, ed, rd, k);
     }
-    if constexpr (NS == NS_SCORES) t = t >= 0 ? t + (int32_t)((uint32_t)((q < 4 ? off[0] : off[1]) >> ((q & 3) * 16)) & 0xffffu) : t;
+    if constexpr (NS >= NS_SCORES) t = t >= 0 ? t + (int32_t)((uint32_t)((q < 4 ? off[0] : off[1]) >> ((q & 3) * 16)) & 0xffffu) : t;
     if (NS && !((s_ns[q][threadIdx.x >> 6] >> (threadIdx.x & 63)) & 1ull)) t = -1;
+    if constexpr (NS == NS_GROUPS) t = (capped >> q) & 1u ? -1 : t;
     out[(int64_t)q * score_stride] = (uint16_t)(t + 1);
   }
 }
@@ -5671,7 +5703,9 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
     for (int u = 8; u < 12; u++) pstamps[PST * batch_index + u] = t;
     for (int u = 12; u < 16; u++) pstamps[PST * batch_index + u] = 0;
   }
-  if constexpr (!DS && !NUMA && !QUOTA) {  // plain batch: the speculative replay on every wave
+  // plain batch: the speculative replay on every wave (a grouped batch, NS_GROUPS: the sequential replay below, whose
+  // Reserves keep the spread group counts)
+  if constexpr (!DS && !NUMA && !QUOTA && NS != NS_GROUPS) {
     __builtin_amdgcn_s_setprio(3);
     replay_spec<EXT, NS>(L, C, s, base, B, k, chosen, chosen_score, global_offset, stamps, batch_index, dev_alloc,
                      touched_out, touched_cnt, pstamps + PST * batch_index, has_t, keep, LS, sorted, th);
@@ -5695,6 +5729,11 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
 //   fetched from the SoA by the next free lane at the start of the pod, into spare registers, so its
 //   latency hides under the re-evaluation; it becomes that lane's row if bu wins.  Pod j+1's record
 //   and candidates are read during pod j, its changed flags right after pod j's Reserve.
+//   NS_GROUPS (a grouped batch): a changed node's fresh key is 0 once the count of pod j's spread group
+//   there has reached the cap, and the owner lane's Reserve increments that count in the device table.  Lane c is
+//   the only reader and writer of its node's counts during the batch, and reads the one pod j+1 needs after pod j's
+//   Reserve (program order on one lane, fenced like the DeviceShare Reserve's SoA writes); unchanged nodes keep the
+//   counts their snapshot keys were made from.  Pod j+1's group id and cap are fetched with its DevPod.
 template <bool DS, bool NUMA, bool QUOTA, bool EXT, int NS>
 __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const SoA& s, const int base, const int B,
                                              const KArgs& k, int32_t* __restrict__ chosen,
@@ -5731,11 +5770,24 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
   double pdd[4] = {L.pd[0][0], L.pd[0][1], L.pd[0][2], L.pd[0][3]};
   uint32_t ck = s_cand[lane];
   bool chg = false;  // changed flag of this lane's candidate (pods < j); nothing is changed at j = 0
+  // NS_GROUPS: pod j's spread group and cap (wave-uniform), and this lane's node's count for it (lane < n_chg)
+  int gid = 0;
+  uint32_t gcap = 65535u, gcnt = 0;
+  if constexpr (NS == NS_GROUPS) {
+    gid = s.sg_ids[base];
+    gcap = s.sg_cap[gid];
+  }
   RPROF_DECL
   for (int j = 0; j < B; j++) {
     const bool more = j + 1 < B;
     const DevPod pod_n = s_pod[more ? j + 1 : j];
     const int jn = more ? j + 1 : j;
+    int gid_n = 0;
+    uint32_t gcap_n = 65535u;
+    if constexpr (NS == NS_GROUPS) {
+      gid_n = s.sg_ids[base + jn];
+      gcap_n = s.sg_cap[gid_n];
+    }
     const double pdd_n[4] = {L.pd[jn][0], L.pd[jn][1], L.pd[jn][2], L.pd[jn][3]};
     const double estd[2] = {pdd[0], pdd[1]}, reqd[2] = {pdd[2], pdd[3]};
     const uint32_t ck_n = more ? s_cand[(j + 1) * KMAX + lane] : 0u;
@@ -5773,6 +5825,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
         tot = fast_total<EXT>(fast, pod, estd, reqd, k);
       }
       kc = ns_mkkey<NS>(s, nsid_of<NS>(L, j), my_node, tot);
+      if constexpr (NS == NS_GROUPS) kc = gcnt >= gcap ? 0u : kc;  // the group is at its cap on this node now
     }
     RPROF(2)
     const uint32_t bc = wave_max_u32(kc);
@@ -5846,6 +5899,12 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
           mine.nreq[1] += pod.req[1];
         }
         if (!FAST && (k.flags & AF_EXT)) ext_reserve(s, my_node, pod, k);  // read back by the next re-evaluations
+        if constexpr (NS == NS_GROUPS) {  // the spread group's count on this node (a winner is below its cap: no wrap)
+          if (gid) {
+            uint16_t* const cnt = s.sg_cnt + (int64_t)gid * s.sg_stride + my_node;
+            st_sc1(cnt, (uint16_t)(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1));
+          }
+        }
         // DeviceShare Reserve (the device SoA is global: a later pod of the batch re-evaluating this node
         // reads it back, wave_lds_sync below)
         if (NUMA) {  // NodeNUMAResource Reserve: the zones of a NUMA-policy node
@@ -5885,8 +5944,16 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
     // pod j+1's changed flags, read after this Reserve's bitmap update (LDS ops of a wave execute in
     // order), so they already include pod j's new node
     const bool chg_n = ck_n != 0 && chg_test(C, key_node(ck_n));
-    if (NUMA || DS) wave_lds_sync();  // the next re-evaluation reads the zones / devices this Reserve patched
+    // the next re-evaluation reads the zones / devices / spread group count this Reserve patched
+    if (NUMA || DS || NS == NS_GROUPS) wave_lds_sync();
     else __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    if constexpr (NS == NS_GROUPS) {  // this lane's node's count of pod j+1's group, behind pod j's increment
+      gcnt = lane < n_chg ? __hip_atomic_load(s.sg_cnt + (int64_t)gid_n * s.sg_stride + my_node, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT)
+                          : 0u;
+      gid = gid_n;
+      gcap = gcap_n;
+    }
     pod = pod_n;
 #pragma unroll
     for (int u = 0; u < 4; u++) pdd[u] = pdd_n[u];
@@ -7191,6 +7258,10 @@ struct DeviceState {
   DevBuf<uint64_t> d_ns_tbl;
   // node score offsets: rows 0 .. nsc_n of `capacity` uint16 entries (row 0 all zero)
   DevBuf<uint16_t> d_nsc_tbl;
+  // spread groups: rows 0 .. sg_n of `capacity` uint16 counts (row 0 all zero), the caps of rows
+  // 0 .. sg_n behind them (row 0: 65535); sg_rows: the rows of the current upload (0: none yet)
+  DevBuf<uint16_t> d_sg_tbl;
+  int64_t sg_rows = 0;
   DevBuf<int8_t> d_vfo;     // [n_pods][2][DS_MINORS] VF ranks of the Reserves
   // batch buffers
   DevBuf<uint16_t> d_scores;  // [MAX_BATCH][capacity]
@@ -7818,6 +7889,58 @@ static int node_scores_sync(Context* ctx) {
   return KE_OK;
 }
 
+// The spread group table for a call that carries group ids: `capacity` uint16 counts a row, row 0 all
+// zero (id 0: never capped), row g the host copy's counts of group g, and behind the rows their caps (row 0: 65535).
+// A reload uploads the table; ke_spread_group_add's patches go up one entry each.  Between those the device keeps the
+// counts itself: its Reserves increment them, and the host copy takes the same increments at a call's completion.
+static std::vector<uint16_t> spread_groups_image(const Context* ctx, int64_t S) {  // the host copy in the device layout
+  const int64_t rows = (int64_t)ctx->sg_n + 1, cols = std::min(S, ctx->sg_stride);
+  std::vector<uint16_t> t((size_t)(rows * S + rows), (uint16_t)0);
+  for (int64_t g = 0; g < ctx->sg_n; g++)
+    std::copy(ctx->sg_cnt.begin() + g * ctx->sg_stride, ctx->sg_cnt.begin() + g * ctx->sg_stride + cols,
+              t.begin() + (g + 1) * S);
+  t[(size_t)(rows * S)] = 65535;
+  std::copy(ctx->sg_cap.begin(), ctx->sg_cap.end(), t.begin() + rows * S + 1);
+  return t;
+}
+static int spread_groups_sync(Context* ctx) {
+  DeviceState* d = ctx->dev;
+  const int64_t S = d->capacity, rows = (int64_t)ctx->sg_n + 1, cols = std::min(S, ctx->sg_stride);
+  if (ctx->sg_dirty || !d->d_sg_tbl || d->sg_rows != rows) {
+    const std::vector<uint16_t> t = spread_groups_image(ctx, S);
+    RC_OK(d->d_sg_tbl.reserve(t.size()));
+    HIP_OK(hipMemcpyAsync(d->d_sg_tbl, t.data(), sizeof(uint16_t) * t.size(), hipMemcpyHostToDevice, d->stream));
+    HIP_OK(hipStreamSynchronize(d->stream));
+    d->sg_rows = rows;
+  } else if (!ctx->sg_dirty_cells.empty()) {
+    for (const auto& gn : ctx->sg_dirty_cells) {
+      if (gn.second >= cols) continue;
+      HIP_OK(hipMemcpyAsync(d->d_sg_tbl + (int64_t)gn.first * S + gn.second,
+                            &ctx->sg_cnt[(size_t)((int64_t)(gn.first - 1) * ctx->sg_stride + gn.second)], sizeof(uint16_t),
+                            hipMemcpyHostToDevice, d->stream));
+    }
+    HIP_OK(hipStreamSynchronize(d->stream));
+  }
+  ctx->sg_dirty = false;
+  ctx->sg_dirty_cells.clear();
+  d->soa.sg_cnt = d->d_sg_tbl;
+  d->soa.sg_cap = d->d_sg_tbl + rows * S;
+  d->soa.sg_stride = (int32_t)S;
+  return KE_OK;
+}
+// the mode of a call's kernels from its ids: groups (which read the set and score tables' row 0 at least), score
+// tables, node sets, none
+static int call_ns(const Context* ctx) {
+  return ctx->sg_call ? NS_GROUPS : ctx->nsc_call ? NS_SCORES : ctx->ns_call ? NS_SETS : 0;
+}
+// the tables a call of mode `ns` reads, brought up to date
+static int id_tables_sync(Context* ctx, int ns) {
+  if (ns) RC_OK(node_sets_sync(ctx));
+  if (ns >= NS_SCORES) RC_OK(node_scores_sync(ctx));
+  if (ns == NS_GROUPS) RC_OK(spread_groups_sync(ctx));
+  return KE_OK;
+}
+
 // The call's upload block: the DevPod records, the node set ids when present (int32 each) and room for
 // tail_words more int32 words, laid out alike in the page-locked host_pods and in d_pods, so one copy carries
 // it.  Without `tail` the block is copied here; with it the caller fills *tail (ke_schedule's batch bases) and
@@ -7828,9 +7951,11 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t
   PinnedVec<DevPod>& dp = d->call.host_pods;
   // the call's node set ids and score table ids (a non-zero one among either): one word per pod behind the
   // records, the set id alone or -- in a call with table ids -- (table id << 16) | set id
+  // -- and in a call with spread group ids those words (zero without set / table ids) and the group ids behind them
   const int32_t* ns = ctx->ns_call;
   const int32_t* sc = ctx->nsc_call;
-  const int64_t ns_words = ns || sc ? (int64_t)n_pods : 0;
+  const int32_t* sg = ctx->sg_call;
+  const int64_t ns_words = (ns || sc || sg ? (int64_t)n_pods : 0) + (sg ? (int64_t)n_pods : 0);
   if (!dp.resize((size_t)n_pods, sizeof(int32_t) * (size_t)(ns_words + tail_words)))
     return fail(KE_ERR_DEVICE, "hipHostMalloc of the pod staging buffer");
   std::vector<DevPodHint>& ph = d->host_ph;  // the hinted pods' records; DevPod::ring_bw = slot
@@ -7854,7 +7979,12 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t
   RC_OK(d->call.d_pods.reserve((size_t)std::max<int64_t>((bytes + (int64_t)sizeof(DevPod) - 1) / (int64_t)sizeof(DevPod), 1)));
   int32_t* const h_words = reinterpret_cast<int32_t*>(dp.data() + n_pods);
   d->soa.ns_ids = nullptr;
-  if (ns || sc) {
+  d->soa.sg_ids = nullptr;
+  if (sg) {
+    std::copy(sg, sg + n_pods, h_words + n_pods);
+    d->soa.sg_ids = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods) + n_pods;
+  }
+  if (ns || sc || sg) {
     static_assert(KE_MAX_NODE_SETS < (1 << 16) && KE_MAX_NODE_SCORE_TABLES < (1 << 15), "the packed id word");
     for (int32_t p = 0; p < n_pods; p++) h_words[p] = (ns ? ns[p] : 0) | (sc ? sc[p] << 16 : 0);
     d->soa.ns_ids = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods);
@@ -7891,13 +8021,18 @@ static auto with_bool(bool v, F&& f) {
 template <class F>
 static auto with_ns_ext(int ns, bool ext, F&& f) {
   auto e = [&](auto NS) { return with_bool(ext, [&](auto EXT) { return f(NS, EXT); }); };
+  using Fn = decltype(e(std::integral_constant<int, 0>{}));  // (NS_GROUPS: no instantiation in these families)
   return ns == NS_SCORES ? e(std::integral_constant<int, NS_SCORES>{})
-         : ns            ? e(std::integral_constant<int, NS_SETS>{})
-                         : e(std::integral_constant<int, 0>{});
+         : ns == NS_SETS ? e(std::integral_constant<int, NS_SETS>{})
+         : ns == 0       ? e(std::integral_constant<int, 0>{})
+                         : Fn(nullptr);
 }
+// ... and NS_GROUPS, for the kernels a grouped batch reaches (pick_eval_batch, pick_eval_plain, pick_resolve)
 template <class F>
-static auto with_ns(int ns, F&& f) {
-  return with_ns_ext(ns, false, [&](auto NS, auto) { return f(NS); });
+static auto with_nsg_ext(int ns, bool ext, F&& f) {
+  if (ns == NS_GROUPS)
+    return with_bool(ext, [&](auto EXT) { return f(std::integral_constant<int, NS_GROUPS>{}, EXT); });
+  return with_ns_ext(ns, ext, f);
 }
 
 // NUMA x CPU x "the call carries ids" (node sets or score tables: the kernel reads a word's set half either way)
@@ -7905,12 +8040,15 @@ using EvalParityFn = decltype(&k_eval_parity<false, false>);
 static EvalParityFn pick_eval_parity(bool numa, bool cpu, int ns) {
   return with_bool(ns != 0, [&](auto IDS) {
     return with_bool(numa, [&](auto NUMA) {
-      return with_bool(cpu, [&](auto CPU) -> EvalParityFn { return k_eval_parity<KV(NUMA), KV(CPU), KV(IDS)>; });
+      return with_bool(cpu, [&](auto CPU) -> EvalParityFn {
+        if (ns == NS_GROUPS) return k_eval_parity<KV(NUMA), KV(CPU), true, true>;
+        return k_eval_parity<KV(NUMA), KV(CPU), KV(IDS)>;
+      });
     });
   });
 }
 static auto pick_parity_finalize(int ns) {
-  return with_bool(ns == NS_SCORES, [](auto SC) { return k_parity_finalize<KV(SC)>; });
+  return with_bool(ns >= NS_SCORES, [](auto SC) { return k_parity_finalize<KV(SC)>; });
 }
 // DS x NUMA x CPU; the plain instantiation (none of them) also NS x EXT, and a DeviceShare one the hint path H (a
 // hinted pod without a DeviceShare request is evaluated without it, as a plain pod is).  EXT is the plain
@@ -7918,7 +8056,7 @@ static auto pick_parity_finalize(int ns) {
 using EvalBatchFn = decltype(&k_eval_batch<false, false, false>);
 static EvalBatchFn pick_eval_batch(bool ds, bool numa, bool cpu, bool hint, bool ext, int ns) {
   if (!ds && !numa && !cpu)
-    return with_ns_ext(ns, ext, [](auto NS, auto EXT) -> EvalBatchFn {
+    return with_nsg_ext(ns, ext, [](auto NS, auto EXT) -> EvalBatchFn {
       return k_eval_batch<false, false, false, KV(EXT), false, KV(NS)>;
     });
   if (ns) return nullptr;
@@ -7930,7 +8068,7 @@ static EvalBatchFn pick_eval_batch(bool ds, bool numa, bool cpu, bool hint, bool
   });
 }
 static auto pick_eval_plain(bool ext, int ns) {
-  return with_ns_ext(ns, ext, [](auto NS, auto EXT) { return k_eval_plain<KV(EXT), KV(NS)>; });
+  return with_nsg_ext(ns, ext, [](auto NS, auto EXT) { return k_eval_plain<KV(EXT), KV(NS)>; });
 }
 static auto pick_patch(bool ext, int ns) {
   return with_ns_ext(ns, ext, [](auto NS, auto EXT) { return k_patch<KV(EXT), KV(NS)>; });
@@ -7947,7 +8085,8 @@ static auto pick_fixlist(bool ext, bool parts, int ns) {
 // DS x NUMA x QUOTA, and NS for the plain instantiation
 using ResolveFn = decltype(&k_resolve<false, false, false>);
 static ResolveFn pick_resolve(bool ds, bool numa, bool quota, int ns) {
-  if (!ds && !numa && !quota) return with_ns(ns, [](auto NS) -> ResolveFn { return k_resolve<false, false, false, KV(NS)>; });
+  if (!ds && !numa && !quota)
+    return with_nsg_ext(ns, false, [](auto NS, auto) -> ResolveFn { return k_resolve<false, false, false, KV(NS)>; });
   if (ns) return nullptr;
   return with_bool(ds, [&](auto DS) {
     return with_bool(numa, [&](auto NUMA) {
@@ -7980,7 +8119,10 @@ static DiagEvalFn pick_diag_eval(bool numa, bool cpu, int ns) {
   if (ns == NS_SCORES) return nullptr;
   return with_bool(ns != 0, [&](auto SETS) {
     return with_bool(numa, [&](auto NUMA) {
-      return with_bool(cpu, [&](auto CPU) -> DiagEvalFn { return k_diag_eval<KV(NUMA), KV(CPU), KV(SETS) ? NS_SETS : 0>; });
+      return with_bool(cpu, [&](auto CPU) -> DiagEvalFn {
+        if (ns == NS_GROUPS) return k_diag_eval<KV(NUMA), KV(CPU), NS_GROUPS>;
+        return k_diag_eval<KV(NUMA), KV(CPU), KV(SETS) ? NS_SETS : 0>;
+      });
     });
   });
 }
@@ -8032,8 +8174,7 @@ static int pair_pass_begin(Context* ctx, int32_t n_pods, const ke_pod* pods, int
   HIP_OK(hipSetDevice(d->device));
   int rc = device_refresh(ctx, now);
   if (rc || n_pods == 0) return rc;
-  if (ns && (rc = node_sets_sync(ctx))) return rc;
-  if (ns == NS_SCORES && (rc = node_scores_sync(ctx))) return rc;
+  if ((rc = id_tables_sync(ctx, ns))) return rc;
   if ((rc = upload_pods(ctx, n_pods, pods))) return rc;
   HIP_OK(hipMemsetAsync(d->soa.kerr, 0, sizeof(int32_t), d->stream));
   pp->k = make_kargs(ctx, now);
@@ -8063,7 +8204,7 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
                 int16_t* la, int16_t* numa, int16_t* ds, int16_t* total, int32_t* best) {
   DeviceState* d = ctx->dev;
   // pods with node sets (NS_SETS) or score tables (NS_SCORES, which reads the set table too: id 0 = its row 0)
-  const int ns = ctx->nsc_call ? NS_SCORES : ctx->ns_call ? NS_SETS : 0;
+  const int ns = call_ns(ctx);  // (NS_GROUPS: spread group ids, with or without the others)
   PairPass pp;
   int rc = pair_pass_begin(ctx, n_pods, pods, now, ns, &pp);
   if (rc || n_pods == 0) return rc;
@@ -8115,7 +8256,8 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
 int device_diagnose(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, ke_pod_diagnosis* out,
                     int32_t words_per_pod, uint64_t* const* bits) {
   DeviceState* d = ctx->dev;
-  const int ns = ctx->ns_call ? NS_SETS : 0;  // (score table ids do not filter: ke_diagnose drops them)
+  // (score table ids do not filter: ke_diagnose drops them; spread groups do)
+  const int ns = ctx->sg_call ? NS_GROUPS : ctx->ns_call ? NS_SETS : 0;
   PairPass pp;
   int rc = pair_pass_begin(ctx, n_pods, pods, now, ns, &pp);
   if (rc || n_pods == 0) return rc;
@@ -8237,6 +8379,7 @@ struct Completion {
   bool behind;  // (ke_schedule_submit: enqueued behind a call in flight)
   int64_t copies, fills;
   int n_pipelined;
+  std::vector<int32_t> groups;  // the call's spread group ids (empty: none): the host copy takes its placements' increments
 };
 
 static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
@@ -8285,6 +8428,13 @@ static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
   if (kerr & (KERR_HINT_ROUTE | KERR_LDS_WAIT)) {  // internal errors: the placements are not the reference's
     return fail(KE_ERR_DEVICE, (kerr & KERR_LDS_WAIT) ? "internal: a replay LDS wait expired (placements invalid)"
                                                       : "internal: a hinted pod reached a kernel without the hint path");
+  }
+  // spread groups: the increments the device's Reserves made, on the host copy (placements of an unsharded context:
+  // chosen is the node index)
+  for (size_t p = 0; p < c.groups.size(); p++) {
+    const int32_t g = c.groups[p], node = chosen[p];
+    if (g > 0 && g <= ctx->sg_n && node >= 0 && (int64_t)node < ctx->sg_stride)
+      ctx->sg_cnt[(size_t)((int64_t)(g - 1) * ctx->sg_stride + node)]++;
   }
   float ms = 0;
   HIP_OK(hipEventElapsedTime(&ms, c.e0, c.e1));
@@ -8346,8 +8496,10 @@ struct ScheduleCall {
   const bool matched;  // one matched pod (ke_schedule's segment of its own, or the fused one): the Reservation plugin
   // a call with node set ids (a plain queue, ke_capi.cpp take_node_sets): the NS instantiations of every kernel that
   // turns a (pod, node) pair into a score or key (NS_SETS), or with score table ids (NS_SCORES: these read the set
-  // table too, id 0 = its all-ones row 0)
+  // table too, id 0 = its all-ones row 0).  A call with spread group ids keeps that mode for its
+  // batches without a grouped pod; a grouped batch runs the NS_GROUPS instantiations (batch_ns), serially.
   const int ns;
+  const bool groups;
   // the plan
   bool fixup = false, two_es = false, ahead = false;  // the schedule of the call's pipelined runs (plan())
   std::vector<Batch> batches;
@@ -8384,7 +8536,8 @@ struct ScheduleCall {
       : ctx(ctx_), d(ctx_->dev), c(d->call), n_pods(n), pods(p), want_score(ws), N(ctx_->n_nodes), fused(ctx_->rsv_fused),
         numa(d->has(ST_NUMA)), quota(!ctx_->quotas.empty()), sharded(d->world > 1 || d->comm || d->host_fn),
         matched(!ctx_->rsv_pairs.empty() || ctx_->rsv_affinity),
-        ns(ctx_->nsc_call ? NS_SCORES : ctx_->ns_call ? NS_SETS : 0) {}
+        ns(ctx_->nsc_call ? NS_SCORES : ctx_->ns_call ? NS_SETS : 0), groups(ctx_->sg_call != nullptr) {}
+  int batch_ns(int b) const { return batches[(size_t)b].grouped ? NS_GROUPS : ns; }
 
   hipError_t copy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
     n_copies++;
@@ -8403,9 +8556,10 @@ struct ScheduleCall {
       if ((ctx->ns_call && (int64_t)ctx->ns_call_ids.size() != n_pods) ||
           (ctx->nsc_call && (int64_t)ctx->nsc_call_ids.size() != n_pods))
         return fail(KE_ERR_DEVICE, "internal: node set / score table ids of another call");
-      if ((rc = node_sets_sync(ctx))) return rc;
     }
-    if (ns == NS_SCORES && (rc = node_scores_sync(ctx))) return rc;
+    if (groups && (int64_t)ctx->sg_call_ids.size() != n_pods)
+      return fail(KE_ERR_DEVICE, "internal: spread group ids of another call");
+    if ((rc = id_tables_sync(ctx, groups ? NS_GROUPS : ns))) return rc;
     return upload_pods(ctx, n_pods, pods, (int64_t)n_pods + 1, &h_bases, &upload_bytes, &n_copies);
   }
 
@@ -8414,7 +8568,7 @@ struct ScheduleCall {
     // the knob is read per call: tests set it between contexts of one process
     knob = select_knob(std::getenv("KOORDEVAL_SELECT_PARTS"));
     ctx->last_ds_cuts = 0;
-    batches = plan_batches(c.host_pods.data(), n_pods, ctx->cfg.pod_batch, !sharded && !numa && N > 0, fused);
+    batches = plan_batches(c.host_pods.data(), n_pods, ctx->cfg.pod_batch, !sharded && !numa && N > 0, fused, ctx->sg_call);
     for (const Batch& b : batches) any_cpu = any_cpu || b.cpu;
     if (any_cpu && !d->has(ST_CPU)) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
     n_batches = (int)batches.size();
@@ -8521,7 +8675,7 @@ struct ScheduleCall {
   // the bookkeeping words, the one copy of everything the call uploads, the call's events, and k_call_begin
   int begin() {
     RC_OK(c.d_sched.reserve((size_t)sl.total));
-    d_bases = reinterpret_cast<int32_t*>(c.d_pods + n_pods) + (ns ? n_pods : 0);
+    d_bases = reinterpret_cast<int32_t*>(c.d_pods + n_pods) + (ns || groups ? n_pods : 0) + (groups ? n_pods : 0);
     d_ready = c.d_sched + sl.ready, d_done = c.d_sched + sl.done, d_tready = c.d_sched + sl.tready;
     d_sstart = c.d_sched + sl.sstart, d_rres = c.d_sched + sl.rres, d_tlist = c.d_sched + sl.tlist;
     d_tmx = reinterpret_cast<uint32_t*>(c.d_sched + sl.tmx);
@@ -8618,7 +8772,7 @@ struct ScheduleCall {
       // was measured slower: 256 select workgroups spinning on the flag)
       if (a.pwait)
         hipLaunchKernelGGL(pick_patch(ext, ns), dim3((unsigned)bp), dim3(64), d->excl_lds, es, d->soa, c.d_pods, bbase, k,
-                           a.ptl, eb.scores, d->capacity, a.pwait, d_err);
+                           a.ptl, eb.scores, d->capacity, a.pwait, d_err);  // (a run's batch: never grouped)
       if (ds && sharded && !d->loopback) {  // DefaultNormalizeScore's max over the feasible nodes of all ranks
         if ((rc = coll_all_reduce(d, d->d_dsmax, 1, KE_COLL_U32, KE_COLL_MAX, es))) return rc;
       }
@@ -8640,10 +8794,10 @@ struct ScheduleCall {
     const dim3 grid = eval_grid(hi - lo, blk, bp, EVAL_PPB);
     const DeferBufs df{defer.list, defer.fb, numa ? defer.cnt + b : nullptr};  // (the batch's own counter)
     if (plain_rec) {  // plain batch: the record-based evaluation
-      hipLaunchKernelGGL(pick_eval_plain(ext, ns), grid, dim3(blk), 0, a.es, d->soa, lo, hi, c.d_pods, bbase, bp, k,
+      hipLaunchKernelGGL(pick_eval_plain(ext, batch_ns(b)), grid, dim3(blk), 0, a.es, d->soa, lo, hi, c.d_pods, bbase, bp, k,
                          eb.scores, d->capacity, stamp, dwait, d_err);
     } else {
-      const auto eval = pick_eval_batch(ds, numa, cpu, batches[b].hint, ext, ns);
+      const auto eval = pick_eval_batch(ds, numa, cpu, batches[b].hint, ext, batch_ns(b));
       if (!eval) return no_variant("k_eval_batch with node sets and a DeviceShare / NUMA / cpuset batch");
       hipLaunchKernelGGL(eval, grid, dim3(blk), 0, a.es, d->soa, lo, hi, c.d_pods, bbase, bp, EVAL_PPB, k, eb.scores,
                          d->capacity, d->d_dsraw, d->d_defer, df.cnt, d->d_aff, d->d_dsmax, stamp);
@@ -8834,7 +8988,9 @@ struct ScheduleCall {
       hipLaunchKernelGGL(k_rsv_gate_apply, dim3(1), dim3(64), 0, d->stream, d->d_rsv_gate, d->d_cand_cnt);
       HIP_OK(copy_async(d->h_rsv_out.data() + 4, d->d_rsv_gate, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
     }
-    if (bp == 1) {  // one pod: the single-node Reserve (cpuset accumulator when it binds)
+    // one pod: the single-node Reserve (cpuset accumulator when it binds) -- but a grouped singleton takes the
+    // replay, which keeps the spread group counts
+    if (bp == 1 && !batches[b].grouped) {
       int elo = 0, ehi = 0;  // nodes whose affinities this batch's eval stored in d_aff (binding batches)
       if (cpu && numa) {
         ehi = N;
@@ -8844,7 +9000,7 @@ struct ScheduleCall {
                          d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score, ctx->cfg.global_node_offset, d_st, d_pst, b,
                          c.d_devalloc, numa ? c.d_numaalloc : nullptr, c.d_cpusets, d->d_aff, elo, ehi);
     } else {
-      const auto resolve = pick_resolve(ds, numa, quota, ns);
+      const auto resolve = pick_resolve(ds, numa, quota, batch_ns(b));
       if (!resolve) return no_variant("k_resolve with node sets and a DeviceShare batch, NUMA or quota");
       hipLaunchKernelGGL(resolve, dim3(1), dim3(resolve_threads(numa)), 0, d->stream, d->soa, c.d_pods, bbase, bp, k,
                          d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score, ctx->cfg.global_node_offset, d_st, d_pst, b,
@@ -8930,6 +9086,7 @@ struct ScheduleCall {
     cp.flush_ms = flush_ms;
     cp.entry = ctx->call_entry, cp.behind = ctx->call_behind;
     cp.copies = n_copies, cp.fills = n_fills, cp.n_pipelined = n_pipelined;
+    if (groups) cp.groups.assign(ctx->sg_call, ctx->sg_call + n_pods);
     *fin = [cp = std::move(cp)](int32_t* chosen, int32_t* score) { return complete_call(cp, chosen, score); };
     return KE_OK;
   }
@@ -9067,6 +9224,24 @@ int device_check_records(Context* ctx, int64_t now, int64_t* bad) {
   HIP_OK(hipMemcpyAsync(&h, dbad, sizeof(h), hipMemcpyDeviceToHost, d->stream));
   HIP_OK(hipStreamSynchronize(d->stream));
   *bad = (int64_t)h;
+  return KE_OK;
+}
+
+// the device's spread group table against the host copy (test of the Reserves' increments and the completion's)
+int device_spread_groups_check(Context* ctx, int64_t* bad) {
+  DeviceState* d = ctx->dev;
+  *bad = 0;
+  if (!d->d_sg_tbl || ctx->sg_dirty) return KE_OK;  // (no device copy, or one the next call replaces)
+  HIP_OK(hipSetDevice(d->device));
+  const int64_t S = d->capacity, rows = d->sg_rows, cols = std::min(S, ctx->sg_stride);
+  if (rows != (int64_t)ctx->sg_n + 1) return fail(KE_ERR_DEVICE, "internal: the device spread group table has other rows");
+  std::vector<uint16_t> t((size_t)(rows * S + rows));
+  HIP_OK(hipMemcpyAsync(t.data(), d->d_sg_tbl, sizeof(uint16_t) * t.size(), hipMemcpyDeviceToHost, d->stream));
+  HIP_OK(hipStreamSynchronize(d->stream));
+  const std::vector<uint16_t> want = spread_groups_image(ctx, S);
+  for (const auto& gn : ctx->sg_dirty_cells)  // (patches the next call uploads: taken as sent)
+    if (gn.second < cols) t[(size_t)((int64_t)gn.first * S + gn.second)] = want[(size_t)((int64_t)gn.first * S + gn.second)];
+  for (size_t q = 0; q < t.size(); q++) *bad += t[q] != want[q];
   return KE_OK;
 }
 

@@ -71,6 +71,9 @@ struct Batch {
   bool ds, cpu;  // DeviceShare-capable batch (its pods' NormalizeScore) / singleton of a pod that may bind CPUs
   bool cut;      // a DeviceShare batch with DeviceShare pods: the replay may stop early
   bool hint;     // singleton of a pod with device hints: its eval kernel carries the hint path (H)
+  // a pod of the batch names a spread group: the batch runs serially on the one-wave sequential
+  // replay, whose Reserves increment the group's per-node counts; never part of a pipelined run
+  bool grouped = false;
 };
 
 // Batches: runs of up to B pods (exact speculative batching).  A pod that may bind CPUs is alone in
@@ -79,7 +82,10 @@ struct Batch {
 // (exact: the replay checks each pod's normalisation max and stops the batch where it may have moved)
 // when `ds_batch` -- unsharded nodes without NUMA policies -- else each is a singleton: its NormalizeScore needs
 // the max over all feasible nodes of the current state.
-inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bool ds_batch, bool fused) {
+// `group_ids` (the call's spread group id per pod, nullptr: none): the segmentation is the same with or without them; a
+// batch holding a pod with a non-zero id is marked `grouped`.
+inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bool ds_batch, bool fused,
+                                       const int32_t* group_ids = nullptr) {
   std::vector<Batch> batches;
   auto alone = [&](uint32_t f) { return (f & PF_CPUSET) || ((f & PF_DS) && !ds_batch) || (f & PF_DS_HINT); };
   for (int p = 0; p < n_pods;) {
@@ -98,6 +104,9 @@ inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bo
     batches.push_back({bp, has_ds, false, has_ds && bp > 1, false});
     p += bp;
   }
+  if (group_ids)
+    for (size_t b = 0, p = 0; b < batches.size(); p += (size_t)batches[b].pods, b++)
+      for (int q = 0; q < batches[b].pods; q++) batches[b].grouped = batches[b].grouped || group_ids[p + (size_t)q] != 0;
   return batches;
 }
 
@@ -111,12 +120,13 @@ inline std::vector<int32_t> plan_bases(const std::vector<Batch>& batches) {
 }
 
 // pipelined runs: maximal stretches of plain batches (no DeviceShare / cpuset pod, not the fused
-// one) in a context without NUMA policies; run_end[b] > 0 marks the first batch of a run and holds its end
+// one, not a grouped batch) in a context without NUMA policies; run_end[b] > 0 marks the first batch of a run and holds its end
 // (a lone plain batch between singletons gains nothing from the second stream: it runs serially)
 inline std::vector<int> plan_runs(const std::vector<Batch>& batches, bool pipeline, int n_nodes, bool numa, bool fused) {
   const int nb = (int)batches.size();
   auto eligible = [&](int b) {
-    return pipeline && n_nodes > 0 && !numa && !batches[b].ds && !batches[b].cpu && !(fused && b == nb - 1);
+    return pipeline && n_nodes > 0 && !numa && !batches[b].ds && !batches[b].cpu && !batches[b].grouped &&
+           !(fused && b == nb - 1);
   };
   std::vector<int> run_end((size_t)nb, 0);
   for (int b = 0; b < nb;) {

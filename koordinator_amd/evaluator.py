@@ -275,6 +275,54 @@ class Evaluator:
         ids = np.ascontiguousarray(table_ids, np.int32)
         self._check(self.lib.ke_pod_node_scores(self.h, len(ids), abi.ptr(ids)))
 
+    def spread_groups_load(self, counts, max_per_node, n_nodes=None):
+        """ke_spread_groups_load: replace the spread groups -- `max_per_node` the cap (>= 1) per group, `counts` a
+        [n_groups, N] matrix of the pods each group already has per node (None: all zero), zero-padded to n_nodes
+        when that is larger; group ids are 1 + the row.  No caps drop the table."""
+        caps = np.asarray(max_per_node).reshape(-1)
+        if caps.size == 0:
+            self._check(self.lib.ke_spread_groups_load(self.h, 0, 0, None, None))
+            return
+        if (caps < 0).any() or (caps > 0xFFFF).any():
+            raise ValueError("spread group cap outside 0..65535")
+        caps = np.ascontiguousarray(caps, np.uint16)
+        if counts is None:
+            n = self.num_nodes if n_nodes is None else int(n_nodes)
+            self._check(self.lib.ke_spread_groups_load(self.h, len(caps), n, None, abi.ptr(caps)))
+            return
+        c = np.atleast_2d(np.asarray(counts))
+        if c.shape[0] != len(caps):
+            raise ValueError("one row of counts per cap")
+        if (c < 0).any() or (c > 0xFFFF).any():
+            raise ValueError("spread group count outside 0..65535")
+        n = c.shape[1] if n_nodes is None else int(n_nodes)
+        if n < c.shape[1]:
+            raise ValueError("n_nodes below the counts' width")
+        v = np.zeros((c.shape[0], n), np.uint16)
+        v[:, :c.shape[1]] = c
+        self._check(self.lib.ke_spread_groups_load(self.h, len(caps), n, abi.ptr(v), abi.ptr(caps)))
+
+    def spread_group_add(self, group, node, delta):
+        """ke_spread_group_add: count[group][node] += delta (an informer pod event, or -1 to undo a placement)."""
+        self._check(self.lib.ke_spread_group_add(self.h, int(group), int(node), int(delta)))
+
+    def spread_groups_get(self, group, n_nodes):
+        """ke_spread_groups_get: group `group`'s current count per node, every Reserve included."""
+        out = np.zeros(int(n_nodes), np.uint16)
+        self._check(self.lib.ke_spread_groups_get(self.h, int(group), len(out), abi.ptr(out) if len(out) else None))
+        return out
+
+    def pod_spread_groups(self, ids):
+        """ke_pod_spread_groups: the spread group id (0 = none) per pod of the next eval / diagnose / schedule / submit."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        self._check(self.lib.ke_pod_spread_groups(self.h, len(ids), abi.ptr(ids)))
+
+    def debug_spread_groups_check(self):
+        """ke_debug_spread_groups_check: entries of the device's spread group table that differ from the host copy."""
+        n = C.c_int64()
+        self._check(self.lib.ke_debug_spread_groups_check(self.h, C.byref(n)))
+        return n.value
+
     def node_info_requested(self, i):
         """ke_node_info_requested: NodeInfo Requested / NonZeroRequested (MilliCPU, Memory) after the restore."""
         req, nz = (C.c_int64 * 2)(), (C.c_int64 * 2)()
@@ -358,14 +406,16 @@ class Evaluator:
         return lo.value, hi.value
 
     # ---- evaluation -------------------------------------------------------------------------
-    def eval(self, pods, now_ns, node_sets=None, node_scores=None):
+    def eval(self, pods, now_ns, node_sets=None, node_scores=None, spread_groups=None):
         """ke_eval; `node_sets` (optional): the node set id per pod (0 = every node); `node_scores` (optional): the
-        score table id per pod (0 = no offset)."""
+        score table id per pod (0 = no offset); `spread_groups` (optional): the spread group id per pod (0 = none)."""
         pods = as_pod_array(pods)
         if node_sets is not None:
             self.pod_node_sets(node_sets)
         if node_scores is not None:
             self.pod_node_scores(node_scores)
+        if spread_groups is not None:
+            self.pod_spread_groups(spread_groups)
         P, N = len(pods), self.num_nodes
         out = {
             "status": np.zeros((P, N), np.uint8),
@@ -381,14 +431,17 @@ class Evaluator:
                                      abi.ptr(out["ds"]), abi.ptr(out["total"]), abi.ptr(out["best"])))
         return out
 
-    def diagnose(self, pods, now_ns, node_sets=None, bitmaps=False):
+    def diagnose(self, pods, now_ns, node_sets=None, bitmaps=False, spread_groups=None):
         """ke_diagnose: per pod the reductions of eval()'s status / reason over every node, computed on the device
         with nothing per pair copied back -- int32 [P] arrays n_nodes, n_absent, n_feasible, n_unschedulable,
         n_unresolvable, n_error, uint32 [P] plugins (abi.PLUGIN_* bits), int32 [P, 128] reason_nodes; with
-        `bitmaps` also the bool [P, N] matrices feasible, unschedulable, unresolvable.  `node_sets` as for eval()."""
+        `bitmaps` also the bool [P, N] matrices feasible, unschedulable, unresolvable.  `node_sets` and `spread_groups`
+        as for eval()."""
         pods = as_pod_array(pods)
         if node_sets is not None:
             self.pod_node_sets(node_sets)
+        if spread_groups is not None:
+            self.pod_spread_groups(spread_groups)
         P, N = len(pods), self.num_nodes
         rec = np.zeros(P, abi.POD_DIAGNOSIS_DTYPE)
         wpp = (N + 63) // 64
@@ -401,10 +454,10 @@ class Evaluator:
             out[k] = unpack_node_sets(w, N)
         return out
 
-    def schedule(self, pods, now_ns, matches=None, node_sets=None, node_scores=None):
+    def schedule(self, pods, now_ns, matches=None, node_sets=None, node_scores=None, spread_groups=None):
         """ke_schedule; `matches` (optional): per pod the reservation indices it matches (KE_RSV_MATCHED pods);
         `node_sets` (optional): the node set id per pod (0 = every node); `node_scores` (optional): the score table
-        id per pod (0 = no offset)."""
+        id per pod (0 = no offset); `spread_groups` (optional): the spread group id per pod (0 = none)."""
         pods = as_pod_array(pods)
         if matches is not None:
             self.pod_reservations(matches)
@@ -412,20 +465,25 @@ class Evaluator:
             self.pod_node_sets(node_sets)
         if node_scores is not None:
             self.pod_node_scores(node_scores)
+        if spread_groups is not None:
+            self.pod_spread_groups(spread_groups)
         chosen = np.zeros(len(pods), np.int32)
         score = np.zeros(len(pods), np.int32)
         self._check(self.lib.ke_schedule(self.h, len(pods), abi.ptr(pods), int(now_ns), abi.ptr(chosen), abi.ptr(score)))
         self._last_n, self._last_out = len(pods), {}  # the per-pod allocations are read on first access
         return chosen, score
 
-    def submit(self, pods, now_ns, node_sets=None, node_scores=None):
+    def submit(self, pods, now_ns, node_sets=None, node_scores=None, spread_groups=None):
         """ke_schedule_submit: enqueue a queue slice behind the calls in flight; returns its ticket (wait() collects
-        it).  The pod array is kept alive here until then.  `node_sets` and `node_scores` as for schedule()."""
+        it).  The pod array is kept alive here until then.  `node_sets`, `node_scores` and `spread_groups` as for
+        schedule()."""
         pods = as_pod_array(pods)
         if node_sets is not None:
             self.pod_node_sets(node_sets)
         if node_scores is not None:
             self.pod_node_scores(node_scores)
+        if spread_groups is not None:
+            self.pod_spread_groups(spread_groups)
         t = C.c_int64()
         self._check(self.lib.ke_schedule_submit(self.h, len(pods), abi.ptr(pods), int(now_ns), C.byref(t)))
         self._inflight[t.value] = pods
