@@ -969,7 +969,7 @@ int ke_pod_node_scores(ke_ctx* ctx, int32_t n_pods, const int32_t* table_ids);
  *  - ke_eval and ke_diagnose read the counts and change nothing.
  *  - ke_unreserve and ke_pod_release do NOT touch the counts: the caller undoes a placement's increment with
  *    ke_spread_group_add(ctx, group, node, -1).
- * Only the hostname topology is covered (a zone-level count would change eligibility on nodes nobody Reserved).
+ * Only the hostname topology is covered here; zone / rack level maxSkew spreading is the spread domains' below.
  * A ke_schedule / ke_schedule_submit call with a non-zero group id must be a plain queue exactly as one with a
  * non-zero node set id (above); anything else is KE_ERR_UNSUPPORTED before any state changes ("spread groups:
  * ...", or the node sets' / node scores' message when a set or table id of the call is non-zero too).  ke_eval and
@@ -992,6 +992,54 @@ int ke_spread_groups_get(ke_ctx* ctx, int32_t group, int32_t n_nodes, uint16_t* 
  * a following call with a different n_pods, or after the table was replaced by a smaller one, is KE_ERR_INVALID.
  * Does not wait for calls in flight. */
 int ke_pod_spread_groups(ke_ctx* ctx, int32_t n_pods, const int32_t* group_ids);
+/* ---- spread domains: zone-level maxSkew that follows every Reserve (additive: KE_ABI_VERSION stays 14) ---
+ * A topologySpreadConstraint with whenUnsatisfiable: DoNotSchedule on a topology key other than the hostname
+ * (topology.kubernetes.io/zone, a rack label): whether a domain is open to replica j depends on where replicas
+ * 0 .. j-1 went.  The semantics are upstream PodTopologySpread's Filter (k8s v1.28), fixed here by convention like the
+ * other in-tree filters.
+ *  - A domain map m (1..n_maps <= KE_MAX_SPREAD_DOMAIN_MAPS) gives every node a domain id 0..63 or KE_DOMAIN_NONE (the
+ *    node lacks the topology key).
+ *  - A spread domain group g (1..n_groups <= KE_MAX_SPREAD_DOMAIN_GROUPS) has a map, a uint64 `domains` bitmask (the
+ *    domains that pass the pod's node affinity: the minimum ranges over these; at least one bit), max_skew >= 1,
+ *    min_domains >= 0 and a uint32 pod count per domain, seeded by the caller.  A pod of a call may name one group
+ *    (id 0 = none), independently of its spread group id above.
+ *  - Filter: min = popcount(domains) < min_domains ? 0 : the least count[g][d] over d in domains.  Node n with
+ *    d = map[n] is filtered for the pod when d is KE_DOMAIN_NONE, when d is not in domains, or when
+ *    count[g][d] + 1 - min > max_skew.  A filtered pair reports exactly as a capped spread group pair
+ *    (KE_REASON_NODE_SET, KE_PLUGIN_NODE_SET, unresolvable, plugin scores 0, total -1), behind the set test and the
+ *    cap test and ahead of every koordinator filter; never a deferred pair.
+ *  - Reserve: a placement on node n does count[g][map[n]] += 1; every later pod sees it -- of later batches, later
+ *    calls, slices submitted ahead (a batch holds at most one pod of a group).  An unplaced pod changes nothing.
+ *  - ke_eval and ke_diagnose read the counts and change nothing.
+ *  - ke_unreserve and ke_pod_release do NOT touch the counts: the caller undoes a placement with
+ *    ke_spread_domain_add(ctx, group, domain, -1).
+ * A ke_schedule / ke_schedule_submit call with a non-zero id must be a plain queue exactly as one with a non-zero
+ * node set id; anything else is KE_ERR_UNSUPPORTED before any state changes ("spread domains: ...", or the node
+ * sets' / node scores' / spread groups' message when such an id of the call is non-zero too). */
+#define KE_MAX_SPREAD_DOMAIN_GROUPS 1024
+#define KE_MAX_SPREAD_DOMAINS 64
+#define KE_MAX_SPREAD_DOMAIN_MAPS 8
+#define KE_DOMAIN_NONE 0xFFFF
+/* Replace maps and groups: map m's domain ids are n_nodes uint16 at node_domain + (m-1)*n_nodes (a value >= 64 other
+ * than KE_DOMAIN_NONE is KE_ERR_INVALID; nodes at or beyond n_nodes are KE_DOMAIN_NONE); group g has map
+ * group_map[g-1] in 1..n_maps, the bitmask domains[g-1] != 0, max_skew[g-1] >= 1, min_domains[g-1] >= 0 (min_domains
+ * NULL = all zero) and the 64 counts at counts + (g-1)*64 (counts NULL = all zero; each <= 2^31-1).  n_groups = 0 drops
+ * the table.  A refused load leaves the table as it was.  Completes calls in flight first. */
+int ke_spread_domains_load(ke_ctx* ctx, int32_t n_maps, int32_t n_nodes, const uint16_t* node_domain, int32_t n_groups,
+                           const int32_t* group_map, const uint64_t* domains, const int32_t* max_skew,
+                           const int32_t* min_domains, const uint32_t* counts);
+/* count[group][domain] += delta; a count clamps at 0, a count that would pass 2^31-1 is KE_ERR_INVALID and changes
+ * nothing.  group in 1..n_groups, domain in 0..63 (KE_ERR_NOT_FOUND otherwise).  Completes calls in flight first. */
+int ke_spread_domain_add(ke_ctx* ctx, int32_t group, int32_t domain, int32_t delta);
+/* map[node] = domain (0..63 or KE_DOMAIN_NONE: KE_ERR_INVALID otherwise) for a node the informer adds or relabels;
+ * map in 1..n_maps, node a node index of the context (KE_ERR_NOT_FOUND otherwise).  The counts are the caller's to
+ * correct.  Completes calls in flight first. */
+int ke_spread_domain_node_set(ke_ctx* ctx, int32_t map, int32_t node, int32_t domain);
+/* The current 64 counts of one group, every Reserve included.  Completes calls in flight first. */
+int ke_spread_domains_get(ke_ctx* ctx, int32_t group, uint32_t* counts64);
+/* Spread domain group id per pod for the NEXT ke_eval / ke_diagnose / ke_schedule / ke_schedule_submit of exactly
+ * n_pods pods, with ke_pod_spread_groups' rules. */
+int ke_pod_spread_domains(ke_ctx* ctx, int32_t n_pods, const int32_t* group_ids);
 /* ---- FitError diagnosis of unschedulable pods (additive: KE_ABI_VERSION stays 14) -------------------
  * A pod ke_schedule left at chosen = -1 must go back to the queue with a framework.FitError.  The reference reads
  * three parts of it, all reductions of the Filter status map (framework.NodeToStatusMap) findNodesThatFitPod fills:
@@ -1404,6 +1452,9 @@ int ke_debug_check_records(ke_ctx* ctx, int64_t now_ns, int64_t* mismatched_node
 /* Number of (group, node) entries of the device's spread group table that differ from the host's copy (which
  * ke_spread_groups_get answers from; 0 = consistent, also without a table). */
 int ke_debug_spread_groups_check(ke_ctx* ctx, int64_t* mismatched);
+/* The same for the spread domains: (group, domain) counts and (map, node) entries of the device's tables that differ
+ * from the host's copy. */
+int ke_debug_spread_domains_check(ke_ctx* ctx, int64_t* mismatched);
 /* Launch the batch eval kernel `iters` times back to back over the current node SoA for `n_pods`
  * (<= 64) pods and return the HIP-event average milliseconds per launch (roofline measurement). */
 int ke_bench_eval_kernel(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns, int32_t iters,

@@ -73,6 +73,11 @@ REASON_NODE_SET = 96  # the node is outside the pod's node eligibility set (ke_p
 MAX_NODE_SETS = 4096
 MAX_NODE_SCORE_TABLES = 1024  # ke_node_scores_load's tables (per-pod node score offsets)
 MAX_SPREAD_GROUPS = 1024  # ke_spread_groups_load's groups (per-node pod caps that follow every Reserve)
+# ke_spread_domains_load: groups, domains per map, maps; the domain id of a node without the topology key
+MAX_SPREAD_DOMAIN_GROUPS = 1024
+MAX_SPREAD_DOMAINS = 64
+MAX_SPREAD_DOMAIN_MAPS = 8
+DOMAIN_NONE = 0xFFFF
 # ke_pod.gpu_required_topology_scope (apiext.DeviceTopologyScope -> level)
 SCOPE_NONE, SCOPE_NODE, SCOPE_NUMA, SCOPE_PCIE, SCOPE_DEVICE, SCOPE_UNKNOWN = range(6)
 SCOPES = {"": SCOPE_NONE, "Node": SCOPE_NODE, "NUMANode": SCOPE_NUMA, "PCIe": SCOPE_PCIE, "Device": SCOPE_DEVICE}
@@ -586,6 +591,12 @@ EXPORTS = {
     "ke_spread_group_add": (C.c_int, [C.c_void_p, i32, i32, i32]),
     "ke_spread_groups_get": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
     "ke_pod_spread_groups": (C.c_int, [C.c_void_p, i32, C.c_void_p]),
+    "ke_spread_domains_load": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "ke_spread_domain_add": (C.c_int, [C.c_void_p, i32, i32, i32]),
+    "ke_spread_domain_node_set": (C.c_int, [C.c_void_p, i32, i32, i32]),
+    "ke_spread_domains_get": (C.c_int, [C.c_void_p, i32, C.c_void_p]),
+    "ke_pod_spread_domains": (C.c_int, [C.c_void_p, i32, C.c_void_p]),
     "ke_node_info_requested": (C.c_int, [C.c_void_p, i32, C.POINTER(i64), C.POINTER(i64)]),
     "ke_decode_pod_device_hints": (C.c_int, [C.c_char_p, i64, C.POINTER(PodDeviceHints), C.POINTER(i32)]),
     "ke_decode_device_flags": (C.c_int, [C.c_char_p, i64, C.c_char_p, i64, C.POINTER(i32), C.POINTER(i32)]),
@@ -610,6 +621,7 @@ EXPORTS = {
     "ke_debug_kernel_phases": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ke_debug_check_records": (C.c_int, [C.c_void_p, i64, C.POINTER(i64)]),
     "ke_debug_spread_groups_check": (C.c_int, [C.c_void_p, C.POINTER(i64)]),
+    "ke_debug_spread_domains_check": (C.c_int, [C.c_void_p, C.POINTER(i64)]),
     "ke_last_host_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ke_last_resolve_split": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "ke_debug_resolve_phases": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -36,6 +36,7 @@ int device_replay_phases(Context* ctx, int which, double* cyc8);
 int device_check_records(Context* ctx, int64_t now, int64_t* bad);
 // (weak: a host-only build of this file, without ke_kernels.hip, links without it -- there is no device copy to check)
 int device_spread_groups_check(Context* ctx, int64_t* bad) __attribute__((weak));
+int device_spread_domains_check(Context* ctx, int64_t* bad) __attribute__((weak));
 int device_bench_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, int32_t iters, double* avg_ms);
 int device_comm_unique_id(uint8_t* id);
 int device_shard_init(Context* ctx, int rank, int world, const uint8_t* id);
@@ -774,23 +775,124 @@ int ke_pod_spread_groups(ke_ctx* ctx, int32_t n_pods, const int32_t* group_ids) 
   return KE_OK;
 }
 
-// The ke_pod_node_sets, ke_pod_node_scores and ke_pod_spread_groups ids of this call, all consumed whether it goes on
-// or not; Context::ns_call / nsc_call / sg_call = the ids of a kind when any of them is non-zero (the device entry
-// points then run the node-set / score-offset / spread-group kernels).  Such a call is refused here, before any state
+// ---- spread domains (include/koord_eval.h): the spread groups' lifecycle ----
+int ke_spread_domains_load(ke_ctx* ctx, int32_t n_maps, int32_t n_nodes, const uint16_t* node_domain, int32_t n_groups,
+                           const int32_t* group_map, const uint64_t* domains, const int32_t* max_skew,
+                           const int32_t* min_domains, const uint32_t* counts) {
+  if (ctx) async_drain(ctx);
+  if (!ctx || n_maps < 0 || n_nodes < 0 || n_groups < 0) return fail(KE_ERR_INVALID, "ke_spread_domains_load arguments");
+  if (n_groups > KE_MAX_SPREAD_DOMAIN_GROUPS)
+    return fail(KE_ERR_INVALID, "ke_spread_domains_load: more than KE_MAX_SPREAD_DOMAIN_GROUPS groups");
+  if (n_groups > 0 && n_maps > KE_MAX_SPREAD_DOMAIN_MAPS)
+    return fail(KE_ERR_INVALID, "ke_spread_domains_load: more than KE_MAX_SPREAD_DOMAIN_MAPS maps");
+  if (n_nodes > MAX_SHARD_NODES) return fail(KE_ERR_INVALID, "ke_spread_domains_load: n_nodes");
+  Context& c = ctx->c;
+  if (n_groups > 0) {
+    if (n_maps < 1 || (n_nodes > 0 && !node_domain)) return fail(KE_ERR_INVALID, "ke_spread_domains_load: node_domain");
+    if (!group_map || !domains || !max_skew) return fail(KE_ERR_INVALID, "ke_spread_domains_load: a group array is NULL");
+    for (int64_t q = 0; q < (int64_t)n_maps * n_nodes; q++)
+      if (node_domain[q] >= KE_MAX_SPREAD_DOMAINS && node_domain[q] != KE_DOMAIN_NONE)
+        return fail(KE_ERR_INVALID, "ke_spread_domains_load: a domain id above 63");
+    for (int32_t g = 0; g < n_groups; g++) {
+      if (group_map[g] < 1 || group_map[g] > n_maps) return fail(KE_ERR_INVALID, "ke_spread_domains_load: a group's map outside 1..n_maps");
+      if (domains[g] == 0) return fail(KE_ERR_INVALID, "ke_spread_domains_load: a group without a domain");
+      if (max_skew[g] < 1) return fail(KE_ERR_INVALID, "ke_spread_domains_load: a max_skew below 1");
+      if (min_domains && min_domains[g] < 0) return fail(KE_ERR_INVALID, "ke_spread_domains_load: a negative min_domains");
+      for (int32_t d = 0; counts && d < KE_MAX_SPREAD_DOMAINS; d++)
+        if (counts[(size_t)g * KE_MAX_SPREAD_DOMAINS + (size_t)d] > (uint32_t)INT32_MAX)
+          return fail(KE_ERR_INVALID, "ke_spread_domains_load: a count above 2^31-1");
+    }
+  }
+  c.sd_n = n_groups;
+  c.sd_maps = n_groups > 0 ? n_maps : 0;
+  // (a Reserve may land on any node of the context: the host copy has an entry for each, NONE beyond n_nodes)
+  c.sd_stride = n_groups > 0 ? std::max<int64_t>(n_nodes, c.cfg.node_capacity) : 0;
+  c.sd_map.assign((size_t)c.sd_maps * (size_t)c.sd_stride, (uint16_t)KE_DOMAIN_NONE);
+  for (int32_t m = 0; m < c.sd_maps; m++)
+    std::copy(node_domain + (size_t)m * (size_t)n_nodes, node_domain + (size_t)(m + 1) * (size_t)n_nodes,
+              c.sd_map.begin() + (int64_t)m * c.sd_stride);
+  c.sd_gmap.assign(group_map, group_map + n_groups);
+  c.sd_dom.assign(domains, domains + n_groups);
+  c.sd_skew.assign(max_skew, max_skew + n_groups);
+  c.sd_mind.assign((size_t)n_groups, 0);
+  if (min_domains) std::copy(min_domains, min_domains + n_groups, c.sd_mind.begin());
+  c.sd_cnt.assign((size_t)n_groups * KE_MAX_SPREAD_DOMAINS, 0u);
+  if (counts) std::copy(counts, counts + (size_t)n_groups * KE_MAX_SPREAD_DOMAINS, c.sd_cnt.begin());
+  c.sd_dirty = true;
+  c.sd_dirty_cells.clear();
+  c.sd_dirty_nodes.clear();
+  return KE_OK;
+}
+
+int ke_spread_domain_add(ke_ctx* ctx, int32_t group, int32_t domain, int32_t delta) {
+  if (ctx) async_drain(ctx);
+  if (!ctx) return fail(KE_ERR_INVALID, "ke_spread_domain_add arguments");
+  Context& c = ctx->c;
+  if (group < 1 || group > c.sd_n) return fail(KE_ERR_NOT_FOUND, "ke_spread_domain_add: group outside 1..n_groups");
+  if (domain < 0 || domain >= KE_MAX_SPREAD_DOMAINS) return fail(KE_ERR_NOT_FOUND, "ke_spread_domain_add: domain outside 0..63");
+  uint32_t& v = c.sd_cnt[(size_t)(group - 1) * KE_MAX_SPREAD_DOMAINS + (size_t)domain];
+  const int64_t nv = std::max<int64_t>((int64_t)v + delta, 0);
+  if (nv > INT32_MAX) return fail(KE_ERR_INVALID, "ke_spread_domain_add: the count would pass 2^31-1");
+  v = (uint32_t)nv;
+  if (!c.sd_dirty) c.sd_dirty_cells.push_back({group, domain});  // (the next call with a non-zero id uploads the entry)
+  return KE_OK;
+}
+
+int ke_spread_domain_node_set(ke_ctx* ctx, int32_t map, int32_t node, int32_t domain) {
+  if (ctx) async_drain(ctx);
+  if (!ctx) return fail(KE_ERR_INVALID, "ke_spread_domain_node_set arguments");
+  Context& c = ctx->c;
+  if (map < 1 || map > c.sd_maps) return fail(KE_ERR_NOT_FOUND, "ke_spread_domain_node_set: map outside 1..n_maps");
+  if (node < 0 || (int64_t)node >= c.sd_stride) return fail(KE_ERR_NOT_FOUND, "ke_spread_domain_node_set: node index beyond the maps");
+  if ((domain < 0 || domain >= KE_MAX_SPREAD_DOMAINS) && domain != KE_DOMAIN_NONE)
+    return fail(KE_ERR_INVALID, "ke_spread_domain_node_set: domain outside 0..63 and not KE_DOMAIN_NONE");
+  c.sd_map[(size_t)(map - 1) * (size_t)c.sd_stride + (size_t)node] = (uint16_t)domain;
+  if (!c.sd_dirty) c.sd_dirty_nodes.push_back({map, node});
+  return KE_OK;
+}
+
+int ke_spread_domains_get(ke_ctx* ctx, int32_t group, uint32_t* counts64) {
+  if (ctx) async_drain(ctx);
+  if (!ctx || !counts64) return fail(KE_ERR_INVALID, "ke_spread_domains_get arguments");
+  const Context& c = ctx->c;
+  if (group < 1 || group > c.sd_n) return fail(KE_ERR_NOT_FOUND, "ke_spread_domains_get: group outside 1..n_groups");
+  std::copy(c.sd_cnt.begin() + (int64_t)(group - 1) * KE_MAX_SPREAD_DOMAINS,
+            c.sd_cnt.begin() + (int64_t)group * KE_MAX_SPREAD_DOMAINS, counts64);
+  return KE_OK;
+}
+
+int ke_pod_spread_domains(ke_ctx* ctx, int32_t n_pods, const int32_t* group_ids) {
+  if (!ctx || n_pods < 0 || (n_pods > 0 && !group_ids)) return fail(KE_ERR_INVALID, "ke_pod_spread_domains arguments");
+  Context& c = ctx->c;
+  for (int32_t p = 0; p < n_pods; p++)
+    if (group_ids[p] < 0 || group_ids[p] > c.sd_n)
+      return fail(KE_ERR_INVALID, "ke_pod_spread_domains: group id outside 0..n_groups");
+  c.sd_staged.assign(group_ids, group_ids + n_pods);
+  c.sd_staged_on = true;
+  return KE_OK;
+}
+
+// The ke_pod_node_sets, ke_pod_node_scores, ke_pod_spread_groups and ke_pod_spread_domains ids of this call, all
+// consumed whether it goes on or not; Context::ns_call / nsc_call / sg_call / sd_call = the ids of a kind when any of
+// them is non-zero (the device entry points then run the node-set / score-offset / spread-group / spread-domain kernels).  Such a call is refused here, before any state
 // changes, where those kernels are not built: node-sharded contexts, and for ke_schedule (`sched`) anything but a
 // plain queue (ke_schedule_submit's sense, with device_async_ok's conditions).  The message names the sets when a
-// set id is non-zero, else the scores when a table id is, else the spread groups.
+// set id is non-zero, else the scores when a table id is, else the spread groups, else the spread domains.
 static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool sched) {
   Context& c = ctx->c;
   c.ns_call = nullptr;
   c.nsc_call = nullptr;
   c.sg_call = nullptr;
-  const bool sets_on = c.ns_staged_on, scores_on = c.nsc_staged_on, groups_on = c.sg_staged_on;
-  if (!sets_on && !scores_on && !groups_on) return KE_OK;
-  c.ns_staged_on = c.nsc_staged_on = c.sg_staged_on = false;
+  c.sd_call = nullptr;
+  const bool sets_on = c.ns_staged_on, scores_on = c.nsc_staged_on, groups_on = c.sg_staged_on, domains_on = c.sd_staged_on;
+  if (!sets_on && !scores_on && !groups_on && !domains_on) return KE_OK;
+  c.ns_staged_on = c.nsc_staged_on = c.sg_staged_on = c.sd_staged_on = false;
   c.ns_call_ids.clear();
   c.nsc_call_ids.clear();
   c.sg_call_ids.clear();
+  c.sd_call_ids.clear();
+  if (domains_on) c.sd_call_ids.swap(c.sd_staged);
+  c.sd_staged.clear();
   if (sets_on) c.ns_call_ids.swap(c.ns_staged);
   if (scores_on) c.nsc_call_ids.swap(c.nsc_staged);
   if (groups_on) c.sg_call_ids.swap(c.sg_staged);
@@ -803,7 +905,9 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
     return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_node_scores ids'");
   if (groups_on && (int32_t)c.sg_call_ids.size() != n_pods)
     return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_spread_groups ids'");
-  bool any = false, any_sc = false, any_sg = false;
+  if (domains_on && (int32_t)c.sd_call_ids.size() != n_pods)
+    return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_spread_domains ids'");
+  bool any = false, any_sc = false, any_sg = false, any_sd = false;
   for (int32_t id : c.ns_call_ids) {
     if (id < 0 || id > c.ns_n) return fail(KE_ERR_INVALID, "a staged node set id is outside the table loaded since");
     any = any || id != 0;
@@ -816,11 +920,16 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
     if (id < 0 || id > c.sg_n) return fail(KE_ERR_INVALID, "a staged spread group id is outside the table loaded since");
     any_sg = any_sg || id != 0;
   }
-  if (!any && !any_sc && !any_sg) return KE_OK;
+  for (int32_t id : c.sd_call_ids) {
+    if (id < 0 || id > c.sd_n) return fail(KE_ERR_INVALID, "a staged spread domain group id is outside the table loaded since");
+    any_sd = any_sd || id != 0;
+  }
+  if (!any && !any_sc && !any_sg && !any_sd) return KE_OK;
   int rc = check_pods(pods, n_pods, &c, sched);
   if (rc) return rc;
-  auto no = [any, any_sc](const char* what) {
-    return fail(KE_ERR_UNSUPPORTED, std::string(any ? "node sets: " : any_sc ? "node scores: " : "spread groups: ") + what);
+  auto no = [any, any_sc, any_sg](const char* what) {
+    return fail(KE_ERR_UNSUPPORTED,
+                std::string(any ? "node sets: " : any_sc ? "node scores: " : any_sg ? "spread groups: " : "spread domains: ") + what);
   };
   if (c.cfg.global_node_offset != 0 || (c.dev && device_sharded(&c))) return no("a node-sharded context");
   if (sched) {
@@ -840,6 +949,7 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
   if (any) c.ns_call = c.ns_call_ids.data();
   if (any_sc) c.nsc_call = c.nsc_call_ids.data();
   if (any_sg) c.sg_call = c.sg_call_ids.data();
+  if (any_sd) c.sd_call = c.sd_call_ids.data();
   return KE_OK;
 }
 
@@ -1781,6 +1891,14 @@ int ke_debug_spread_groups_check(ke_ctx* ctx, int64_t* mismatched) {
   *mismatched = 0;
   if (!ctx->c.dev || !device_spread_groups_check) return KE_OK;  // (no device copy yet)
   return device_spread_groups_check(&ctx->c, mismatched);
+}
+
+int ke_debug_spread_domains_check(ke_ctx* ctx, int64_t* mismatched) {
+  if (ctx) async_drain(ctx);
+  if (!ctx || !mismatched) return fail(KE_ERR_INVALID, "ke_debug_spread_domains_check arguments");
+  *mismatched = 0;
+  if (!ctx->c.dev || !device_spread_domains_check) return KE_OK;  // (no device copy yet)
+  return device_spread_domains_check(&ctx->c, mismatched);
 }
 
 int ke_set_pipeline(ke_ctx* ctx, int32_t on) {

@@ -262,6 +262,24 @@ struct Context {
   bool sg_staged_on = false;
   std::vector<int32_t> sg_call_ids;
   const int32_t* sg_call = nullptr;
+  // Spread domains (ke_spread_domains_load), with the same lifecycle: the maps as loaded (sd_maps rows
+  // of sd_stride uint16 domain ids, map m = row m - 1, KE_DOMAIN_NONE at and beyond the loaded n_nodes; sd_stride covers
+  // the node capacity), the groups' parameters and their counts (sd_n rows of 64, group g = row g - 1).  A call's
+  // completion adds its placements to the counts as the device's Reserves did.  What of the device copy is stale: all
+  // of it, or the (group, domain) counts ke_spread_domain_add and the (map, node) entries ke_spread_domain_node_set
+  // patched.  The ke_pod_spread_domains staging and the ids of the call in progress, as for the spread groups.
+  int32_t sd_maps = 0, sd_n = 0;
+  int64_t sd_stride = 0;
+  std::vector<uint16_t> sd_map;
+  std::vector<int32_t> sd_gmap, sd_skew, sd_mind;
+  std::vector<uint64_t> sd_dom;
+  std::vector<uint32_t> sd_cnt;
+  bool sd_dirty = false;
+  std::vector<std::pair<int32_t, int32_t>> sd_dirty_cells, sd_dirty_nodes;
+  std::vector<int32_t> sd_staged;
+  bool sd_staged_on = false;
+  std::vector<int32_t> sd_call_ids;
+  const int32_t* sd_call = nullptr;
   // the KE_RSV_MATCHED pod of the current segment: its nodes with matched reservations, their
   // (node, ScoreReservation of the nominated one, smallest order) for the device pick, the nominated index
   std::vector<int32_t> rsv_nodes;

@@ -59,6 +59,12 @@ inline dim3 eval_grid(int n_nodes, int block, int pods, int ppb) {
   return dim3((unsigned)((tiles + 7) / 8 * 8), (unsigned)((pods + ppb - 1) / ppb));
 }
 
+// a spread domain group's parameters as the device reads them: the domains the minimum ranges over,
+// the map's row in SoA::sd_map
+struct SdGroup {
+  uint64_t domains;
+  int32_t max_skew, min_domains, map, pad;
+};
 struct SoA {
   int64_t* f;       // NUM_I64_FIELDS arrays of `stride` int64
   uint32_t* flags;  // `stride` u32
@@ -109,11 +115,22 @@ struct SoA {
   uint16_t* sg_cnt;
   const uint16_t* sg_cap;
   const int32_t* sg_ids;
+  // spread domains: rows 0 .. n_maps of sd_stride (= the node capacity) uint16 domain ids (row 0 all
+  // zero), rows 0 .. n_groups of 64 uint32 pod counts, the groups' parameters (row 0: map 0, every domain, a max_skew
+  // no count reaches, so group id 0 needs no branch); the current call's group id per pod and the pods' eligible-domain
+  // masks, which k_domain_masks computes ahead of every eval that reads them.  Read only by the NS_DOMAINS
+  // instantiations; the one-wave replay of a grouped batch increments the count of every (group, domain) it Reserves.
+  int32_t sd_stride;
+  const uint16_t* sd_map;
+  uint32_t* sd_cnt;
+  const SdGroup* sd_par;
+  const int32_t* sd_ids;
+  uint64_t* sd_mask;
 };
 // NS, the template mode of every kernel that makes a score or key: 0 = the call has no per-pod ids, NS_SETS = its
 // ns_ids words are node set ids, NS_SCORES = they are (score table id << 16) | node set id, NS_GROUPS = NS_SCORES and
-// the pods' spread groups (sg_ids) besides
-constexpr int NS_SETS = 1, NS_SCORES = 2, NS_GROUPS = 3;
+// the pods' spread groups (sg_ids) besides, NS_DOMAINS = NS_GROUPS and the pods' spread domain groups (sd_ids)
+constexpr int NS_SETS = 1, NS_SCORES = 2, NS_GROUPS = 3, NS_DOMAINS = 4;
 // node `node` is in the set of id word `idw` (NS instantiations; every node < 64 * ns_wps is in bounds, the ids
 // checked by the host)
 template <int NS>
@@ -125,6 +142,16 @@ __device__ __forceinline__ bool ns_ok(const SoA& s, int idw, int node) {
 // load, for the eval kernels: the counts change only in the one-wave replay of an earlier launch on their stream
 __device__ __forceinline__ bool sg_capped(const SoA& s, int gid, int node) {
   return s.sg_cnt[(int64_t)gid * s.sg_stride + node] >= s.sg_cap[gid];
+}
+// the domain of `node` in map row `map` is in `mask`, a pod's eligible-domain mask (NS_DOMAINS; node < sd_stride; a
+// node without the topology key, KE_DOMAIN_NONE, is in no mask).  Maps do not change during a call
+__device__ __forceinline__ bool sd_in_mask(const SoA& s, int map, uint64_t mask, int node) {
+  const uint32_t d = s.sd_map[(int64_t)map * s.sd_stride + node];
+  return d < 64u && ((mask >> d) & 1ull);
+}
+// ... of pod `p` of the call (wave-uniform p: scalar loads of the pod's group, its map and the pod's mask)
+__device__ __forceinline__ bool sd_ok(const SoA& s, int p, int node) {
+  return sd_in_mask(s, s.sd_par[s.sd_ids[p]].map, s.sd_mask[p], node);
 }
 // a fresh key of (pod with set `sid`, node): 0 (filtered) outside the set
 template <int NS>
@@ -3275,10 +3302,31 @@ struct BatchOut {
   }
 };
 
+// Spread domains, the one place with the skew arithmetic: the eligible-domain mask of pods
+// [base, base + n) of the call, one wave a pod.  Lane d holds count[g][d] of the pod's group g; the minimum runs over
+// the group's `domains` (0 when they are fewer than min_domains), and domain d is open when it is one of them and
+// count + 1 - min <= max_skew (upstream PodTopologySpread's Filter).  Group 0 (row 0: zero counts, every domain, a
+// max_skew no count reaches) gives all ones.  Launched on the stream of the eval that reads the masks, ahead of it and
+// behind the previous batch's Reserves, whose increments it sees at the kernel boundary; the counts of a group do not
+// change while a batch with a pod of it runs (one pod of a group per batch, ke_plan.h).
+__global__ __launch_bounds__(64) void k_domain_masks(SoA s, int base, int n) {
+  if ((int)blockIdx.x >= n) return;
+  const int p = base + (int)blockIdx.x, lane = threadIdx.x;
+  const int g = s.sd_ids[p];
+  const SdGroup gp = s.sd_par[g];
+  const uint32_t cnt = ld_sc1(s.sd_cnt + (int64_t)g * 64 + lane);
+  const bool in = (gp.domains >> lane) & 1ull;
+  // (min = ~max(~x); counts stay below 2^31, so count + 1 - min does not wrap)
+  uint32_t mn = ~wave_max_u32(in ? ~cnt : 0u);
+  if ((int)__popcll(gp.domains) < gp.min_domains) mn = 0;
+  const uint64_t open = __ballot(in && (int64_t)cnt + 1 - (int64_t)mn <= (int64_t)gp.max_skew);
+  if (lane == 0) s.sd_mask[p] = open;
+}
+
 // The classification ke_eval and ke_diagnose share, of (pod p, node i) in the first pass: the pod's node set ahead of
 // every other filter (NS: the call carries ids; a pair outside the set is KE_REASON_NODE_SET -- scores 0, total -1,
 // never deferred, and not part of the pod's DeviceShare normalisation max), with NS_GROUPS the pod's spread group cap
-// right behind it (same report), then eval_pair; *deferred: the pair is
+// right behind it and with NS_DOMAINS the pod's eligible domains behind that (same report), then eval_pair; *deferred: the pair is
 // left to k_numa_fallback / k_numa_finish (o.status == STATUS_DEFERRED).
 template <bool NUMA, bool CPU, int NS>
 __device__ __forceinline__ EvalOut classify_pair(const SoA& s, const NodeRegs& n, bool expired, const DevPod* pods, int p,
@@ -3287,7 +3335,10 @@ __device__ __forceinline__ EvalOut classify_pair(const SoA& s, const NodeRegs& n
   bool out_of_set = NS && !ns_ok<NS>(s, s.ns_ids[p], i);  // (one table word a wave: the lanes' addresses are equal)
   // NS_GROUPS: a node where the pod's spread group has reached its cap reports as one outside the set (the lanes read
   // 64 consecutive counts of a wave-uniform row)
-  if constexpr (NS == NS_GROUPS) out_of_set = out_of_set || sg_capped(s, s.sg_ids[p], i);
+  if constexpr (NS >= NS_GROUPS) out_of_set = out_of_set || sg_capped(s, s.sg_ids[p], i);
+  // NS_DOMAINS: so does a node whose domain is closed to the pod's spread domain group (64 consecutive domain ids of a
+  // wave-uniform map row against the pod's mask)
+  if constexpr (NS == NS_DOMAINS) out_of_set = out_of_set || !sd_ok(s, p, i);
   if (out_of_set) {
     EvalOut o;
     o.status = KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE;
@@ -3305,8 +3356,9 @@ __device__ __forceinline__ EvalOut classify_pair(const SoA& s, const NodeRegs& n
 // parity mode: the full status / score matrices of `out`, every pair classified by classify_pair (an empty slot by
 // eval_pair's own NF_VALID test, behind the node-set gate).
 // IDS: the call carries per-pod ids (SoA::ns_ids): the low half of a word is the pod's node set (the high half, a
-// score table id, is k_parity_finalize's).  GRP: it carries spread group ids too (NS_GROUPS).
-template <bool NUMA, bool CPU, bool IDS = false, bool GRP = false>
+// score table id, is k_parity_finalize's).  GRP: it carries spread group ids too (NS_GROUPS); DOM: and spread domain
+// group ids (NS_DOMAINS).
+template <bool NUMA, bool CPU, bool IDS = false, bool GRP = false, bool DOM = false>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, const DevPod* __restrict__ pods, int n_pods,
                                                             int pods_per_block, KArgs k, ParityOut out,
                                                             uint64_t* defer_list, uint32_t* defer_cnt) {
@@ -3327,7 +3379,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, const DevPod*
     uint32_t m = 0;
     bool deferred = false;
     if (live) {
-      const EvalOut o = classify_pair<NUMA, CPU, GRP ? NS_GROUPS : IDS ? NS_SCORES : 0>(s, n, expired, pods, p, k, i, nv, &deferred);
+      const EvalOut o = classify_pair<NUMA, CPU, DOM ? NS_DOMAINS : GRP ? NS_GROUPS : IDS ? NS_SCORES : 0>(s, n, expired, pods, p, k, i, nv, &deferred);
       out.store(p, i, o);
       m = o.total >= 0 ? (uint32_t)o.ds + 1 : 0u;
     }
@@ -3532,7 +3584,8 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_batch(SoA s, int lo, int hi
       if (EXT && tot >= 0) tot += ext_score(s, i, pod, k);  // FitPlus / SRA / Fit: its own variant
       if (NS && !ns_ok<NS>(s, s.ns_ids[base + p], i)) tot = -1;  // (wave-uniform word address)
       if constexpr (NS >= NS_SCORES) tot = tot >= 0 ? tot + ns_off<NS>(s, s.ns_ids[base + p], i) : tot;
-      if constexpr (NS == NS_GROUPS) tot = sg_capped(s, s.sg_ids[base + p], i) ? -1 : tot;  // (wave-uniform row)
+      if constexpr (NS >= NS_GROUPS) tot = sg_capped(s, s.sg_ids[base + p], i) ? -1 : tot;  // (wave-uniform row)
+      if constexpr (NS == NS_DOMAINS) tot = sd_ok(s, base + p, i) ? tot : -1;  // (wave-uniform map row and mask)
       scores[(int64_t)p * score_stride + i] = (uint16_t)(tot + 1);
       continue;
     }
@@ -3601,10 +3654,17 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
   // NS_GROUPS: bit q = the spread group of the group's pod q has reached its cap on this lane's node, read the same
   // way (64 consecutive counts of a wave-uniform row per pod, the row and its cap found by scalar loads)
   uint32_t capped = 0;
-  if constexpr (NS == NS_GROUPS) {
+  if constexpr (NS >= NS_GROUPS) {
 #pragma unroll
     for (int q = 0; q < EVAL_PPB; q++)
       if (q < np && i < hi && sg_capped(s, s.sg_ids[base + p0 + q], i)) capped |= 1u << q;
+  }
+  // NS_DOMAINS: one more reason for bit q -- this lane's node's domain (in the map of pod q's spread domain group: the
+  // pods of the group may use different maps) is outside pod q's eligible-domain mask (wave-uniform loads)
+  if constexpr (NS == NS_DOMAINS) {
+#pragma unroll
+    for (int q = 0; q < EVAL_PPB; q++)
+      if (q < np && i < hi && !sd_ok(s, base + p0 + q, i)) capped |= 1u << q;
   }
   if ((int)threadIdx.x < 4 * np) {
     const int q = threadIdx.x >> 2, c = threadIdx.x & 3;
@@ -3641,7 +3701,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
     }
     if constexpr (NS >= NS_SCORES) t = t >= 0 ? t + (int32_t)((uint32_t)((q < 4 ? off[0] : off[1]) >> ((q & 3) * 16)) & 0xffffu) : t;
     if (NS && !((s_ns[q][threadIdx.x >> 6] >> (threadIdx.x & 63)) & 1ull)) t = -1;
-    if constexpr (NS == NS_GROUPS) t = (capped >> q) & 1u ? -1 : t;
+    if constexpr (NS >= NS_GROUPS) t = (capped >> q) & 1u ? -1 : t;
     out[(int64_t)q * score_stride] = (uint16_t)(t + 1);
   }
 }
@@ -5705,7 +5765,7 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
   }
   // plain batch: the speculative replay on every wave (a grouped batch, NS_GROUPS: the sequential replay below, whose
   // Reserves keep the spread group counts)
-  if constexpr (!DS && !NUMA && !QUOTA && NS != NS_GROUPS) {
+  if constexpr (!DS && !NUMA && !QUOTA && NS < NS_GROUPS) {
     __builtin_amdgcn_s_setprio(3);
     replay_spec<EXT, NS>(L, C, s, base, B, k, chosen, chosen_score, global_offset, stamps, batch_index, dev_alloc,
                      touched_out, touched_cnt, pstamps + PST * batch_index, has_t, keep, LS, sorted, th);
@@ -5734,6 +5794,11 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
 //   the only reader and writer of its node's counts during the batch, and reads the one pod j+1 needs after pod j's
 //   Reserve (program order on one lane, fenced like the DeviceShare Reserve's SoA writes); unchanged nodes keep the
 //   counts their snapshot keys were made from.  Pod j+1's group id and cap are fetched with its DevPod.
+//   NS_DOMAINS: besides, a changed node's fresh key is 0 when the node's domain is outside pod j's
+//   eligible-domain mask (k_domain_masks made it from the counts at the batch's snapshot, and no other pod of the
+//   batch is of pod j's group: the mask holds for the whole batch), and the owner lane's Reserve increments the count
+//   of (pod j's group, the node's domain), which no later pod of the batch reads.  Lane c reads its node's domain in
+//   pod j+1's map behind pod j's Reserve (maps do not change during a call: no ordering needed).
 template <bool DS, bool NUMA, bool QUOTA, bool EXT, int NS>
 __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const SoA& s, const int base, const int B,
                                              const KArgs& k, int32_t* __restrict__ chosen,
@@ -5773,9 +5838,19 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
   // NS_GROUPS: pod j's spread group and cap (wave-uniform), and this lane's node's count for it (lane < n_chg)
   int gid = 0;
   uint32_t gcap = 65535u, gcnt = 0;
-  if constexpr (NS == NS_GROUPS) {
+  if constexpr (NS >= NS_GROUPS) {
     gid = s.sg_ids[base];
     gcap = s.sg_cap[gid];
+  }
+  // NS_DOMAINS: pod j's spread domain group, its map row and the pod's mask (wave-uniform), and this lane's node's
+  // domain in that map (lane < n_chg)
+  int dgid = 0, dmap = 0;
+  uint64_t dmask = ~0ull;
+  uint32_t ddom = 0;
+  if constexpr (NS == NS_DOMAINS) {
+    dgid = s.sd_ids[base];
+    dmap = s.sd_par[dgid].map;
+    dmask = s.sd_mask[base];
   }
   RPROF_DECL
   for (int j = 0; j < B; j++) {
@@ -5784,9 +5859,16 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
     const int jn = more ? j + 1 : j;
     int gid_n = 0;
     uint32_t gcap_n = 65535u;
-    if constexpr (NS == NS_GROUPS) {
+    if constexpr (NS >= NS_GROUPS) {
       gid_n = s.sg_ids[base + jn];
       gcap_n = s.sg_cap[gid_n];
+    }
+    int dgid_n = 0, dmap_n = 0;
+    uint64_t dmask_n = ~0ull;
+    if constexpr (NS == NS_DOMAINS) {
+      dgid_n = s.sd_ids[base + jn];
+      dmap_n = s.sd_par[dgid_n].map;
+      dmask_n = s.sd_mask[base + jn];
     }
     const double pdd_n[4] = {L.pd[jn][0], L.pd[jn][1], L.pd[jn][2], L.pd[jn][3]};
     const double estd[2] = {pdd[0], pdd[1]}, reqd[2] = {pdd[2], pdd[3]};
@@ -5825,7 +5907,8 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
         tot = fast_total<EXT>(fast, pod, estd, reqd, k);
       }
       kc = ns_mkkey<NS>(s, nsid_of<NS>(L, j), my_node, tot);
-      if constexpr (NS == NS_GROUPS) kc = gcnt >= gcap ? 0u : kc;  // the group is at its cap on this node now
+      if constexpr (NS >= NS_GROUPS) kc = gcnt >= gcap ? 0u : kc;  // the group is at its cap on this node now
+      if constexpr (NS == NS_DOMAINS) kc = ddom < 64u && ((dmask >> ddom) & 1ull) ? kc : 0u;  // the domain is closed to pod j
     }
     RPROF(2)
     const uint32_t bc = wave_max_u32(kc);
@@ -5899,10 +5982,17 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
           mine.nreq[1] += pod.req[1];
         }
         if (!FAST && (k.flags & AF_EXT)) ext_reserve(s, my_node, pod, k);  // read back by the next re-evaluations
-        if constexpr (NS == NS_GROUPS) {  // the spread group's count on this node (a winner is below its cap: no wrap)
+        if constexpr (NS >= NS_GROUPS) {  // the spread group's count on this node (a winner is below its cap: no wrap)
           if (gid) {
             uint16_t* const cnt = s.sg_cnt + (int64_t)gid * s.sg_stride + my_node;
             st_sc1(cnt, (uint16_t)(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1));
+          }
+        }
+        if constexpr (NS == NS_DOMAINS) {  // the spread domain group's count of this node's domain (a winner's is open)
+          if (dgid) {
+            const uint32_t d = s.sd_map[(int64_t)dmap * s.sd_stride + my_node];
+            uint32_t* const cnt = s.sd_cnt + (int64_t)dgid * 64 + d;
+            if (d < 64u) st_sc1(cnt, ld_sc1(cnt) + 1u);
           }
         }
         // DeviceShare Reserve (the device SoA is global: a later pod of the batch re-evaluating this node
@@ -5945,14 +6035,20 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
     // order), so they already include pod j's new node
     const bool chg_n = ck_n != 0 && chg_test(C, key_node(ck_n));
     // the next re-evaluation reads the zones / devices / spread group count this Reserve patched
-    if (NUMA || DS || NS == NS_GROUPS) wave_lds_sync();
+    if (NUMA || DS || NS >= NS_GROUPS) wave_lds_sync();
     else __atomic_signal_fence(__ATOMIC_SEQ_CST);
-    if constexpr (NS == NS_GROUPS) {  // this lane's node's count of pod j+1's group, behind pod j's increment
+    if constexpr (NS >= NS_GROUPS) {  // this lane's node's count of pod j+1's group, behind pod j's increment
       gcnt = lane < n_chg ? __hip_atomic_load(s.sg_cnt + (int64_t)gid_n * s.sg_stride + my_node, __ATOMIC_RELAXED,
                                               __HIP_MEMORY_SCOPE_AGENT)
                           : 0u;
       gid = gid_n;
       gcap = gcap_n;
+    }
+    if constexpr (NS == NS_DOMAINS) {  // this lane's node's domain in the map of pod j+1's group
+      ddom = lane < n_chg ? (uint32_t)s.sd_map[(int64_t)dmap_n * s.sd_stride + my_node] : 0u;
+      dgid = dgid_n;
+      dmap = dmap_n;
+      dmask = dmask_n;
     }
     pod = pod_n;
 #pragma unroll
@@ -7208,6 +7304,7 @@ struct CallBufs {
   DevBuf<uint64_t> d_cpusets;    // [n_pods][4] cpuset of each pod
   DevBuf<int32_t> d_sched;       // ke_schedule bookkeeping (SchedLayout): hand-off flags, the T helpers' lists
   PinnedVec<uint8_t> h_out;      // the read-back staging (HostOutLayout)
+  DevBuf<uint64_t> d_sd_mask;    // [n_pods] eligible-domain masks of a call with spread domain ids (k_domain_masks)
   std::vector<hipEvent_t> tev;   // the call's events (pool): span, the call's end per stream, samples
 };
 
@@ -7262,6 +7359,13 @@ struct DeviceState {
   // 0 .. sg_n behind them (row 0: 65535); sg_rows: the rows of the current upload (0: none yet)
   DevBuf<uint16_t> d_sg_tbl;
   int64_t sg_rows = 0;
+  // spread domains: rows 0 .. sd_maps of `capacity` uint16 domain ids (row 0 all zero), rows 0 .. sd_n
+  // of 64 uint32 counts (row 0 all zero) and the groups' parameters (row 0: every domain, map 0, max_skew INT32_MAX);
+  // sd_map_rows / sd_rows: the rows of the current upload (0: none yet)
+  DevBuf<uint16_t> d_sd_map;
+  DevBuf<uint32_t> d_sd_cnt;
+  DevBuf<SdGroup> d_sd_par;
+  int64_t sd_map_rows = 0, sd_rows = 0;
   DevBuf<int8_t> d_vfo;     // [n_pods][2][DS_MINORS] VF ranks of the Reserves
   // batch buffers
   DevBuf<uint16_t> d_scores;  // [MAX_BATCH][capacity]
@@ -7928,17 +8032,83 @@ static int spread_groups_sync(Context* ctx) {
   d->soa.sg_stride = (int32_t)S;
   return KE_OK;
 }
-// the mode of a call's kernels from its ids: groups (which read the set and score tables' row 0 at least), score
-// tables, node sets, none
+// The spread domain tables for a call that carries spread domain ids, in the device layout: the maps
+// (`capacity` uint16 a row, row 0 all zero: with id 0's all-ones mask every node passes), the counts (64 uint32 a row,
+// row 0 all zero) and the groups' parameters.  A reload uploads all three; ke_spread_domain_add's and
+// ke_spread_domain_node_set's patches go up one entry each.  Between those the device keeps the counts itself, as it
+// keeps the spread groups'.
+static std::vector<uint16_t> spread_domain_maps_image(const Context* ctx, int64_t S) {
+  const int64_t rows = (int64_t)ctx->sd_maps + 1, cols = std::min(S, ctx->sd_stride);
+  std::vector<uint16_t> t((size_t)(rows * S), (uint16_t)KE_DOMAIN_NONE);
+  std::fill(t.begin(), t.begin() + S, (uint16_t)0);
+  for (int64_t m = 0; m < ctx->sd_maps; m++)
+    std::copy(ctx->sd_map.begin() + m * ctx->sd_stride, ctx->sd_map.begin() + m * ctx->sd_stride + cols,
+              t.begin() + (m + 1) * S);
+  return t;
+}
+static std::vector<uint32_t> spread_domain_counts_image(const Context* ctx) {
+  std::vector<uint32_t> t((size_t)(ctx->sd_n + 1) * 64, 0u);
+  std::copy(ctx->sd_cnt.begin(), ctx->sd_cnt.end(), t.begin() + 64);
+  return t;
+}
+static int spread_domains_sync(Context* ctx) {
+  DeviceState* d = ctx->dev;
+  const int64_t S = d->capacity, rows = (int64_t)ctx->sd_n + 1, mrows = (int64_t)ctx->sd_maps + 1;
+  const int64_t cols = std::min(S, ctx->sd_stride);
+  if (ctx->sd_dirty || !d->d_sd_cnt || d->sd_rows != rows || d->sd_map_rows != mrows) {
+    const std::vector<uint16_t> maps = spread_domain_maps_image(ctx, S);
+    const std::vector<uint32_t> cnt = spread_domain_counts_image(ctx);
+    std::vector<SdGroup> par((size_t)rows);
+    par[0] = SdGroup{~0ull, INT32_MAX, 0, 0, 0};
+    for (int64_t g = 1; g < rows; g++)
+      par[(size_t)g] = SdGroup{ctx->sd_dom[(size_t)g - 1], ctx->sd_skew[(size_t)g - 1], ctx->sd_mind[(size_t)g - 1],
+                               ctx->sd_gmap[(size_t)g - 1], 0};
+    RC_OK(d->d_sd_map.reserve(maps.size()));
+    RC_OK(d->d_sd_cnt.reserve(cnt.size()));
+    RC_OK(d->d_sd_par.reserve(par.size()));
+    HIP_OK(hipMemcpyAsync(d->d_sd_map, maps.data(), sizeof(uint16_t) * maps.size(), hipMemcpyHostToDevice, d->stream));
+    HIP_OK(hipMemcpyAsync(d->d_sd_cnt, cnt.data(), sizeof(uint32_t) * cnt.size(), hipMemcpyHostToDevice, d->stream));
+    HIP_OK(hipMemcpyAsync(d->d_sd_par, par.data(), sizeof(SdGroup) * par.size(), hipMemcpyHostToDevice, d->stream));
+    HIP_OK(hipStreamSynchronize(d->stream));
+    d->sd_rows = rows, d->sd_map_rows = mrows;
+  } else if (!ctx->sd_dirty_cells.empty() || !ctx->sd_dirty_nodes.empty()) {
+    for (const auto& gd : ctx->sd_dirty_cells)
+      HIP_OK(hipMemcpyAsync(d->d_sd_cnt + (int64_t)gd.first * 64 + gd.second,
+                            &ctx->sd_cnt[(size_t)((int64_t)(gd.first - 1) * 64 + gd.second)], sizeof(uint32_t),
+                            hipMemcpyHostToDevice, d->stream));
+    for (const auto& mn : ctx->sd_dirty_nodes) {
+      if (mn.second >= cols) continue;
+      HIP_OK(hipMemcpyAsync(d->d_sd_map + (int64_t)mn.first * S + mn.second,
+                            &ctx->sd_map[(size_t)((int64_t)(mn.first - 1) * ctx->sd_stride + mn.second)], sizeof(uint16_t),
+                            hipMemcpyHostToDevice, d->stream));
+    }
+    HIP_OK(hipStreamSynchronize(d->stream));
+  }
+  ctx->sd_dirty = false;
+  ctx->sd_dirty_cells.clear();
+  ctx->sd_dirty_nodes.clear();
+  d->soa.sd_map = d->d_sd_map;
+  d->soa.sd_cnt = d->d_sd_cnt;
+  d->soa.sd_par = d->d_sd_par;
+  d->soa.sd_stride = (int32_t)S;
+  return KE_OK;
+}
+// the mode of a call's kernels from its ids: spread domains (which read the other tables' row 0 at least), groups
+// (likewise), score tables, node sets, none
 static int call_ns(const Context* ctx) {
-  return ctx->sg_call ? NS_GROUPS : ctx->nsc_call ? NS_SCORES : ctx->ns_call ? NS_SETS : 0;
+  return ctx->sd_call ? NS_DOMAINS : ctx->sg_call ? NS_GROUPS : ctx->nsc_call ? NS_SCORES : ctx->ns_call ? NS_SETS : 0;
 }
 // the tables a call of mode `ns` reads, brought up to date
 static int id_tables_sync(Context* ctx, int ns) {
   if (ns) RC_OK(node_sets_sync(ctx));
   if (ns >= NS_SCORES) RC_OK(node_scores_sync(ctx));
-  if (ns == NS_GROUPS) RC_OK(spread_groups_sync(ctx));
+  if (ns >= NS_GROUPS) RC_OK(spread_groups_sync(ctx));
+  if (ns == NS_DOMAINS) RC_OK(spread_domains_sync(ctx));
   return KE_OK;
+}
+// the eligible-domain masks of pods [base, base + n) of a call with spread domain ids, on stream `st`
+static void launch_domain_masks(DeviceState* d, int base, int n, hipStream_t st) {
+  if (n > 0) hipLaunchKernelGGL(k_domain_masks, dim3((unsigned)n), dim3(64), 0, st, d->soa, base, n);
 }
 
 // The call's upload block: the DevPod records, the node set ids when present (int32 each) and room for
@@ -7952,10 +8122,12 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t
   // the call's node set ids and score table ids (a non-zero one among either): one word per pod behind the
   // records, the set id alone or -- in a call with table ids -- (table id << 16) | set id
   // -- and in a call with spread group ids those words (zero without set / table ids) and the group ids behind them
+  // -- and in a call with spread domain ids both of those (zero where the call has none) and the domain ids behind them
   const int32_t* ns = ctx->ns_call;
   const int32_t* sc = ctx->nsc_call;
   const int32_t* sg = ctx->sg_call;
-  const int64_t ns_words = (ns || sc || sg ? (int64_t)n_pods : 0) + (sg ? (int64_t)n_pods : 0);
+  const int32_t* sd = ctx->sd_call;
+  const int64_t ns_words = (ns || sc || sg || sd ? (int64_t)n_pods : 0) + (sg || sd ? (int64_t)n_pods : 0) + (sd ? (int64_t)n_pods : 0);
   if (!dp.resize((size_t)n_pods, sizeof(int32_t) * (size_t)(ns_words + tail_words)))
     return fail(KE_ERR_DEVICE, "hipHostMalloc of the pod staging buffer");
   std::vector<DevPodHint>& ph = d->host_ph;  // the hinted pods' records; DevPod::ring_bw = slot
@@ -7980,11 +8152,20 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t
   int32_t* const h_words = reinterpret_cast<int32_t*>(dp.data() + n_pods);
   d->soa.ns_ids = nullptr;
   d->soa.sg_ids = nullptr;
-  if (sg) {
-    std::copy(sg, sg + n_pods, h_words + n_pods);
+  d->soa.sd_ids = nullptr;
+  d->soa.sd_mask = nullptr;
+  if (sg || sd) {
+    if (sg) std::copy(sg, sg + n_pods, h_words + n_pods);
+    else std::fill(h_words + n_pods, h_words + 2 * (int64_t)n_pods, 0);
     d->soa.sg_ids = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods) + n_pods;
   }
-  if (ns || sc || sg) {
+  if (sd) {
+    std::copy(sd, sd + n_pods, h_words + 2 * (int64_t)n_pods);
+    d->soa.sd_ids = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods) + 2 * (int64_t)n_pods;
+    RC_OK(d->call.d_sd_mask.reserve((size_t)std::max<int32_t>(n_pods, 1)));
+    d->soa.sd_mask = d->call.d_sd_mask;
+  }
+  if (ns || sc || sg || sd) {
     static_assert(KE_MAX_NODE_SETS < (1 << 16) && KE_MAX_NODE_SCORE_TABLES < (1 << 15), "the packed id word");
     for (int32_t p = 0; p < n_pods; p++) h_words[p] = (ns ? ns[p] : 0) | (sc ? sc[p] << 16 : 0);
     d->soa.ns_ids = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods);
@@ -8027,11 +8208,14 @@ static auto with_ns_ext(int ns, bool ext, F&& f) {
          : ns == 0       ? e(std::integral_constant<int, 0>{})
                          : Fn(nullptr);
 }
-// ... and NS_GROUPS, for the kernels a grouped batch reaches (pick_eval_batch, pick_eval_plain, pick_resolve)
+// ... and NS_GROUPS / NS_DOMAINS, for the kernels a grouped batch reaches (pick_eval_batch, pick_eval_plain,
+// pick_resolve)
 template <class F>
 static auto with_nsg_ext(int ns, bool ext, F&& f) {
   if (ns == NS_GROUPS)
     return with_bool(ext, [&](auto EXT) { return f(std::integral_constant<int, NS_GROUPS>{}, EXT); });
+  if (ns == NS_DOMAINS)
+    return with_bool(ext, [&](auto EXT) { return f(std::integral_constant<int, NS_DOMAINS>{}, EXT); });
   return with_ns_ext(ns, ext, f);
 }
 
@@ -8041,6 +8225,7 @@ static EvalParityFn pick_eval_parity(bool numa, bool cpu, int ns) {
   return with_bool(ns != 0, [&](auto IDS) {
     return with_bool(numa, [&](auto NUMA) {
       return with_bool(cpu, [&](auto CPU) -> EvalParityFn {
+        if (ns == NS_DOMAINS) return k_eval_parity<KV(NUMA), KV(CPU), true, true, true>;
         if (ns == NS_GROUPS) return k_eval_parity<KV(NUMA), KV(CPU), true, true>;
         return k_eval_parity<KV(NUMA), KV(CPU), KV(IDS)>;
       });
@@ -8120,6 +8305,7 @@ static DiagEvalFn pick_diag_eval(bool numa, bool cpu, int ns) {
   return with_bool(ns != 0, [&](auto SETS) {
     return with_bool(numa, [&](auto NUMA) {
       return with_bool(cpu, [&](auto CPU) -> DiagEvalFn {
+        if (ns == NS_DOMAINS) return k_diag_eval<KV(NUMA), KV(CPU), NS_DOMAINS>;
         if (ns == NS_GROUPS) return k_diag_eval<KV(NUMA), KV(CPU), NS_GROUPS>;
         return k_diag_eval<KV(NUMA), KV(CPU), KV(SETS) ? NS_SETS : 0>;
       });
@@ -8176,6 +8362,7 @@ static int pair_pass_begin(Context* ctx, int32_t n_pods, const ke_pod* pods, int
   if (rc || n_pods == 0) return rc;
   if ((rc = id_tables_sync(ctx, ns))) return rc;
   if ((rc = upload_pods(ctx, n_pods, pods))) return rc;
+  if (ns == NS_DOMAINS) launch_domain_masks(d, 0, n_pods, d->stream);  // (ke_eval / ke_diagnose: one wave per pod of the call)
   HIP_OK(hipMemsetAsync(d->soa.kerr, 0, sizeof(int32_t), d->stream));
   pp->k = make_kargs(ctx, now);
   for (const DevPod& q : d->call.host_pods) pp->cpu = pp->cpu || (q.flags & PF_CPUSET);
@@ -8257,7 +8444,7 @@ int device_diagnose(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t no
                     int32_t words_per_pod, uint64_t* const* bits) {
   DeviceState* d = ctx->dev;
   // (score table ids do not filter: ke_diagnose drops them; spread groups do)
-  const int ns = ctx->sg_call ? NS_GROUPS : ctx->ns_call ? NS_SETS : 0;
+  const int ns = ctx->sd_call ? NS_DOMAINS : ctx->sg_call ? NS_GROUPS : ctx->ns_call ? NS_SETS : 0;
   PairPass pp;
   int rc = pair_pass_begin(ctx, n_pods, pods, now, ns, &pp);
   if (rc || n_pods == 0) return rc;
@@ -8380,6 +8567,7 @@ struct Completion {
   int64_t copies, fills;
   int n_pipelined;
   std::vector<int32_t> groups;  // the call's spread group ids (empty: none): the host copy takes its placements' increments
+  std::vector<int32_t> domains;  // ... and its spread domain group ids
 };
 
 static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
@@ -8435,6 +8623,13 @@ static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
     const int32_t g = c.groups[p], node = chosen[p];
     if (g > 0 && g <= ctx->sg_n && node >= 0 && (int64_t)node < ctx->sg_stride)
       ctx->sg_cnt[(size_t)((int64_t)(g - 1) * ctx->sg_stride + node)]++;
+  }
+  // spread domains: likewise, on the count of the placement's domain in the group's map
+  for (size_t p = 0; p < c.domains.size(); p++) {
+    const int32_t g = c.domains[p], node = chosen[p];
+    if (g < 1 || g > ctx->sd_n || node < 0 || (int64_t)node >= ctx->sd_stride) continue;
+    const uint16_t dom = ctx->sd_map[(size_t)((int64_t)(ctx->sd_gmap[(size_t)g - 1] - 1) * ctx->sd_stride + node)];
+    if (dom < KE_MAX_SPREAD_DOMAINS) ctx->sd_cnt[(size_t)(g - 1) * KE_MAX_SPREAD_DOMAINS + dom]++;
   }
   float ms = 0;
   HIP_OK(hipEventElapsedTime(&ms, c.e0, c.e1));
@@ -8498,8 +8693,10 @@ struct ScheduleCall {
   // turns a (pod, node) pair into a score or key (NS_SETS), or with score table ids (NS_SCORES: these read the set
   // table too, id 0 = its all-ones row 0).  A call with spread group ids keeps that mode for its
   // batches without a grouped pod; a grouped batch runs the NS_GROUPS instantiations (batch_ns), serially.
+  // A call with spread domain ids likewise: its batches holding a pod with such an id are grouped and
+  // run the NS_DOMAINS instantiations, the others what they ran before.
   const int ns;
-  const bool groups;
+  const bool groups, domains;
   // the plan
   bool fixup = false, two_es = false, ahead = false;  // the schedule of the call's pipelined runs (plan())
   std::vector<Batch> batches;
@@ -8536,8 +8733,9 @@ struct ScheduleCall {
       : ctx(ctx_), d(ctx_->dev), c(d->call), n_pods(n), pods(p), want_score(ws), N(ctx_->n_nodes), fused(ctx_->rsv_fused),
         numa(d->has(ST_NUMA)), quota(!ctx_->quotas.empty()), sharded(d->world > 1 || d->comm || d->host_fn),
         matched(!ctx_->rsv_pairs.empty() || ctx_->rsv_affinity),
-        ns(ctx_->nsc_call ? NS_SCORES : ctx_->ns_call ? NS_SETS : 0), groups(ctx_->sg_call != nullptr) {}
-  int batch_ns(int b) const { return batches[(size_t)b].grouped ? NS_GROUPS : ns; }
+        ns(ctx_->nsc_call ? NS_SCORES : ctx_->ns_call ? NS_SETS : 0), groups(ctx_->sg_call != nullptr),
+        domains(ctx_->sd_call != nullptr) {}
+  int batch_ns(int b) const { return !batches[(size_t)b].grouped ? ns : domains ? NS_DOMAINS : NS_GROUPS; }
 
   hipError_t copy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
     n_copies++;
@@ -8559,7 +8757,9 @@ struct ScheduleCall {
     }
     if (groups && (int64_t)ctx->sg_call_ids.size() != n_pods)
       return fail(KE_ERR_DEVICE, "internal: spread group ids of another call");
-    if ((rc = id_tables_sync(ctx, groups ? NS_GROUPS : ns))) return rc;
+    if (domains && (int64_t)ctx->sd_call_ids.size() != n_pods)
+      return fail(KE_ERR_DEVICE, "internal: spread domain ids of another call");
+    if ((rc = id_tables_sync(ctx, domains ? NS_DOMAINS : groups ? NS_GROUPS : ns))) return rc;
     return upload_pods(ctx, n_pods, pods, (int64_t)n_pods + 1, &h_bases, &upload_bytes, &n_copies);
   }
 
@@ -8568,7 +8768,7 @@ struct ScheduleCall {
     // the knob is read per call: tests set it between contexts of one process
     knob = select_knob(std::getenv("KOORDEVAL_SELECT_PARTS"));
     ctx->last_ds_cuts = 0;
-    batches = plan_batches(c.host_pods.data(), n_pods, ctx->cfg.pod_batch, !sharded && !numa && N > 0, fused, ctx->sg_call);
+    batches = plan_batches(c.host_pods.data(), n_pods, ctx->cfg.pod_batch, !sharded && !numa && N > 0, fused, ctx->sg_call, ctx->sd_call);
     for (const Batch& b : batches) any_cpu = any_cpu || b.cpu;
     if (any_cpu && !d->has(ST_CPU)) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
     n_batches = (int)batches.size();
@@ -8675,7 +8875,7 @@ struct ScheduleCall {
   // the bookkeeping words, the one copy of everything the call uploads, the call's events, and k_call_begin
   int begin() {
     RC_OK(c.d_sched.reserve((size_t)sl.total));
-    d_bases = reinterpret_cast<int32_t*>(c.d_pods + n_pods) + (ns || groups ? n_pods : 0) + (groups ? n_pods : 0);
+    d_bases = reinterpret_cast<int32_t*>(c.d_pods + n_pods) + (ns || groups || domains ? n_pods : 0) + (groups || domains ? n_pods : 0) + (domains ? n_pods : 0);
     d_ready = c.d_sched + sl.ready, d_done = c.d_sched + sl.done, d_tready = c.d_sched + sl.tready;
     d_sstart = c.d_sched + sl.sstart, d_rres = c.d_sched + sl.rres, d_tlist = c.d_sched + sl.tlist;
     d_tmx = reinterpret_cast<uint32_t*>(c.d_sched + sl.tmx);
@@ -8793,6 +8993,9 @@ struct ScheduleCall {
     const int blk = bp == 1 ? 64 : EVAL_BLOCK;
     const dim3 grid = eval_grid(hi - lo, blk, bp, EVAL_PPB);
     const DeferBufs df{defer.list, defer.fb, numa ? defer.cnt + b : nullptr};  // (the batch's own counter)
+    // a grouped batch of a call with spread domain ids: its pods' eligible-domain masks from the counts as the previous
+    // batch's Reserves left them (a serial batch: this stream ran them)
+    if (batch_ns(b) == NS_DOMAINS) launch_domain_masks(d, bases[b], bp, a.es);
     if (plain_rec) {  // plain batch: the record-based evaluation
       hipLaunchKernelGGL(pick_eval_plain(ext, batch_ns(b)), grid, dim3(blk), 0, a.es, d->soa, lo, hi, c.d_pods, bbase, bp, k,
                          eb.scores, d->capacity, stamp, dwait, d_err);
@@ -9087,6 +9290,7 @@ struct ScheduleCall {
     cp.entry = ctx->call_entry, cp.behind = ctx->call_behind;
     cp.copies = n_copies, cp.fills = n_fills, cp.n_pipelined = n_pipelined;
     if (groups) cp.groups.assign(ctx->sg_call, ctx->sg_call + n_pods);
+    if (domains) cp.domains.assign(ctx->sd_call, ctx->sd_call + n_pods);
     *fin = [cp = std::move(cp)](int32_t* chosen, int32_t* score) { return complete_call(cp, chosen, score); };
     return KE_OK;
   }
@@ -9242,6 +9446,31 @@ int device_spread_groups_check(Context* ctx, int64_t* bad) {
   for (const auto& gn : ctx->sg_dirty_cells)  // (patches the next call uploads: taken as sent)
     if (gn.second < cols) t[(size_t)((int64_t)gn.first * S + gn.second)] = want[(size_t)((int64_t)gn.first * S + gn.second)];
   for (size_t q = 0; q < t.size(); q++) *bad += t[q] != want[q];
+  return KE_OK;
+}
+
+// ... and the spread domain counts and maps
+int device_spread_domains_check(Context* ctx, int64_t* bad) {
+  DeviceState* d = ctx->dev;
+  *bad = 0;
+  if (!d->d_sd_cnt || ctx->sd_dirty) return KE_OK;  // (no device copy, or one the next call replaces)
+  HIP_OK(hipSetDevice(d->device));
+  const int64_t S = d->capacity, cols = std::min(S, ctx->sd_stride);
+  if (d->sd_rows != (int64_t)ctx->sd_n + 1 || d->sd_map_rows != (int64_t)ctx->sd_maps + 1)
+    return fail(KE_ERR_DEVICE, "internal: the device spread domain tables have other rows");
+  const std::vector<uint16_t> want_map = spread_domain_maps_image(ctx, S);
+  const std::vector<uint32_t> want_cnt = spread_domain_counts_image(ctx);
+  std::vector<uint16_t> maps(want_map.size());
+  std::vector<uint32_t> cnt(want_cnt.size());
+  HIP_OK(hipMemcpyAsync(maps.data(), d->d_sd_map, sizeof(uint16_t) * maps.size(), hipMemcpyDeviceToHost, d->stream));
+  HIP_OK(hipMemcpyAsync(cnt.data(), d->d_sd_cnt, sizeof(uint32_t) * cnt.size(), hipMemcpyDeviceToHost, d->stream));
+  HIP_OK(hipStreamSynchronize(d->stream));
+  for (const auto& gd : ctx->sd_dirty_cells)  // (patches the next call uploads: taken as sent)
+    cnt[(size_t)((int64_t)gd.first * 64 + gd.second)] = want_cnt[(size_t)((int64_t)gd.first * 64 + gd.second)];
+  for (const auto& mn : ctx->sd_dirty_nodes)
+    if (mn.second < cols) maps[(size_t)((int64_t)mn.first * S + mn.second)] = want_map[(size_t)((int64_t)mn.first * S + mn.second)];
+  for (size_t q = 0; q < cnt.size(); q++) *bad += cnt[q] != want_cnt[q];
+  for (size_t q = 0; q < maps.size(); q++) *bad += maps[q] != want_map[q];
   return KE_OK;
 }
 

@@ -84,9 +84,21 @@ struct Batch {
 // the max over all feasible nodes of the current state.
 // `group_ids` (the call's spread group id per pod, nullptr: none): the segmentation is the same with or without them; a
 // batch holding a pod with a non-zero id is marked `grouped`.
+// `domain_ids` (the call's spread domain group id per pod; nullptr: none): a batch holds at most one pod
+// of any spread domain group -- it ends before a pod whose non-zero id already occurs in it, so the group's domain
+// counts during the batch are those of the batch's snapshot -- and a batch holding such a pod is `grouped` too.  With
+// every id zero the plan is the one without them.
 inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bool ds_batch, bool fused,
-                                       const int32_t* group_ids = nullptr) {
+                                       const int32_t* group_ids = nullptr, const int32_t* domain_ids = nullptr) {
   std::vector<Batch> batches;
+  // pod p0 + bp names a spread domain group that one of the bp pods from p0 on names already
+  auto repeats = [&](int p0, int bp) {
+    const int32_t id = domain_ids ? domain_ids[p0 + bp] : 0;
+    if (id == 0) return false;
+    for (int q = 0; q < bp; q++)
+      if (domain_ids[p0 + q] == id) return true;
+    return false;
+  };
   auto alone = [&](uint32_t f) { return (f & PF_CPUSET) || ((f & PF_DS) && !ds_batch) || (f & PF_DS_HINT); };
   for (int p = 0; p < n_pods;) {
     const uint32_t f = pods[p].flags;
@@ -97,7 +109,8 @@ inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bo
     }
     int bp = 0;
     bool has_ds = false;
-    while (p + bp < n_pods && bp < B && !(fused && p + bp == n_pods - 1) && !alone(pods[p + bp].flags)) {
+    while (p + bp < n_pods && bp < B && !(fused && p + bp == n_pods - 1) && !alone(pods[p + bp].flags) &&
+           !repeats(p, bp)) {
       has_ds = has_ds || (pods[p + bp].flags & PF_DS);
       bp++;
     }
@@ -107,6 +120,9 @@ inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bo
   if (group_ids)
     for (size_t b = 0, p = 0; b < batches.size(); p += (size_t)batches[b].pods, b++)
       for (int q = 0; q < batches[b].pods; q++) batches[b].grouped = batches[b].grouped || group_ids[p + (size_t)q] != 0;
+  if (domain_ids)
+    for (size_t b = 0, p = 0; b < batches.size(); p += (size_t)batches[b].pods, b++)
+      for (int q = 0; q < batches[b].pods; q++) batches[b].grouped = batches[b].grouped || domain_ids[p + (size_t)q] != 0;
   return batches;
 }
 

@@ -323,6 +323,69 @@ class Evaluator:
         self._check(self.lib.ke_debug_spread_groups_check(self.h, C.byref(n)))
         return n.value
 
+    def spread_domains_load(self, node_domain, group_map, domains, max_skew, min_domains=None, counts=None, n_nodes=None):
+        """ke_spread_domains_load: replace the spread domains -- `node_domain` a [n_maps, N] matrix of domain ids
+        (0..63, abi.DOMAIN_NONE for a node without the topology key; padded with DOMAIN_NONE to n_nodes when that is
+        larger); per group its map (1 + the row of node_domain), the uint64 bitmask `domains`, `max_skew` (>= 1),
+        `min_domains` (None: 0) and `counts`, a [n_groups, 64] matrix of the pods it already has per domain (None:
+        zero).  Group ids are 1 + the index.  No groups drop the table."""
+        gm = np.ascontiguousarray(np.asarray(group_map).reshape(-1), np.int32)
+        G = len(gm)
+        if G == 0:
+            self._check(self.lib.ke_spread_domains_load(self.h, 0, 0, None, 0, None, None, None, None, None))
+            return
+        m = np.atleast_2d(np.asarray(node_domain))
+        if (m < 0).any() or (m > 0xFFFF).any():
+            raise ValueError("domain id outside 0..65535")
+        n = m.shape[1] if n_nodes is None else int(n_nodes)
+        if n < m.shape[1]:
+            raise ValueError("n_nodes below the maps' width")
+        v = np.full((m.shape[0], n), abi.DOMAIN_NONE, np.uint16)
+        v[:, :m.shape[1]] = m
+        dom = np.ascontiguousarray([int(d) for d in np.asarray(domains, object).reshape(-1)], np.uint64)
+        skew = np.ascontiguousarray(np.asarray(max_skew).reshape(-1), np.int32)
+        mind = None if min_domains is None else np.ascontiguousarray(np.asarray(min_domains).reshape(-1), np.int32)
+        if len(dom) != G or len(skew) != G or (mind is not None and len(mind) != G):
+            raise ValueError("one map, domains mask, max_skew (and min_domains) per group")
+        cnt = None
+        if counts is not None:
+            c = np.atleast_2d(np.asarray(counts))
+            if c.shape != (G, abi.MAX_SPREAD_DOMAINS):
+                raise ValueError("counts is [n_groups, 64]")
+            if (c < 0).any() or (c > 0xFFFFFFFF).any():
+                raise ValueError("spread domain count outside 0..2^32-1")
+            cnt = np.ascontiguousarray(c, np.uint32)
+        self._check(self.lib.ke_spread_domains_load(
+            self.h, v.shape[0], n, abi.ptr(v) if v.size else None, G, abi.ptr(gm), abi.ptr(dom), abi.ptr(skew),
+            None if mind is None else abi.ptr(mind), None if cnt is None else abi.ptr(cnt)))
+
+    def spread_domain_add(self, group, domain, delta):
+        """ke_spread_domain_add: count[group][domain] += delta (an informer pod event, or -1 to undo a placement)."""
+        self._check(self.lib.ke_spread_domain_add(self.h, int(group), int(domain), int(delta)))
+
+    def spread_domain_node_set(self, map_id, node, domain):
+        """ke_spread_domain_node_set: the domain of `node` in map `map_id` (a node the informer adds or relabels)."""
+        self._check(self.lib.ke_spread_domain_node_set(self.h, int(map_id), int(node), int(domain)))
+
+    def spread_domains_get(self, group):
+        """ke_spread_domains_get: group `group`'s current count per domain [64], every Reserve included."""
+        out = np.zeros(abi.MAX_SPREAD_DOMAINS, np.uint32)
+        self._check(self.lib.ke_spread_domains_get(self.h, int(group), abi.ptr(out)))
+        return out
+
+    def pod_spread_domains(self, ids):
+        """ke_pod_spread_domains: the spread domain group id (0 = none) per pod of the next eval / diagnose / schedule /
+        submit."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        self._check(self.lib.ke_pod_spread_domains(self.h, len(ids), abi.ptr(ids)))
+
+    def debug_spread_domains_check(self):
+        """ke_debug_spread_domains_check: counts and map entries of the device's spread domain tables that differ from
+        the host copy."""
+        n = C.c_int64()
+        self._check(self.lib.ke_debug_spread_domains_check(self.h, C.byref(n)))
+        return n.value
+
     def node_info_requested(self, i):
         """ke_node_info_requested: NodeInfo Requested / NonZeroRequested (MilliCPU, Memory) after the restore."""
         req, nz = (C.c_int64 * 2)(), (C.c_int64 * 2)()
@@ -406,9 +469,10 @@ class Evaluator:
         return lo.value, hi.value
 
     # ---- evaluation -------------------------------------------------------------------------
-    def eval(self, pods, now_ns, node_sets=None, node_scores=None, spread_groups=None):
+    def eval(self, pods, now_ns, node_sets=None, node_scores=None, spread_groups=None, spread_domains=None):
         """ke_eval; `node_sets` (optional): the node set id per pod (0 = every node); `node_scores` (optional): the
-        score table id per pod (0 = no offset); `spread_groups` (optional): the spread group id per pod (0 = none)."""
+        score table id per pod (0 = no offset); `spread_groups` (optional): the spread group id per pod (0 = none);
+        `spread_domains` (optional): the spread domain group id per pod (0 = none)."""
         pods = as_pod_array(pods)
         if node_sets is not None:
             self.pod_node_sets(node_sets)
@@ -416,6 +480,8 @@ class Evaluator:
             self.pod_node_scores(node_scores)
         if spread_groups is not None:
             self.pod_spread_groups(spread_groups)
+        if spread_domains is not None:
+            self.pod_spread_domains(spread_domains)
         P, N = len(pods), self.num_nodes
         out = {
             "status": np.zeros((P, N), np.uint8),
@@ -431,17 +497,19 @@ class Evaluator:
                                      abi.ptr(out["ds"]), abi.ptr(out["total"]), abi.ptr(out["best"])))
         return out
 
-    def diagnose(self, pods, now_ns, node_sets=None, bitmaps=False, spread_groups=None):
+    def diagnose(self, pods, now_ns, node_sets=None, bitmaps=False, spread_groups=None, spread_domains=None):
         """ke_diagnose: per pod the reductions of eval()'s status / reason over every node, computed on the device
         with nothing per pair copied back -- int32 [P] arrays n_nodes, n_absent, n_feasible, n_unschedulable,
         n_unresolvable, n_error, uint32 [P] plugins (abi.PLUGIN_* bits), int32 [P, 128] reason_nodes; with
-        `bitmaps` also the bool [P, N] matrices feasible, unschedulable, unresolvable.  `node_sets` and `spread_groups`
-        as for eval()."""
+        `bitmaps` also the bool [P, N] matrices feasible, unschedulable, unresolvable.  `node_sets`, `spread_groups`
+        and `spread_domains` as for eval()."""
         pods = as_pod_array(pods)
         if node_sets is not None:
             self.pod_node_sets(node_sets)
         if spread_groups is not None:
             self.pod_spread_groups(spread_groups)
+        if spread_domains is not None:
+            self.pod_spread_domains(spread_domains)
         P, N = len(pods), self.num_nodes
         rec = np.zeros(P, abi.POD_DIAGNOSIS_DTYPE)
         wpp = (N + 63) // 64
@@ -454,10 +522,12 @@ class Evaluator:
             out[k] = unpack_node_sets(w, N)
         return out
 
-    def schedule(self, pods, now_ns, matches=None, node_sets=None, node_scores=None, spread_groups=None):
+    def schedule(self, pods, now_ns, matches=None, node_sets=None, node_scores=None, spread_groups=None,
+                 spread_domains=None):
         """ke_schedule; `matches` (optional): per pod the reservation indices it matches (KE_RSV_MATCHED pods);
         `node_sets` (optional): the node set id per pod (0 = every node); `node_scores` (optional): the score table
-        id per pod (0 = no offset); `spread_groups` (optional): the spread group id per pod (0 = none)."""
+        id per pod (0 = no offset); `spread_groups` (optional): the spread group id per pod (0 = none);
+        `spread_domains` (optional): the spread domain group id per pod (0 = none)."""
         pods = as_pod_array(pods)
         if matches is not None:
             self.pod_reservations(matches)
@@ -467,16 +537,18 @@ class Evaluator:
             self.pod_node_scores(node_scores)
         if spread_groups is not None:
             self.pod_spread_groups(spread_groups)
+        if spread_domains is not None:
+            self.pod_spread_domains(spread_domains)
         chosen = np.zeros(len(pods), np.int32)
         score = np.zeros(len(pods), np.int32)
         self._check(self.lib.ke_schedule(self.h, len(pods), abi.ptr(pods), int(now_ns), abi.ptr(chosen), abi.ptr(score)))
         self._last_n, self._last_out = len(pods), {}  # the per-pod allocations are read on first access
         return chosen, score
 
-    def submit(self, pods, now_ns, node_sets=None, node_scores=None, spread_groups=None):
+    def submit(self, pods, now_ns, node_sets=None, node_scores=None, spread_groups=None, spread_domains=None):
         """ke_schedule_submit: enqueue a queue slice behind the calls in flight; returns its ticket (wait() collects
-        it).  The pod array is kept alive here until then.  `node_sets`, `node_scores` and `spread_groups` as for
-        schedule()."""
+        it).  The pod array is kept alive here until then.  `node_sets`, `node_scores`, `spread_groups` and
+        `spread_domains` as for schedule()."""
         pods = as_pod_array(pods)
         if node_sets is not None:
             self.pod_node_sets(node_sets)
@@ -484,6 +556,8 @@ class Evaluator:
             self.pod_node_scores(node_scores)
         if spread_groups is not None:
             self.pod_spread_groups(spread_groups)
+        if spread_domains is not None:
+            self.pod_spread_domains(spread_domains)
         t = C.c_int64()
         self._check(self.lib.ke_schedule_submit(self.h, len(pods), abi.ptr(pods), int(now_ns), C.byref(t)))
         self._inflight[t.value] = pods
