@@ -1040,6 +1040,52 @@ int ke_spread_domains_get(ke_ctx* ctx, int32_t group, uint32_t* counts64);
 /* Spread domain group id per pod for the NEXT ke_eval / ke_diagnose / ke_schedule / ke_schedule_submit of exactly
  * n_pods pods, with ke_pod_spread_groups' rules. */
 int ke_pod_spread_domains(ke_ctx* ctx, int32_t n_pods, const int32_t* group_ids);
+/* ---- spread terms: per-pod affinity, anti-affinity and preference lists over the spread group counts (additive:
+ *      KE_ABI_VERSION stays 14) ---
+ * A spread group id is one shape of inter-pod constraint: the pod is filtered on the group it increments, and the
+ * test is count < cap.  Spread terms open the same count table (ke_spread_groups_load / ke_spread_group_add /
+ * ke_spread_groups_get, unchanged) to the rest of what InterPodAffinity and hostname-level PodTopologySpread do with
+ * per-node pod counts.  A pod of a call may carry two lists:
+ *  - Terms, up to KE_MAX_POD_TERMS, each (group, kind, param, weight), group in 1..n_groups, param in 1..65535:
+ *      KE_TERM_ANTI          node filtered when count[group][node] >= param               weight 0
+ *      KE_TERM_AFFINITY      node filtered when count[group][node] <  param               weight 0
+ *      KE_TERM_PREFER_FEWER  feasible total += weight * (param - min(count, param))       weight 1..100
+ *      KE_TERM_PREFER_MORE   feasible total += weight * min(count, param)                 weight 1..100
+ *    A filtered pair reports exactly as a capped spread group pair: KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE,
+ *    KE_REASON_NODE_SET (KE_PLUGIN_NODE_SET), plugin scores 0, total -1, outside best[] and DeviceShare's
+ *    NormalizeScore maximum, never deferred; the test follows the node-set and spread-domain tests and precedes every
+ *    koordinator filter.  The bonus of the score terms is added where a ke_pod_node_scores offset is added (in ke_eval
+ *    behind DeviceShare's normalisation); a filtered pair gets none.
+ *  - Members, up to KE_MAX_POD_MEMBERS distinct groups: ke_schedule / ke_schedule_submit placing the pod on node n do
+ *    count[m][n] += 1 for every member m, saturating at 65535 (device and host copy alike); every later pod -- of the
+ *    same batch, of later batches, of later calls, of a slice submitted ahead -- sees it.  An unplaced pod changes
+ *    nothing.  An AFFINITY term therefore sees a node a placement of the same call has just opened.
+ * A pod with both lists empty is a plain pod.  A spread group id g is the special case terms = {ANTI(g, cap[g])},
+ * members = {g}; max_per_node is not read by term lists.  ke_eval and ke_diagnose read the counts and change nothing;
+ * ke_diagnose applies the filter kinds only (score tables are not part of a diagnosis either).  ke_unreserve and
+ * ke_pod_release do NOT touch the counts: the caller sends ke_spread_group_add(ctx, member, node, -1) per member.
+ * Key range: a call is KE_ERR_UNSUPPORTED before any state changes ("spread terms: ...", naming the cap) when for some
+ * pod the sum of weight * param over its score terms exceeds 1022 - 100 * (sum of the Score plugin weights) minus --
+ * when the call carries a non-zero score table id -- the largest entry of the loaded score tables.
+ * A ke_schedule / ke_schedule_submit call with a non-empty list must be a plain queue exactly as one with a non-zero
+ * node set id; anything else is KE_ERR_UNSUPPORTED before any state changes ("spread terms: ...", or the node sets' /
+ * node scores' / spread domains' message when such an id of the call is non-zero too).  Term lists may be staged
+ * together with set ids, table ids and spread domain ids; together with ke_pod_spread_groups ids the call is
+ * KE_ERR_INVALID. */
+#define KE_MAX_POD_TERMS 4
+#define KE_MAX_POD_MEMBERS 4
+#define KE_TERM_ANTI 1
+#define KE_TERM_AFFINITY 2
+#define KE_TERM_PREFER_FEWER 3
+#define KE_TERM_PREFER_MORE 4
+/* The lists per pod, CSR like ke_pod_reservations: pod p's terms are terms[4 * term_offsets[p] .. 4 * term_offsets[p+1])
+ * (four int32 a term: group, kind, param, weight), its members members[member_offsets[p] .. member_offsets[p+1]).  For
+ * the NEXT ke_eval / ke_diagnose / ke_schedule / ke_schedule_submit of exactly n_pods pods, consumed by that call
+ * whether it succeeds or not; does not wait for calls in flight; otherwise ke_pod_spread_groups' rules.
+ * KE_ERR_INVALID: a group outside 1..n_groups (or no table loaded), an unknown kind, a param or weight outside its
+ * range, more than 4 terms or members for one pod, a repeated member, offsets that do not ascend from 0. */
+int ke_pod_spread_terms(ke_ctx* ctx, int32_t n_pods, const int32_t* term_offsets, const int32_t* terms,
+                        const int32_t* member_offsets, const int32_t* members);
 /* ---- FitError diagnosis of unschedulable pods (additive: KE_ABI_VERSION stays 14) -------------------
  * A pod ke_schedule left at chosen = -1 must go back to the queue with a framework.FitError.  The reference reads
  * three parts of it, all reductions of the Filter status map (framework.NodeToStatusMap) findNodesThatFitPod fills:

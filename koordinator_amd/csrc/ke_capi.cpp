@@ -872,27 +872,83 @@ int ke_pod_spread_domains(ke_ctx* ctx, int32_t n_pods, const int32_t* group_ids)
   return KE_OK;
 }
 
+// ---- spread terms (include/koord_eval.h): ke_pod_spread_groups' rules, per-pod lists ----
+static_assert(KE_MAX_POD_TERMS == POD_TERMS && KE_MAX_POD_MEMBERS == POD_MEMBERS && KE_TERM_ANTI == ST_ANTI &&
+                  KE_TERM_AFFINITY == ST_AFFINITY && KE_TERM_PREFER_FEWER == ST_PREFER_FEWER &&
+                  KE_TERM_PREFER_MORE == ST_PREFER_MORE && KE_MAX_SPREAD_GROUPS < (1 << 16),
+              "the packed record");
+int ke_pod_spread_terms(ke_ctx* ctx, int32_t n_pods, const int32_t* term_offsets, const int32_t* terms,
+                        const int32_t* member_offsets, const int32_t* members) {
+  if (!ctx || n_pods < 0 || !term_offsets || !member_offsets) return fail(KE_ERR_INVALID, "ke_pod_spread_terms arguments");
+  Context& c = ctx->c;
+  if (term_offsets[0] != 0 || member_offsets[0] != 0) return fail(KE_ERR_INVALID, "ke_pod_spread_terms: offsets do not start at 0");
+  for (int32_t p = 0; p < n_pods; p++) {
+    if (term_offsets[p + 1] < term_offsets[p] || member_offsets[p + 1] < member_offsets[p])
+      return fail(KE_ERR_INVALID, "ke_pod_spread_terms: offsets do not ascend");
+    if (term_offsets[p + 1] - term_offsets[p] > KE_MAX_POD_TERMS)
+      return fail(KE_ERR_INVALID, "ke_pod_spread_terms: more than KE_MAX_POD_TERMS terms for one pod");
+    if (member_offsets[p + 1] - member_offsets[p] > KE_MAX_POD_MEMBERS)
+      return fail(KE_ERR_INVALID, "ke_pod_spread_terms: more than KE_MAX_POD_MEMBERS members for one pod");
+  }
+  if ((term_offsets[n_pods] > 0 && !terms) || (member_offsets[n_pods] > 0 && !members))
+    return fail(KE_ERR_INVALID, "ke_pod_spread_terms arguments");
+  std::vector<PodTerms> recs((size_t)n_pods, PodTerms{});
+  for (int32_t p = 0; p < n_pods; p++) {
+    PodTerms& r = recs[(size_t)p];
+    for (int32_t q = term_offsets[p], t = 0; q < term_offsets[p + 1]; q++, t++) {
+      const int32_t group = terms[4 * q], kind = terms[4 * q + 1], param = terms[4 * q + 2], weight = terms[4 * q + 3];
+      if (group < 1 || group > c.sg_n) return fail(KE_ERR_INVALID, "ke_pod_spread_terms: a term's group outside 1..n_groups");
+      if (kind < KE_TERM_ANTI || kind > KE_TERM_PREFER_MORE) return fail(KE_ERR_INVALID, "ke_pod_spread_terms: unknown term kind");
+      if (param < 1 || param > 65535) return fail(KE_ERR_INVALID, "ke_pod_spread_terms: a param outside 1..65535");
+      const bool score = kind >= KE_TERM_PREFER_FEWER;
+      if (score ? (weight < 1 || weight > 100) : weight != 0)
+        return fail(KE_ERR_INVALID, "ke_pod_spread_terms: a weight outside 1..100 (score terms) or not 0 (filter terms)");
+      r.tw[t] = (uint32_t)group | (uint32_t)kind << 16 | (uint32_t)weight << 24;
+      r.tp[t >> 1] |= (uint32_t)param << ((t & 1) * 16);
+    }
+    for (int32_t q = member_offsets[p], m = 0; q < member_offsets[p + 1]; q++, m++) {
+      const int32_t group = members[q];
+      if (group < 1 || group > c.sg_n) return fail(KE_ERR_INVALID, "ke_pod_spread_terms: a member outside 1..n_groups");
+      for (int32_t u = member_offsets[p]; u < q; u++)
+        if (members[u] == group) return fail(KE_ERR_INVALID, "ke_pod_spread_terms: a repeated member");
+      r.mem[m >> 1] |= (uint32_t)group << ((m & 1) * 16);
+    }
+  }
+  c.st_staged.swap(recs);
+  c.st_staged_on = true;
+  return KE_OK;
+}
+
 // The ke_pod_node_sets, ke_pod_node_scores, ke_pod_spread_groups and ke_pod_spread_domains ids of this call, all
 // consumed whether it goes on or not; Context::ns_call / nsc_call / sg_call / sd_call = the ids of a kind when any of
 // them is non-zero (the device entry points then run the node-set / score-offset / spread-group / spread-domain kernels).  Such a call is refused here, before any state
 // changes, where those kernels are not built: node-sharded contexts, and for ke_schedule (`sched`) anything but a
 // plain queue (ke_schedule_submit's sense, with device_async_ok's conditions).  The message names the sets when a
-// set id is non-zero, else the scores when a table id is, else the spread groups, else the spread domains.
+// set id is non-zero, else the scores when a table id is, else the spread groups, else the spread domains, else the
+// spread terms.  ke_pod_spread_terms' lists go the same way: Context::st_call = the call's records when
+// one of them is not empty; staged together with group ids they are KE_ERR_INVALID, and a pod whose score terms could
+// push total + 1 out of the key's 10 bits is KE_ERR_UNSUPPORTED.
 static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool sched) {
   Context& c = ctx->c;
   c.ns_call = nullptr;
   c.nsc_call = nullptr;
   c.sg_call = nullptr;
   c.sd_call = nullptr;
+  c.st_call = nullptr;
   const bool sets_on = c.ns_staged_on, scores_on = c.nsc_staged_on, groups_on = c.sg_staged_on, domains_on = c.sd_staged_on;
-  if (!sets_on && !scores_on && !groups_on && !domains_on) return KE_OK;
-  c.ns_staged_on = c.nsc_staged_on = c.sg_staged_on = c.sd_staged_on = false;
+  const bool terms_on = c.st_staged_on;
+  if (!sets_on && !scores_on && !groups_on && !domains_on && !terms_on) return KE_OK;
+  c.ns_staged_on = c.nsc_staged_on = c.sg_staged_on = c.sd_staged_on = c.st_staged_on = false;
   c.ns_call_ids.clear();
   c.nsc_call_ids.clear();
   c.sg_call_ids.clear();
   c.sd_call_ids.clear();
   if (domains_on) c.sd_call_ids.swap(c.sd_staged);
   c.sd_staged.clear();
+  c.st_call_recs.clear();
+  c.st_listed.clear();
+  if (terms_on) c.st_call_recs.swap(c.st_staged);
+  c.st_staged.clear();
   if (sets_on) c.ns_call_ids.swap(c.ns_staged);
   if (scores_on) c.nsc_call_ids.swap(c.nsc_staged);
   if (groups_on) c.sg_call_ids.swap(c.sg_staged);
@@ -907,7 +963,11 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
     return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_spread_groups ids'");
   if (domains_on && (int32_t)c.sd_call_ids.size() != n_pods)
     return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_spread_domains ids'");
-  bool any = false, any_sc = false, any_sg = false, any_sd = false;
+  if (terms_on && (int32_t)c.st_call_recs.size() != n_pods)
+    return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_spread_terms lists'");
+  if (terms_on && groups_on)
+    return fail(KE_ERR_INVALID, "a call with both ke_pod_spread_groups ids and ke_pod_spread_terms lists staged");
+  bool any = false, any_sc = false, any_sg = false, any_sd = false, any_st = false;
   for (int32_t id : c.ns_call_ids) {
     if (id < 0 || id > c.ns_n) return fail(KE_ERR_INVALID, "a staged node set id is outside the table loaded since");
     any = any || id != 0;
@@ -924,12 +984,25 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
     if (id < 0 || id > c.sd_n) return fail(KE_ERR_INVALID, "a staged spread domain group id is outside the table loaded since");
     any_sd = any_sd || id != 0;
   }
-  if (!any && !any_sc && !any_sg && !any_sd) return KE_OK;
+  int32_t st_sum = 0;  // the largest bonus a pod's score terms can add
+  for (const PodTerms& r : c.st_call_recs) {
+    int32_t sum = 0;
+    for (int t = 0; t < POD_TERMS; t++) {
+      if (st_group(r, t) > c.sg_n) return fail(KE_ERR_INVALID, "a staged spread term's group is outside the table loaded since");
+      if (st_kind(r, t) >= ST_PREFER_FEWER) sum += st_weight(r, t) * (int32_t)st_param(r, t);
+    }
+    for (int m = 0; m < POD_MEMBERS; m++)
+      if (st_member(r, m) > c.sg_n) return fail(KE_ERR_INVALID, "a staged spread member is outside the table loaded since");
+    st_sum = std::max(st_sum, sum);
+    c.st_listed.push_back(st_empty(r) ? 0 : 1);
+    any_st = any_st || !st_empty(r);
+  }
+  if (!any && !any_sc && !any_sg && !any_sd && !any_st) return KE_OK;
   int rc = check_pods(pods, n_pods, &c, sched);
   if (rc) return rc;
-  auto no = [any, any_sc, any_sg](const char* what) {
+  auto no = [any, any_sc, any_sg, any_sd](const char* what) {
     return fail(KE_ERR_UNSUPPORTED,
-                std::string(any ? "node sets: " : any_sc ? "node scores: " : any_sg ? "spread groups: " : "spread domains: ") + what);
+                std::string(any ? "node sets: " : any_sc ? "node scores: " : any_sg ? "spread groups: " : any_sd ? "spread domains: " : "spread terms: ") + what);
   };
   if (c.cfg.global_node_offset != 0 || (c.dev && device_sharded(&c))) return no("a node-sharded context");
   if (sched) {
@@ -945,6 +1018,18 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
       if (f & (PF_DS | PF_DS_HINT)) return no("a DeviceShare pod in ke_schedule");
       if (f & PF_CPUSET) return no("a cpuset pod in ke_schedule");
     }
+  }
+  if (any_st) {
+    // the key holds total + 1 in 10 bits: the plugins' total, the largest table entry the call can add and the
+    // largest bonus of a pod must fit together
+    int32_t cap = node_score_cap(c.cfg);
+    if (any_sc && !c.nsc_vals.empty()) cap -= (int32_t)*std::max_element(c.nsc_vals.begin(), c.nsc_vals.end());
+    if (st_sum > cap)
+      return fail(KE_ERR_UNSUPPORTED, "spread terms: a pod's score terms can add " + std::to_string(st_sum) + ", above the cap " +
+                                          std::to_string(cap) + " = 1022 - 100 * (sum of the Score plugin weights)" +
+                                          (any_sc ? " - the largest score table entry" : "") +
+                                          ": total + 1 must fit the key's 10 bits");
+    c.st_call = c.st_call_recs.data();
   }
   if (any) c.ns_call = c.ns_call_ids.data();
   if (any_sc) c.nsc_call = c.nsc_call_ids.data();

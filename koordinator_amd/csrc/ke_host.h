@@ -280,6 +280,15 @@ struct Context {
   bool sd_staged_on = false;
   std::vector<int32_t> sd_call_ids;
   const int32_t* sd_call = nullptr;
+  // Spread terms (ke_pod_spread_terms): per-pod term and member lists over the spread groups' counts,
+  // one packed record a pod.  The staging for the next call, and the records of the call in progress (nullptr: every
+  // list empty, the call runs the kernels it ran without them) with st_listed[p] != 0 where pod p's record is not
+  // empty (the plan's `grouped` mark).  A call with term lists carries no spread group ids (sg_call == nullptr).
+  std::vector<PodTerms> st_staged;
+  bool st_staged_on = false;
+  std::vector<PodTerms> st_call_recs;
+  std::vector<int32_t> st_listed;
+  const PodTerms* st_call = nullptr;
   // the KE_RSV_MATCHED pod of the current segment: its nodes with matched reservations, their
   // (node, ScoreReservation of the nominated one, smallest order) for the device pick, the nominated index
   std::vector<int32_t> rsv_nodes;

@@ -126,11 +126,16 @@ struct SoA {
   const SdGroup* sd_par;
   const int32_t* sd_ids;
   uint64_t* sd_mask;
+  // spread terms: the current call's term / member record per pod, parallel to its DevPod array, over
+  // the spread groups' count table (sg_cnt; such a call's sg_ids are all zero).  Read only by the NS_TERMS
+  // instantiations; the one-wave replay of a grouped batch increments the count of every (member, node) it Reserves.
+  const PodTerms* st_rec;
 };
 // NS, the template mode of every kernel that makes a score or key: 0 = the call has no per-pod ids, NS_SETS = its
 // ns_ids words are node set ids, NS_SCORES = they are (score table id << 16) | node set id, NS_GROUPS = NS_SCORES and
-// the pods' spread groups (sg_ids) besides, NS_DOMAINS = NS_GROUPS and the pods' spread domain groups (sd_ids)
-constexpr int NS_SETS = 1, NS_SCORES = 2, NS_GROUPS = 3, NS_DOMAINS = 4;
+// the pods' spread groups (sg_ids) besides, NS_DOMAINS = NS_GROUPS and the pods' spread domain groups (sd_ids),
+// NS_TERMS = NS_DOMAINS and the pods' spread term records (st_rec)
+constexpr int NS_SETS = 1, NS_SCORES = 2, NS_GROUPS = 3, NS_DOMAINS = 4, NS_TERMS = 5;
 // node `node` is in the set of id word `idw` (NS instantiations; every node < 64 * ns_wps is in bounds, the ids
 // checked by the host)
 template <int NS>
@@ -152,6 +157,20 @@ __device__ __forceinline__ bool sd_in_mask(const SoA& s, int map, uint64_t mask,
 // ... of pod `p` of the call (wave-uniform p: scalar loads of the pod's group, its map and the pod's mask)
 __device__ __forceinline__ bool sd_ok(const SoA& s, int p, int node) {
   return sd_in_mask(s, s.sd_par[s.sd_ids[p]].map, s.sd_mask[p], node);
+}
+// the spread terms of record `r` (wave-uniform) on `node` (NS_TERMS; node < sg_stride), for the eval kernels: the lanes
+// read consecutive counts of each term's wave-uniform row, plain loads as in sg_capped.
+// Returns whether a filter term closes the node; *bonus = what the score terms add to a feasible total
+__device__ __forceinline__ bool st_eval(const SoA& s, const PodTerms& r, int node, int32_t* bonus) {
+  uint32_t c[POD_TERMS];
+#pragma unroll
+  for (int t = 0; t < POD_TERMS; t++)  // (a wave-uniform test: an unused slot costs no load)
+    c[t] = st_kind(r, t) ? s.sg_cnt[(int64_t)st_group(r, t) * s.sg_stride + node] : (uint16_t)0;
+  bool filtered = false;
+  *bonus = 0;
+#pragma unroll
+  for (int t = 0; t < POD_TERMS; t++) st_apply(r, t, c[t], &filtered, bonus);
+  return filtered;
 }
 // a fresh key of (pod with set `sid`, node): 0 (filtered) outside the set
 template <int NS>
@@ -3326,7 +3345,8 @@ __global__ __launch_bounds__(64) void k_domain_masks(SoA s, int base, int n) {
 // The classification ke_eval and ke_diagnose share, of (pod p, node i) in the first pass: the pod's node set ahead of
 // every other filter (NS: the call carries ids; a pair outside the set is KE_REASON_NODE_SET -- scores 0, total -1,
 // never deferred, and not part of the pod's DeviceShare normalisation max), with NS_GROUPS the pod's spread group cap
-// right behind it and with NS_DOMAINS the pod's eligible domains behind that (same report), then eval_pair; *deferred: the pair is
+// right behind it, with NS_DOMAINS the pod's eligible domains behind that and with NS_TERMS the pod's filter terms
+// behind those (same report), then eval_pair; *deferred: the pair is
 // left to k_numa_fallback / k_numa_finish (o.status == STATUS_DEFERRED).
 template <bool NUMA, bool CPU, int NS>
 __device__ __forceinline__ EvalOut classify_pair(const SoA& s, const NodeRegs& n, bool expired, const DevPod* pods, int p,
@@ -3338,7 +3358,13 @@ __device__ __forceinline__ EvalOut classify_pair(const SoA& s, const NodeRegs& n
   if constexpr (NS >= NS_GROUPS) out_of_set = out_of_set || sg_capped(s, s.sg_ids[p], i);
   // NS_DOMAINS: so does a node whose domain is closed to the pod's spread domain group (64 consecutive domain ids of a
   // wave-uniform map row against the pod's mask)
-  if constexpr (NS == NS_DOMAINS) out_of_set = out_of_set || !sd_ok(s, p, i);
+  if constexpr (NS >= NS_DOMAINS) out_of_set = out_of_set || !sd_ok(s, p, i);
+  // NS_TERMS: and a node one of the pod's filter terms closes (the score terms are k_parity_finalize's; per term the
+  // lanes read 64 consecutive counts of a wave-uniform row)
+  if constexpr (NS == NS_TERMS) {
+    int32_t bonus;
+    out_of_set = st_eval(s, s.st_rec[p], i, &bonus) || out_of_set;
+  }
   if (out_of_set) {
     EvalOut o;
     o.status = KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE;
@@ -3357,8 +3383,8 @@ __device__ __forceinline__ EvalOut classify_pair(const SoA& s, const NodeRegs& n
 // eval_pair's own NF_VALID test, behind the node-set gate).
 // IDS: the call carries per-pod ids (SoA::ns_ids): the low half of a word is the pod's node set (the high half, a
 // score table id, is k_parity_finalize's).  GRP: it carries spread group ids too (NS_GROUPS); DOM: and spread domain
-// group ids (NS_DOMAINS).
-template <bool NUMA, bool CPU, bool IDS = false, bool GRP = false, bool DOM = false>
+// group ids (NS_DOMAINS); TRM: and spread term records (NS_TERMS).
+template <bool NUMA, bool CPU, bool IDS = false, bool GRP = false, bool DOM = false, bool TRM = false>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, const DevPod* __restrict__ pods, int n_pods,
                                                             int pods_per_block, KArgs k, ParityOut out,
                                                             uint64_t* defer_list, uint32_t* defer_cnt) {
@@ -3379,7 +3405,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, const DevPod*
     uint32_t m = 0;
     bool deferred = false;
     if (live) {
-      const EvalOut o = classify_pair<NUMA, CPU, DOM ? NS_DOMAINS : GRP ? NS_GROUPS : IDS ? NS_SCORES : 0>(s, n, expired, pods, p, k, i, nv, &deferred);
+      const EvalOut o = classify_pair<NUMA, CPU, TRM ? NS_TERMS : DOM ? NS_DOMAINS : GRP ? NS_GROUPS : IDS ? NS_SCORES : 0>(s, n, expired, pods, p, k, i, nv, &deferred);
       out.store(p, i, o);
       m = o.total >= 0 ? (uint32_t)o.ds + 1 : 0u;
     }
@@ -3521,7 +3547,9 @@ __device__ __forceinline__ int32_t ds_norm(int32_t raw, uint32_t dsmax1) {
 // normalized DeviceShare score into the weighted sum, then selectHost's packed-key max per pod
 // SC: the call carries score table ids (packed in ids[], SoA::nsc_tbl): a feasible pair's offset goes into its
 // total here, after the normalisation and for the pairs the NUMA deferral finished too, ahead of the key
-template <bool SC = false>
+// TRM: it carries spread term records (SoA::st_rec, NS_TERMS): a feasible pair's bonus goes in with the offset (a pair
+// a filter term closes has total -1 from classify_pair)
+template <bool SC = false, bool TRM = false>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_parity_finalize(int n_nodes, KArgs k, const int16_t* ds,
                                                                 int16_t* total, const uint32_t* dsmax,
                                                                 uint32_t* best_key, SoA s) {
@@ -3534,6 +3562,11 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_parity_finalize(int n_nodes, KAr
     if (t >= 0) {
       t += k.wp_ds * ds_norm(ds[o], dsmax[p]);
       if constexpr (SC) t += ns_off<NS_SCORES>(s, s.ns_ids[p], i);  // (i < n_nodes <= nsc_stride)
+      if constexpr (TRM) {
+        int32_t bonus;
+        st_eval(s, s.st_rec[p], i, &bonus);
+        t += bonus;
+      }
       total[o] = (int16_t)t;
     }
     key = make_key(t, i);
@@ -3585,7 +3618,12 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_batch(SoA s, int lo, int hi
       if (NS && !ns_ok<NS>(s, s.ns_ids[base + p], i)) tot = -1;  // (wave-uniform word address)
       if constexpr (NS >= NS_SCORES) tot = tot >= 0 ? tot + ns_off<NS>(s, s.ns_ids[base + p], i) : tot;
       if constexpr (NS >= NS_GROUPS) tot = sg_capped(s, s.sg_ids[base + p], i) ? -1 : tot;  // (wave-uniform row)
-      if constexpr (NS == NS_DOMAINS) tot = sd_ok(s, base + p, i) ? tot : -1;  // (wave-uniform map row and mask)
+      if constexpr (NS >= NS_DOMAINS) tot = sd_ok(s, base + p, i) ? tot : -1;  // (wave-uniform map row and mask)
+      if constexpr (NS == NS_TERMS) {  // (wave-uniform record and rows)
+        int32_t bonus;
+        const bool closed = st_eval(s, s.st_rec[base + p], i, &bonus);
+        tot = closed ? -1 : tot >= 0 ? tot + bonus : tot;
+      }
       scores[(int64_t)p * score_stride + i] = (uint16_t)(tot + 1);
       continue;
     }
@@ -3661,10 +3699,22 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
   }
   // NS_DOMAINS: one more reason for bit q -- this lane's node's domain (in the map of pod q's spread domain group: the
   // pods of the group may use different maps) is outside pod q's eligible-domain mask (wave-uniform loads)
-  if constexpr (NS == NS_DOMAINS) {
+  if constexpr (NS >= NS_DOMAINS) {
 #pragma unroll
     for (int q = 0; q < EVAL_PPB; q++)
       if (q < np && i < hi && !sd_ok(s, base + p0 + q, i)) capped |= 1u << q;
+  }
+  // NS_TERMS: per pod q this lane's node's count for each of the pod's terms (wave-uniform record and rows, coalesced
+  // loads); the filter terms are one more reason for bit q, the score terms' bonus joins pod q's offset -- both go
+  // into a feasible total before the store, and their sum stays within the key's range (take_node_sets)
+  if constexpr (NS == NS_TERMS) {
+#pragma unroll
+    for (int q = 0; q < EVAL_PPB; q++)
+      if (q < np && i < hi) {
+        int32_t bonus;
+        if (st_eval(s, s.st_rec[base + p0 + q], i, &bonus)) capped |= 1u << q;
+        off[q >> 2] += (uint64_t)(uint32_t)bonus << ((q & 3) * 16);
+      }
   }
   if ((int)threadIdx.x < 4 * np) {
     const int q = threadIdx.x >> 2, c = threadIdx.x & 3;
@@ -5799,6 +5849,13 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
 //   batch is of pod j's group: the mask holds for the whole batch), and the owner lane's Reserve increments the count
 //   of (pod j's group, the node's domain), which no later pod of the batch reads.  Lane c reads its node's domain in
 //   pod j+1's map behind pod j's Reserve (maps do not change during a call: no ordering needed).
+//   NS_TERMS: pod j's term / member record is wave-uniform, fetched from global memory one pod ahead
+//   with its DevPod.  Lane c holds its node's current count for each of pod j's terms: a changed node's fresh key is 0
+//   where a filter term closes it -- or open where an AFFINITY term's group arrived there with an earlier pod of the
+//   batch -- and a feasible total takes the score terms' bonus from those counts before the key is packed.  The owner
+//   lane's Reserve does load + saturating add + store for every member; behind it and the wave_lds_sync every lane
+//   < n_chg, the new owner included, reads its node's counts for pod j+1's terms.  As with NS_GROUPS, lane c is the
+//   only reader and writer of its node's counts during the batch.
 template <bool DS, bool NUMA, bool QUOTA, bool EXT, int NS>
 __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const SoA& s, const int base, const int B,
                                              const KArgs& k, int32_t* __restrict__ chosen,
@@ -5847,11 +5904,15 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
   int dgid = 0, dmap = 0;
   uint64_t dmask = ~0ull;
   uint32_t ddom = 0;
-  if constexpr (NS == NS_DOMAINS) {
+  if constexpr (NS >= NS_DOMAINS) {
     dgid = s.sd_ids[base];
     dmap = s.sd_par[dgid].map;
     dmask = s.sd_mask[base];
   }
+  // NS_TERMS: pod j's record (wave-uniform) and this lane's node's counts for its terms (lane < n_chg)
+  PodTerms tr = {};
+  uint32_t tc[POD_TERMS] = {0u, 0u, 0u, 0u};
+  if constexpr (NS == NS_TERMS) tr = s.st_rec[base];
   RPROF_DECL
   for (int j = 0; j < B; j++) {
     const bool more = j + 1 < B;
@@ -5865,11 +5926,13 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
     }
     int dgid_n = 0, dmap_n = 0;
     uint64_t dmask_n = ~0ull;
-    if constexpr (NS == NS_DOMAINS) {
+    if constexpr (NS >= NS_DOMAINS) {
       dgid_n = s.sd_ids[base + jn];
       dmap_n = s.sd_par[dgid_n].map;
       dmask_n = s.sd_mask[base + jn];
     }
+    PodTerms tr_n = {};
+    if constexpr (NS == NS_TERMS) tr_n = s.st_rec[base + jn];
     const double pdd_n[4] = {L.pd[jn][0], L.pd[jn][1], L.pd[jn][2], L.pd[jn][3]};
     const double estd[2] = {pdd[0], pdd[1]}, reqd[2] = {pdd[2], pdd[3]};
     const uint32_t ck_n = more ? s_cand[(j + 1) * KMAX + lane] : 0u;
@@ -5906,9 +5969,17 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
       } else {
         tot = fast_total<EXT>(fast, pod, estd, reqd, k);
       }
+      bool closed = false;  // NS_TERMS: a filter term of pod j closes this node at its current counts
+      if constexpr (NS == NS_TERMS) {
+        int32_t bonus = 0;
+#pragma unroll
+        for (int t = 0; t < POD_TERMS; t++) st_apply(tr, t, tc[t], &closed, &bonus);
+        tot = tot >= 0 ? tot + bonus : tot;
+      }
       kc = ns_mkkey<NS>(s, nsid_of<NS>(L, j), my_node, tot);
+      if constexpr (NS == NS_TERMS) kc = closed ? 0u : kc;
       if constexpr (NS >= NS_GROUPS) kc = gcnt >= gcap ? 0u : kc;  // the group is at its cap on this node now
-      if constexpr (NS == NS_DOMAINS) kc = ddom < 64u && ((dmask >> ddom) & 1ull) ? kc : 0u;  // the domain is closed to pod j
+      if constexpr (NS >= NS_DOMAINS) kc = ddom < 64u && ((dmask >> ddom) & 1ull) ? kc : 0u;  // the domain is closed to pod j
     }
     RPROF(2)
     const uint32_t bc = wave_max_u32(kc);
@@ -5988,7 +6059,18 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
             st_sc1(cnt, (uint16_t)(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1));
           }
         }
-        if constexpr (NS == NS_DOMAINS) {  // the spread domain group's count of this node's domain (a winner's is open)
+        if constexpr (NS == NS_TERMS) {  // every member's count on this node, saturating (plain vector stores)
+#pragma unroll
+          for (int m = 0; m < POD_MEMBERS; m++) {
+            const int g = st_member(tr, m);
+            if (g) {
+              uint16_t* const cnt = s.sg_cnt + (int64_t)g * s.sg_stride + my_node;
+              const uint32_t v = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              st_sc1(cnt, (uint16_t)(v < 65535u ? v + 1u : 65535u));
+            }
+          }
+        }
+        if constexpr (NS >= NS_DOMAINS) {  // the spread domain group's count of this node's domain (a winner's is open)
           if (dgid) {
             const uint32_t d = s.sd_map[(int64_t)dmap * s.sd_stride + my_node];
             uint32_t* const cnt = s.sd_cnt + (int64_t)dgid * 64 + d;
@@ -6044,11 +6126,19 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
       gid = gid_n;
       gcap = gcap_n;
     }
-    if constexpr (NS == NS_DOMAINS) {  // this lane's node's domain in the map of pod j+1's group
+    if constexpr (NS >= NS_DOMAINS) {  // this lane's node's domain in the map of pod j+1's group
       ddom = lane < n_chg ? (uint32_t)s.sd_map[(int64_t)dmap_n * s.sd_stride + my_node] : 0u;
       dgid = dgid_n;
       dmap = dmap_n;
       dmask = dmask_n;
+    }
+    if constexpr (NS == NS_TERMS) {  // this lane's node's counts for pod j+1's terms, behind pod j's increments
+#pragma unroll
+      for (int t = 0; t < POD_TERMS; t++)
+        tc[t] = lane < n_chg && st_kind(tr_n, t) ? __hip_atomic_load(s.sg_cnt + (int64_t)st_group(tr_n, t) * s.sg_stride + my_node,
+                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                             : 0u;
+      tr = tr_n;
     }
     pod = pod_n;
 #pragma unroll
@@ -8096,19 +8186,27 @@ static int spread_domains_sync(Context* ctx) {
 // the mode of a call's kernels from its ids: spread domains (which read the other tables' row 0 at least), groups
 // (likewise), score tables, node sets, none
 static int call_ns(const Context* ctx) {
-  return ctx->sd_call ? NS_DOMAINS : ctx->sg_call ? NS_GROUPS : ctx->nsc_call ? NS_SCORES : ctx->ns_call ? NS_SETS : 0;
+  return ctx->st_call ? NS_TERMS : ctx->sd_call ? NS_DOMAINS : ctx->sg_call ? NS_GROUPS : ctx->nsc_call ? NS_SCORES : ctx->ns_call ? NS_SETS : 0;
 }
 // the tables a call of mode `ns` reads, brought up to date
 static int id_tables_sync(Context* ctx, int ns) {
   if (ns) RC_OK(node_sets_sync(ctx));
   if (ns >= NS_SCORES) RC_OK(node_scores_sync(ctx));
   if (ns >= NS_GROUPS) RC_OK(spread_groups_sync(ctx));
-  if (ns == NS_DOMAINS) RC_OK(spread_domains_sync(ctx));
+  if (ns >= NS_DOMAINS) RC_OK(spread_domains_sync(ctx));  // (NS_TERMS without domain groups: row 0 alone)
   return KE_OK;
 }
 // the eligible-domain masks of pods [base, base + n) of a call with spread domain ids, on stream `st`
 static void launch_domain_masks(DeviceState* d, int base, int n, hipStream_t st) {
   if (n > 0) hipLaunchKernelGGL(k_domain_masks, dim3((unsigned)n), dim3(64), 0, st, d->soa, base, n);
+}
+
+// the int32 words of a call's per-pod ids and records behind its DevPod array (upload_pods lays them out): the packed
+// set / table id words, the spread group ids, the spread domain ids and the spread term records -- a later kind brings
+// the earlier ones' words with it
+static int64_t id_words(const Context* ctx, int64_t n_pods) {
+  const bool st = ctx->st_call, sd = st || ctx->sd_call, sg = sd || ctx->sg_call, ns = sg || ctx->ns_call || ctx->nsc_call;
+  return n_pods * ((ns ? 1 : 0) + (sg ? 1 : 0) + (sd ? 1 : 0) + (st ? 8 : 0));
 }
 
 // The call's upload block: the DevPod records, the node set ids when present (int32 each) and room for
@@ -8127,7 +8225,10 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t
   const int32_t* sc = ctx->nsc_call;
   const int32_t* sg = ctx->sg_call;
   const int32_t* sd = ctx->sd_call;
-  const int64_t ns_words = (ns || sc || sg || sd ? (int64_t)n_pods : 0) + (sg || sd ? (int64_t)n_pods : 0) + (sd ? (int64_t)n_pods : 0);
+  // -- and in a call with spread term lists all three (zero where the call has none; never group ids) and the pods'
+  // eight-word records behind them
+  const PodTerms* tr = ctx->st_call;
+  const int64_t ns_words = id_words(ctx, n_pods);
   if (!dp.resize((size_t)n_pods, sizeof(int32_t) * (size_t)(ns_words + tail_words)))
     return fail(KE_ERR_DEVICE, "hipHostMalloc of the pod staging buffer");
   std::vector<DevPodHint>& ph = d->host_ph;  // the hinted pods' records; DevPod::ring_bw = slot
@@ -8154,18 +8255,25 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t
   d->soa.sg_ids = nullptr;
   d->soa.sd_ids = nullptr;
   d->soa.sd_mask = nullptr;
-  if (sg || sd) {
+  d->soa.st_rec = nullptr;
+  if (sg || sd || tr) {
     if (sg) std::copy(sg, sg + n_pods, h_words + n_pods);
     else std::fill(h_words + n_pods, h_words + 2 * (int64_t)n_pods, 0);
     d->soa.sg_ids = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods) + n_pods;
   }
-  if (sd) {
-    std::copy(sd, sd + n_pods, h_words + 2 * (int64_t)n_pods);
+  if (tr) {
+    static_assert(sizeof(PodTerms) == 8 * sizeof(int32_t), "id_words");
+    std::memcpy(h_words + 3 * (int64_t)n_pods, tr, sizeof(PodTerms) * (size_t)n_pods);
+    d->soa.st_rec = reinterpret_cast<const PodTerms*>(reinterpret_cast<int32_t*>(d->call.d_pods + n_pods) + 3 * (int64_t)n_pods);
+  }
+  if (sd || tr) {
+    if (sd) std::copy(sd, sd + n_pods, h_words + 2 * (int64_t)n_pods);
+    else std::fill(h_words + 2 * (int64_t)n_pods, h_words + 3 * (int64_t)n_pods, 0);
     d->soa.sd_ids = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods) + 2 * (int64_t)n_pods;
     RC_OK(d->call.d_sd_mask.reserve((size_t)std::max<int32_t>(n_pods, 1)));
     d->soa.sd_mask = d->call.d_sd_mask;
   }
-  if (ns || sc || sg || sd) {
+  if (ns || sc || sg || sd || tr) {
     static_assert(KE_MAX_NODE_SETS < (1 << 16) && KE_MAX_NODE_SCORE_TABLES < (1 << 15), "the packed id word");
     for (int32_t p = 0; p < n_pods; p++) h_words[p] = (ns ? ns[p] : 0) | (sc ? sc[p] << 16 : 0);
     d->soa.ns_ids = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods);
@@ -8208,7 +8316,7 @@ static auto with_ns_ext(int ns, bool ext, F&& f) {
          : ns == 0       ? e(std::integral_constant<int, 0>{})
                          : Fn(nullptr);
 }
-// ... and NS_GROUPS / NS_DOMAINS, for the kernels a grouped batch reaches (pick_eval_batch, pick_eval_plain,
+// ... and NS_GROUPS / NS_DOMAINS / NS_TERMS, for the kernels a grouped batch reaches (pick_eval_batch, pick_eval_plain,
 // pick_resolve)
 template <class F>
 static auto with_nsg_ext(int ns, bool ext, F&& f) {
@@ -8216,6 +8324,8 @@ static auto with_nsg_ext(int ns, bool ext, F&& f) {
     return with_bool(ext, [&](auto EXT) { return f(std::integral_constant<int, NS_GROUPS>{}, EXT); });
   if (ns == NS_DOMAINS)
     return with_bool(ext, [&](auto EXT) { return f(std::integral_constant<int, NS_DOMAINS>{}, EXT); });
+  if (ns == NS_TERMS)
+    return with_bool(ext, [&](auto EXT) { return f(std::integral_constant<int, NS_TERMS>{}, EXT); });
   return with_ns_ext(ns, ext, f);
 }
 
@@ -8225,6 +8335,7 @@ static EvalParityFn pick_eval_parity(bool numa, bool cpu, int ns) {
   return with_bool(ns != 0, [&](auto IDS) {
     return with_bool(numa, [&](auto NUMA) {
       return with_bool(cpu, [&](auto CPU) -> EvalParityFn {
+        if (ns == NS_TERMS) return k_eval_parity<KV(NUMA), KV(CPU), true, true, true, true>;
         if (ns == NS_DOMAINS) return k_eval_parity<KV(NUMA), KV(CPU), true, true, true>;
         if (ns == NS_GROUPS) return k_eval_parity<KV(NUMA), KV(CPU), true, true>;
         return k_eval_parity<KV(NUMA), KV(CPU), KV(IDS)>;
@@ -8233,6 +8344,7 @@ static EvalParityFn pick_eval_parity(bool numa, bool cpu, int ns) {
   });
 }
 static auto pick_parity_finalize(int ns) {
+  if (ns == NS_TERMS) return k_parity_finalize<true, true>;
   return with_bool(ns >= NS_SCORES, [](auto SC) { return k_parity_finalize<KV(SC)>; });
 }
 // DS x NUMA x CPU; the plain instantiation (none of them) also NS x EXT, and a DeviceShare one the hint path H (a
@@ -8305,6 +8417,7 @@ static DiagEvalFn pick_diag_eval(bool numa, bool cpu, int ns) {
   return with_bool(ns != 0, [&](auto SETS) {
     return with_bool(numa, [&](auto NUMA) {
       return with_bool(cpu, [&](auto CPU) -> DiagEvalFn {
+        if (ns == NS_TERMS) return k_diag_eval<KV(NUMA), KV(CPU), NS_TERMS>;
         if (ns == NS_DOMAINS) return k_diag_eval<KV(NUMA), KV(CPU), NS_DOMAINS>;
         if (ns == NS_GROUPS) return k_diag_eval<KV(NUMA), KV(CPU), NS_GROUPS>;
         return k_diag_eval<KV(NUMA), KV(CPU), KV(SETS) ? NS_SETS : 0>;
@@ -8362,7 +8475,7 @@ static int pair_pass_begin(Context* ctx, int32_t n_pods, const ke_pod* pods, int
   if (rc || n_pods == 0) return rc;
   if ((rc = id_tables_sync(ctx, ns))) return rc;
   if ((rc = upload_pods(ctx, n_pods, pods))) return rc;
-  if (ns == NS_DOMAINS) launch_domain_masks(d, 0, n_pods, d->stream);  // (ke_eval / ke_diagnose: one wave per pod of the call)
+  if (ns >= NS_DOMAINS) launch_domain_masks(d, 0, n_pods, d->stream);  // (ke_eval / ke_diagnose: one wave per pod of the call)
   HIP_OK(hipMemsetAsync(d->soa.kerr, 0, sizeof(int32_t), d->stream));
   pp->k = make_kargs(ctx, now);
   for (const DevPod& q : d->call.host_pods) pp->cpu = pp->cpu || (q.flags & PF_CPUSET);
@@ -8444,7 +8557,7 @@ int device_diagnose(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t no
                     int32_t words_per_pod, uint64_t* const* bits) {
   DeviceState* d = ctx->dev;
   // (score table ids do not filter: ke_diagnose drops them; spread groups do)
-  const int ns = ctx->sd_call ? NS_DOMAINS : ctx->sg_call ? NS_GROUPS : ctx->ns_call ? NS_SETS : 0;
+  const int ns = ctx->st_call ? NS_TERMS : ctx->sd_call ? NS_DOMAINS : ctx->sg_call ? NS_GROUPS : ctx->ns_call ? NS_SETS : 0;
   PairPass pp;
   int rc = pair_pass_begin(ctx, n_pods, pods, now, ns, &pp);
   if (rc || n_pods == 0) return rc;
@@ -8568,6 +8681,7 @@ struct Completion {
   int n_pipelined;
   std::vector<int32_t> groups;  // the call's spread group ids (empty: none): the host copy takes its placements' increments
   std::vector<int32_t> domains;  // ... and its spread domain group ids
+  std::vector<PodTerms> terms;   // ... and its spread term records: every member of a placement
 };
 
 static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
@@ -8623,6 +8737,17 @@ static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
     const int32_t g = c.groups[p], node = chosen[p];
     if (g > 0 && g <= ctx->sg_n && node >= 0 && (int64_t)node < ctx->sg_stride)
       ctx->sg_cnt[(size_t)((int64_t)(g - 1) * ctx->sg_stride + node)]++;
+  }
+  // spread terms: every member of a placement, saturating as the device's Reserve does
+  for (size_t p = 0; p < c.terms.size(); p++) {
+    const int32_t node = chosen[p];
+    if (node < 0 || (int64_t)node >= ctx->sg_stride) continue;
+    for (int m = 0; m < POD_MEMBERS; m++) {
+      const int g = st_member(c.terms[p], m);
+      if (g < 1 || g > ctx->sg_n) continue;
+      uint16_t& v = ctx->sg_cnt[(size_t)((int64_t)(g - 1) * ctx->sg_stride + node)];
+      if (v < 65535) v++;
+    }
   }
   // spread domains: likewise, on the count of the placement's domain in the group's map
   for (size_t p = 0; p < c.domains.size(); p++) {
@@ -8696,7 +8821,8 @@ struct ScheduleCall {
   // A call with spread domain ids likewise: its batches holding a pod with such an id are grouped and
   // run the NS_DOMAINS instantiations, the others what they ran before.
   const int ns;
-  const bool groups, domains;
+  // A call with spread term lists likewise: NS_TERMS for the batches holding a pod with a list.
+  const bool groups, domains, terms;
   // the plan
   bool fixup = false, two_es = false, ahead = false;  // the schedule of the call's pipelined runs (plan())
   std::vector<Batch> batches;
@@ -8734,8 +8860,8 @@ struct ScheduleCall {
         numa(d->has(ST_NUMA)), quota(!ctx_->quotas.empty()), sharded(d->world > 1 || d->comm || d->host_fn),
         matched(!ctx_->rsv_pairs.empty() || ctx_->rsv_affinity),
         ns(ctx_->nsc_call ? NS_SCORES : ctx_->ns_call ? NS_SETS : 0), groups(ctx_->sg_call != nullptr),
-        domains(ctx_->sd_call != nullptr) {}
-  int batch_ns(int b) const { return !batches[(size_t)b].grouped ? ns : domains ? NS_DOMAINS : NS_GROUPS; }
+        domains(ctx_->sd_call != nullptr), terms(ctx_->st_call != nullptr) {}
+  int batch_ns(int b) const { return !batches[(size_t)b].grouped ? ns : terms ? NS_TERMS : domains ? NS_DOMAINS : NS_GROUPS; }
 
   hipError_t copy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
     n_copies++;
@@ -8759,7 +8885,9 @@ struct ScheduleCall {
       return fail(KE_ERR_DEVICE, "internal: spread group ids of another call");
     if (domains && (int64_t)ctx->sd_call_ids.size() != n_pods)
       return fail(KE_ERR_DEVICE, "internal: spread domain ids of another call");
-    if ((rc = id_tables_sync(ctx, domains ? NS_DOMAINS : groups ? NS_GROUPS : ns))) return rc;
+    if (terms && (int64_t)ctx->st_call_recs.size() != n_pods)
+      return fail(KE_ERR_DEVICE, "internal: spread term lists of another call");
+    if ((rc = id_tables_sync(ctx, terms ? NS_TERMS : domains ? NS_DOMAINS : groups ? NS_GROUPS : ns))) return rc;
     return upload_pods(ctx, n_pods, pods, (int64_t)n_pods + 1, &h_bases, &upload_bytes, &n_copies);
   }
 
@@ -8768,7 +8896,8 @@ struct ScheduleCall {
     // the knob is read per call: tests set it between contexts of one process
     knob = select_knob(std::getenv("KOORDEVAL_SELECT_PARTS"));
     ctx->last_ds_cuts = 0;
-    batches = plan_batches(c.host_pods.data(), n_pods, ctx->cfg.pod_batch, !sharded && !numa && N > 0, fused, ctx->sg_call, ctx->sd_call);
+    batches = plan_batches(c.host_pods.data(), n_pods, ctx->cfg.pod_batch, !sharded && !numa && N > 0, fused,
+                           terms ? ctx->st_listed.data() : ctx->sg_call, ctx->sd_call);  // (term lists mark a batch as group ids do)
     for (const Batch& b : batches) any_cpu = any_cpu || b.cpu;
     if (any_cpu && !d->has(ST_CPU)) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
     n_batches = (int)batches.size();
@@ -8875,7 +9004,7 @@ struct ScheduleCall {
   // the bookkeeping words, the one copy of everything the call uploads, the call's events, and k_call_begin
   int begin() {
     RC_OK(c.d_sched.reserve((size_t)sl.total));
-    d_bases = reinterpret_cast<int32_t*>(c.d_pods + n_pods) + (ns || groups || domains ? n_pods : 0) + (groups || domains ? n_pods : 0) + (domains ? n_pods : 0);
+    d_bases = reinterpret_cast<int32_t*>(c.d_pods + n_pods) + id_words(ctx, n_pods);
     d_ready = c.d_sched + sl.ready, d_done = c.d_sched + sl.done, d_tready = c.d_sched + sl.tready;
     d_sstart = c.d_sched + sl.sstart, d_rres = c.d_sched + sl.rres, d_tlist = c.d_sched + sl.tlist;
     d_tmx = reinterpret_cast<uint32_t*>(c.d_sched + sl.tmx);
@@ -8995,7 +9124,7 @@ struct ScheduleCall {
     const DeferBufs df{defer.list, defer.fb, numa ? defer.cnt + b : nullptr};  // (the batch's own counter)
     // a grouped batch of a call with spread domain ids: its pods' eligible-domain masks from the counts as the previous
     // batch's Reserves left them (a serial batch: this stream ran them)
-    if (batch_ns(b) == NS_DOMAINS) launch_domain_masks(d, bases[b], bp, a.es);
+    if (batch_ns(b) >= NS_DOMAINS) launch_domain_masks(d, bases[b], bp, a.es);
     if (plain_rec) {  // plain batch: the record-based evaluation
       hipLaunchKernelGGL(pick_eval_plain(ext, batch_ns(b)), grid, dim3(blk), 0, a.es, d->soa, lo, hi, c.d_pods, bbase, bp, k,
                          eb.scores, d->capacity, stamp, dwait, d_err);
@@ -9291,6 +9420,7 @@ struct ScheduleCall {
     cp.copies = n_copies, cp.fills = n_fills, cp.n_pipelined = n_pipelined;
     if (groups) cp.groups.assign(ctx->sg_call, ctx->sg_call + n_pods);
     if (domains) cp.domains.assign(ctx->sd_call, ctx->sd_call + n_pods);
+    if (terms) cp.terms.assign(ctx->st_call, ctx->st_call + n_pods);
     *fin = [cp = std::move(cp)](int32_t* chosen, int32_t* score) { return complete_call(cp, chosen, score); };
     return KE_OK;
   }

@@ -459,4 +459,33 @@ KE_HD inline int32_t key_score(uint32_t key) { return (int32_t)(key >> KEY_IDX_B
 
 constexpr int MAX_BATCH = 64;  // pods per speculative batch (== max candidates per pod)
 
+// A pod's spread terms and members (ke_pod_spread_terms), packed: term t is tw[t] = group (bits 0-15) |
+// kind << 16 | weight << 24 with its param in half t & 1 of tp[t >> 1]; the terms fill the front, an unused slot is all
+// zero (kind 0; its group 0 is the count table's all-zero row, so a reader may fetch a slot's count before it looks at
+// the kind).  mem: the member groups, two 16-bit halves a word, 0 = none.  Words only: a record sits behind int32 ids.
+constexpr int POD_TERMS = 4, POD_MEMBERS = 4;
+struct PodTerms {
+  uint32_t tw[POD_TERMS];
+  uint32_t tp[POD_TERMS / 2];
+  uint32_t mem[POD_MEMBERS / 2];
+};
+static_assert(sizeof(PodTerms) == 32 && alignof(PodTerms) == 4, "eight int32 words behind the call's id words");
+constexpr int ST_ANTI = 1, ST_AFFINITY = 2, ST_PREFER_FEWER = 3, ST_PREFER_MORE = 4;  // == KE_TERM_*
+KE_HD inline int st_group(const PodTerms& r, int t) { return (int)(r.tw[t] & 0xffffu); }
+KE_HD inline int st_kind(const PodTerms& r, int t) { return (int)((r.tw[t] >> 16) & 0xffu); }
+KE_HD inline int st_weight(const PodTerms& r, int t) { return (int)(r.tw[t] >> 24); }
+KE_HD inline uint32_t st_param(const PodTerms& r, int t) { return (r.tp[t >> 1] >> ((t & 1) * 16)) & 0xffffu; }
+KE_HD inline int st_member(const PodTerms& r, int m) { return (int)((r.mem[m >> 1] >> ((m & 1) * 16)) & 0xffffu); }
+KE_HD inline bool st_empty(const PodTerms& r) { return !r.tw[0] && !r.mem[0]; }
+// What term t does with its group's count `c` on a node: a filter term may close the node (*filtered), a score term
+// adds to the bonus a feasible total takes.  The one place with the term arithmetic, host and device.
+KE_HD inline void st_apply(const PodTerms& r, int t, uint32_t c, bool* filtered, int32_t* bonus) {
+  const int kind = st_kind(r, t);
+  const uint32_t param = st_param(r, t), cl = c < param ? c : param;
+  if (kind == ST_ANTI) *filtered = *filtered || c >= param;
+  else if (kind == ST_AFFINITY) *filtered = *filtered || c < param;
+  else if (kind == ST_PREFER_FEWER) *bonus += st_weight(r, t) * (int32_t)(param - cl);
+  else if (kind == ST_PREFER_MORE) *bonus += st_weight(r, t) * (int32_t)cl;
+}
+
 }  // namespace ke
