@@ -647,14 +647,20 @@ int ke_node_set_bits(ke_ctx* ctx, int32_t node, int32_t n_sets, const uint8_t* m
   return KE_OK;
 }
 
-int ke_pod_node_sets(ke_ctx* ctx, int32_t n_pods, const int32_t* set_ids) {
-  if (!ctx || n_pods < 0 || (n_pods > 0 && !set_ids)) return fail(KE_ERR_INVALID, "ke_pod_node_sets arguments");
+// The four per-pod id stagings (ke_pod_node_sets, ke_pod_node_scores, ke_pod_spread_groups, ke_pod_spread_domains): ids
+// in 0..the loaded table's rows, staged for the next call
+static int stage_pod_ids(ke_ctx* ctx, int32_t n_pods, const int32_t* ids, const char* fn, const char* outside,
+                         int32_t Context::*limit, AttachSlot<int32_t> Context::*slot) {
+  if (!ctx || n_pods < 0 || (n_pods > 0 && !ids)) return fail(KE_ERR_INVALID, std::string(fn) + " arguments");
   Context& c = ctx->c;
   for (int32_t p = 0; p < n_pods; p++)
-    if (set_ids[p] < 0 || set_ids[p] > c.ns_n) return fail(KE_ERR_INVALID, "ke_pod_node_sets: set id outside 0..n_sets");
-  c.ns_staged.assign(set_ids, set_ids + n_pods);
-  c.ns_staged_on = true;
+    if (ids[p] < 0 || ids[p] > c.*limit) return fail(KE_ERR_INVALID, std::string(fn) + ": " + outside);
+  (c.*slot).stage(ids, n_pods);
   return KE_OK;
+}
+
+int ke_pod_node_sets(ke_ctx* ctx, int32_t n_pods, const int32_t* set_ids) {
+  return stage_pod_ids(ctx, n_pods, set_ids, "ke_pod_node_sets", "set id outside 0..n_sets", &Context::ns_n, &Context::pod_sets);
 }
 
 // ---- per-pod node score offsets (include/koord_eval.h): the node sets' lifecycle ----
@@ -704,14 +710,8 @@ int ke_node_scores_set(ke_ctx* ctx, int32_t node, int32_t n_tables, const uint16
 }
 
 int ke_pod_node_scores(ke_ctx* ctx, int32_t n_pods, const int32_t* table_ids) {
-  if (!ctx || n_pods < 0 || (n_pods > 0 && !table_ids)) return fail(KE_ERR_INVALID, "ke_pod_node_scores arguments");
-  Context& c = ctx->c;
-  for (int32_t p = 0; p < n_pods; p++)
-    if (table_ids[p] < 0 || table_ids[p] > c.nsc_n)
-      return fail(KE_ERR_INVALID, "ke_pod_node_scores: table id outside 0..n_tables");
-  c.nsc_staged.assign(table_ids, table_ids + n_pods);
-  c.nsc_staged_on = true;
-  return KE_OK;
+  return stage_pod_ids(ctx, n_pods, table_ids, "ke_pod_node_scores", "table id outside 0..n_tables", &Context::nsc_n,
+                       &Context::pod_scores);
 }
 
 // ---- spread groups (include/koord_eval.h): the node sets' lifecycle ----
@@ -765,14 +765,8 @@ int ke_spread_groups_get(ke_ctx* ctx, int32_t group, int32_t n_nodes, uint16_t* 
 }
 
 int ke_pod_spread_groups(ke_ctx* ctx, int32_t n_pods, const int32_t* group_ids) {
-  if (!ctx || n_pods < 0 || (n_pods > 0 && !group_ids)) return fail(KE_ERR_INVALID, "ke_pod_spread_groups arguments");
-  Context& c = ctx->c;
-  for (int32_t p = 0; p < n_pods; p++)
-    if (group_ids[p] < 0 || group_ids[p] > c.sg_n)
-      return fail(KE_ERR_INVALID, "ke_pod_spread_groups: group id outside 0..n_groups");
-  c.sg_staged.assign(group_ids, group_ids + n_pods);
-  c.sg_staged_on = true;
-  return KE_OK;
+  return stage_pod_ids(ctx, n_pods, group_ids, "ke_pod_spread_groups", "group id outside 0..n_groups", &Context::sg_n,
+                       &Context::pod_groups);
 }
 
 // ---- spread domains (include/koord_eval.h): the spread groups' lifecycle ----
@@ -862,14 +856,8 @@ int ke_spread_domains_get(ke_ctx* ctx, int32_t group, uint32_t* counts64) {
 }
 
 int ke_pod_spread_domains(ke_ctx* ctx, int32_t n_pods, const int32_t* group_ids) {
-  if (!ctx || n_pods < 0 || (n_pods > 0 && !group_ids)) return fail(KE_ERR_INVALID, "ke_pod_spread_domains arguments");
-  Context& c = ctx->c;
-  for (int32_t p = 0; p < n_pods; p++)
-    if (group_ids[p] < 0 || group_ids[p] > c.sd_n)
-      return fail(KE_ERR_INVALID, "ke_pod_spread_domains: group id outside 0..n_groups");
-  c.sd_staged.assign(group_ids, group_ids + n_pods);
-  c.sd_staged_on = true;
-  return KE_OK;
+  return stage_pod_ids(ctx, n_pods, group_ids, "ke_pod_spread_domains", "group id outside 0..n_groups", &Context::sd_n,
+                       &Context::pod_domains);
 }
 
 // ---- spread terms (include/koord_eval.h): ke_pod_spread_groups' rules, per-pod lists ----
@@ -914,78 +902,58 @@ int ke_pod_spread_terms(ke_ctx* ctx, int32_t n_pods, const int32_t* term_offsets
       r.mem[m >> 1] |= (uint32_t)group << ((m & 1) * 16);
     }
   }
-  c.st_staged.swap(recs);
-  c.st_staged_on = true;
+  c.pod_terms.stage(recs);
   return KE_OK;
 }
 
 // The ke_pod_node_sets, ke_pod_node_scores, ke_pod_spread_groups and ke_pod_spread_domains ids of this call, all
-// consumed whether it goes on or not; Context::ns_call / nsc_call / sg_call / sd_call = the ids of a kind when any of
-// them is non-zero (the device entry points then run the node-set / score-offset / spread-group / spread-domain kernels).  Such a call is refused here, before any state
-// changes, where those kernels are not built: node-sharded contexts, and for ke_schedule (`sched`) anything but a
-// plain queue (ke_schedule_submit's sense, with device_async_ok's conditions).  The message names the sets when a
-// set id is non-zero, else the scores when a table id is, else the spread groups, else the spread domains, else the
-// spread terms.  ke_pod_spread_terms' lists go the same way: Context::st_call = the call's records when
-// one of them is not empty; staged together with group ids they are KE_ERR_INVALID, and a pod whose score terms could
-// push total + 1 out of the key's 10 bits is KE_ERR_UNSUPPORTED.
-static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool sched) {
+// consumed whether it goes on or not; Context::att names the ids of a kind when any of them is non-zero (the device
+// entry points then run the node-set / score-offset / spread-group / spread-domain kernels).  Such a call is refused
+// here, before any state changes, where those kernels are not built: node-sharded contexts, and for ke_schedule
+// (`sched`) anything but a plain queue (ke_schedule_submit's sense, with device_async_ok's conditions).  The message
+// names the sets when a set id is non-zero, else the scores when a table id is, else the spread groups, else the spread
+// domains, else the spread terms.  ke_pod_spread_terms' lists go the same way: att.terms = the call's
+// records when one of them is not empty; staged together with group ids they are KE_ERR_INVALID, and a pod whose score
+// terms could push total + 1 out of the key's 10 bits is KE_ERR_UNSUPPORTED.  `filter_only` (ke_diagnose): the call
+// is checked as any other and then goes on without its score table ids, which do not filter.
+// The id kinds, in the order of every check and of the message prefix:
+enum { AK_SETS, AK_SCORES, AK_GROUPS, AK_DOMAINS, N_ID_KINDS };
+static const struct {
+  AttachSlot<int32_t> Context::*slot;
+  int32_t Context::*limit;
+  const int32_t* CallAttach::*view;
+  const char *mismatch, *outside, *prefix;
+} ID_KINDS[N_ID_KINDS] = {
+    {&Context::pod_sets, &Context::ns_n, &CallAttach::sets, "the call's n_pods differs from the staged ke_pod_node_sets ids'",
+     "a staged node set id is outside the table loaded since", "node sets: "},
+    {&Context::pod_scores, &Context::nsc_n, &CallAttach::scores, "the call's n_pods differs from the staged ke_pod_node_scores ids'",
+     "a staged node score table id is outside the table loaded since", "node scores: "},
+    {&Context::pod_groups, &Context::sg_n, &CallAttach::groups, "the call's n_pods differs from the staged ke_pod_spread_groups ids'",
+     "a staged spread group id is outside the table loaded since", "spread groups: "},
+    {&Context::pod_domains, &Context::sd_n, &CallAttach::domains, "the call's n_pods differs from the staged ke_pod_spread_domains ids'",
+     "a staged spread domain group id is outside the table loaded since", "spread domains: "},
+};
+static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool sched, bool filter_only = false) {
   Context& c = ctx->c;
-  c.ns_call = nullptr;
-  c.nsc_call = nullptr;
-  c.sg_call = nullptr;
-  c.sd_call = nullptr;
-  c.st_call = nullptr;
-  const bool sets_on = c.ns_staged_on, scores_on = c.nsc_staged_on, groups_on = c.sg_staged_on, domains_on = c.sd_staged_on;
-  const bool terms_on = c.st_staged_on;
-  if (!sets_on && !scores_on && !groups_on && !domains_on && !terms_on) return KE_OK;
-  c.ns_staged_on = c.nsc_staged_on = c.sg_staged_on = c.sd_staged_on = c.st_staged_on = false;
-  c.ns_call_ids.clear();
-  c.nsc_call_ids.clear();
-  c.sg_call_ids.clear();
-  c.sd_call_ids.clear();
-  if (domains_on) c.sd_call_ids.swap(c.sd_staged);
-  c.sd_staged.clear();
-  c.st_call_recs.clear();
-  c.st_listed.clear();
-  if (terms_on) c.st_call_recs.swap(c.st_staged);
-  c.st_staged.clear();
-  if (sets_on) c.ns_call_ids.swap(c.ns_staged);
-  if (scores_on) c.nsc_call_ids.swap(c.nsc_staged);
-  if (groups_on) c.sg_call_ids.swap(c.sg_staged);
-  c.ns_staged.clear();
-  c.nsc_staged.clear();
-  c.sg_staged.clear();
-  if (sets_on && (int32_t)c.ns_call_ids.size() != n_pods)
-    return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_node_sets ids'");
-  if (scores_on && (int32_t)c.nsc_call_ids.size() != n_pods)
-    return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_node_scores ids'");
-  if (groups_on && (int32_t)c.sg_call_ids.size() != n_pods)
-    return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_spread_groups ids'");
-  if (domains_on && (int32_t)c.sd_call_ids.size() != n_pods)
-    return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_spread_domains ids'");
-  if (terms_on && (int32_t)c.st_call_recs.size() != n_pods)
+  c.att.reset();
+  if (!(c.pod_sets.on || c.pod_scores.on || c.pod_groups.on || c.pod_domains.on || c.pod_terms.on)) return KE_OK;
+  bool on[N_ID_KINDS], any[N_ID_KINDS] = {false, false, false, false};
+  for (int k = 0; k < N_ID_KINDS; k++) on[k] = (c.*ID_KINDS[k].slot).take();
+  const bool terms_on = c.pod_terms.take();
+  for (int k = 0; k < N_ID_KINDS; k++)
+    if (on[k] && (int32_t)(c.*ID_KINDS[k].slot).call.size() != n_pods) return fail(KE_ERR_INVALID, ID_KINDS[k].mismatch);
+  if (terms_on && (int32_t)c.pod_terms.call.size() != n_pods)
     return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_spread_terms lists'");
-  if (terms_on && groups_on)
+  if (terms_on && on[AK_GROUPS])
     return fail(KE_ERR_INVALID, "a call with both ke_pod_spread_groups ids and ke_pod_spread_terms lists staged");
-  bool any = false, any_sc = false, any_sg = false, any_sd = false, any_st = false;
-  for (int32_t id : c.ns_call_ids) {
-    if (id < 0 || id > c.ns_n) return fail(KE_ERR_INVALID, "a staged node set id is outside the table loaded since");
-    any = any || id != 0;
-  }
-  for (int32_t id : c.nsc_call_ids) {
-    if (id < 0 || id > c.nsc_n) return fail(KE_ERR_INVALID, "a staged node score table id is outside the table loaded since");
-    any_sc = any_sc || id != 0;
-  }
-  for (int32_t id : c.sg_call_ids) {
-    if (id < 0 || id > c.sg_n) return fail(KE_ERR_INVALID, "a staged spread group id is outside the table loaded since");
-    any_sg = any_sg || id != 0;
-  }
-  for (int32_t id : c.sd_call_ids) {
-    if (id < 0 || id > c.sd_n) return fail(KE_ERR_INVALID, "a staged spread domain group id is outside the table loaded since");
-    any_sd = any_sd || id != 0;
-  }
+  for (int k = 0; k < N_ID_KINDS; k++)
+    for (int32_t id : (c.*ID_KINDS[k].slot).call) {
+      if (id < 0 || id > c.*ID_KINDS[k].limit) return fail(KE_ERR_INVALID, ID_KINDS[k].outside);
+      any[k] = any[k] || id != 0;
+    }
+  bool any_st = false;
   int32_t st_sum = 0;  // the largest bonus a pod's score terms can add
-  for (const PodTerms& r : c.st_call_recs) {
+  for (const PodTerms& r : c.pod_terms.call) {
     int32_t sum = 0;
     for (int t = 0; t < POD_TERMS; t++) {
       if (st_group(r, t) > c.sg_n) return fail(KE_ERR_INVALID, "a staged spread term's group is outside the table loaded since");
@@ -994,16 +962,17 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
     for (int m = 0; m < POD_MEMBERS; m++)
       if (st_member(r, m) > c.sg_n) return fail(KE_ERR_INVALID, "a staged spread member is outside the table loaded since");
     st_sum = std::max(st_sum, sum);
-    c.st_listed.push_back(st_empty(r) ? 0 : 1);
+    c.att.listed.push_back(st_empty(r) ? 0 : 1);
     any_st = any_st || !st_empty(r);
   }
-  if (!any && !any_sc && !any_sg && !any_sd && !any_st) return KE_OK;
+  const bool any_sc = any[AK_SCORES];
+  const char* prefix = any_st ? "spread terms: " : nullptr;  // (the first kind present names a refusal)
+  for (int k = N_ID_KINDS - 1; k >= 0; k--)
+    if (any[k]) prefix = ID_KINDS[k].prefix;
+  if (!prefix) return KE_OK;
   int rc = check_pods(pods, n_pods, &c, sched);
   if (rc) return rc;
-  auto no = [any, any_sc, any_sg, any_sd](const char* what) {
-    return fail(KE_ERR_UNSUPPORTED,
-                std::string(any ? "node sets: " : any_sc ? "node scores: " : any_sg ? "spread groups: " : any_sd ? "spread domains: " : "spread terms: ") + what);
-  };
+  auto no = [prefix](const char* what) { return fail(KE_ERR_UNSUPPORTED, std::string(prefix) + what); };
   if (c.cfg.global_node_offset != 0 || (c.dev && device_sharded(&c))) return no("a node-sharded context");
   if (sched) {
     if (!c.match_off.empty()) return no("a call with staged ke_pod_reservations lists");
@@ -1029,12 +998,11 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
                                           std::to_string(cap) + " = 1022 - 100 * (sum of the Score plugin weights)" +
                                           (any_sc ? " - the largest score table entry" : "") +
                                           ": total + 1 must fit the key's 10 bits");
-    c.st_call = c.st_call_recs.data();
+    c.att.terms = c.pod_terms.call.data();
   }
-  if (any) c.ns_call = c.ns_call_ids.data();
-  if (any_sc) c.nsc_call = c.nsc_call_ids.data();
-  if (any_sg) c.sg_call = c.sg_call_ids.data();
-  if (any_sd) c.sd_call = c.sd_call_ids.data();
+  for (int k = 0; k < N_ID_KINDS; k++)
+    if (any[k] && !(filter_only && k == AK_SCORES)) c.att.*ID_KINDS[k].view = (c.*ID_KINDS[k].slot).call.data();
+  c.att.n_pods = n_pods;
   return KE_OK;
 }
 
@@ -1345,8 +1313,7 @@ int ke_diagnose(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns,
   if (ctx) async_drain(ctx);
   if (!ctx) return fail(KE_ERR_INVALID, "null context");
   flush_mirror(ctx->c);
-  int rc = take_node_sets(ctx, n_pods, pods, false);
-  ctx->c.nsc_call = nullptr;  // score offsets do not filter
+  int rc = take_node_sets(ctx, n_pods, pods, false, /*filter_only=*/true);  // (score offsets do not filter)
   if (rc) return rc;
   if (n_pods > 0 && !out) return fail(KE_ERR_INVALID, "diagnose: null out");
   if ((feasible || unschedulable || unresolvable) && words_per_pod < (ctx->c.n_nodes + 63) / 64)

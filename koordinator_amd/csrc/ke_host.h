@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/koord_eval.h"
+#include "ke_attach.h"
 #include "ke_types.h"
 
 namespace ke {
@@ -224,50 +225,34 @@ struct Context {
   std::vector<int32_t> match_off, match_ids;
   // Per-pod node eligibility sets (ke_node_sets_load): the host mirror of the table (ns_n rows of
   // ns_wps words, set s = row s - 1; bit i & 63 of word i >> 6 = node i), what of the device copy is stale (all of
-  // it, or the word columns ke_node_set_bits patched: the next call with a non-zero id uploads them), the
-  // ke_pod_node_sets staging for the next call (ns_staged_on: staged, also when every id is 0), and the ids of the
-  // call in progress (nullptr: no non-zero id, the call runs the set-free kernels)
+  // it, or the word columns ke_node_set_bits patched: the next call with a non-zero id uploads them)
   int32_t ns_n = 0, ns_wps = 0;
   std::vector<uint64_t> ns_bits;
   bool ns_dirty = false;
   std::vector<int32_t> ns_dirty_words;
-  std::vector<int32_t> ns_staged;
-  bool ns_staged_on = false;
-  std::vector<int32_t> ns_call_ids;
-  const int32_t* ns_call = nullptr;
   // Per-pod node score offsets (ke_node_scores_load), with the node sets' lifecycle: the host mirror
   // of the table (nsc_n rows of nsc_nodes entries, table t = row t - 1), what of the device copy is stale (all of
-  // it, or the node columns ke_node_scores_set patched), the ke_pod_node_scores staging for the next call, and the
-  // table ids of the call in progress (nullptr: no non-zero id, the call runs the kernels it ran without them)
+  // it, or the node columns ke_node_scores_set patched)
   int32_t nsc_n = 0, nsc_nodes = 0;
   std::vector<uint16_t> nsc_vals;
   bool nsc_dirty = false;
   std::vector<int32_t> nsc_dirty_nodes;
-  std::vector<int32_t> nsc_staged;
-  bool nsc_staged_on = false;
-  std::vector<int32_t> nsc_call_ids;
-  const int32_t* nsc_call = nullptr;
   // Spread groups (ke_spread_groups_load), with the node sets' lifecycle: the host copy of the table
   // (sg_n rows of sg_stride counts, group g = row g - 1; sg_stride covers the loaded n_nodes and the node capacity, so
   // every Reserve has an entry) and the caps; a call's completion applies its placements' increments here -- the
   // device does the same arithmetic, no read-back.  What of the device copy is stale: all of it, or the
-  // (row, node) entries ke_spread_group_add patched.  The ke_pod_spread_groups staging for the next call and the
-  // group ids of the call in progress (nullptr: no non-zero id, the call runs the kernels it ran without them).
+  // (row, node) entries ke_spread_group_add patched.
   int32_t sg_n = 0, sg_nodes = 0;
   int64_t sg_stride = 0;
   std::vector<uint16_t> sg_cnt, sg_cap;
   bool sg_dirty = false;
   std::vector<std::pair<int32_t, int32_t>> sg_dirty_cells;
-  std::vector<int32_t> sg_staged;
-  bool sg_staged_on = false;
-  std::vector<int32_t> sg_call_ids;
-  const int32_t* sg_call = nullptr;
   // Spread domains (ke_spread_domains_load), with the same lifecycle: the maps as loaded (sd_maps rows
   // of sd_stride uint16 domain ids, map m = row m - 1, KE_DOMAIN_NONE at and beyond the loaded n_nodes; sd_stride covers
   // the node capacity), the groups' parameters and their counts (sd_n rows of 64, group g = row g - 1).  A call's
   // completion adds its placements to the counts as the device's Reserves did.  What of the device copy is stale: all
   // of it, or the (group, domain) counts ke_spread_domain_add and the (map, node) entries ke_spread_domain_node_set
-  // patched.  The ke_pod_spread_domains staging and the ids of the call in progress, as for the spread groups.
+  // patched.
   int32_t sd_maps = 0, sd_n = 0;
   int64_t sd_stride = 0;
   std::vector<uint16_t> sd_map;
@@ -276,19 +261,13 @@ struct Context {
   std::vector<uint32_t> sd_cnt;
   bool sd_dirty = false;
   std::vector<std::pair<int32_t, int32_t>> sd_dirty_cells, sd_dirty_nodes;
-  std::vector<int32_t> sd_staged;
-  bool sd_staged_on = false;
-  std::vector<int32_t> sd_call_ids;
-  const int32_t* sd_call = nullptr;
-  // Spread terms (ke_pod_spread_terms): per-pod term and member lists over the spread groups' counts,
-  // one packed record a pod.  The staging for the next call, and the records of the call in progress (nullptr: every
-  // list empty, the call runs the kernels it ran without them) with st_listed[p] != 0 where pod p's record is not
-  // empty (the plan's `grouped` mark).  A call with term lists carries no spread group ids (sg_call == nullptr).
-  std::vector<PodTerms> st_staged;
-  bool st_staged_on = false;
-  std::vector<PodTerms> st_call_recs;
-  std::vector<int32_t> st_listed;
-  const PodTerms* st_call = nullptr;
+  // The per-pod attachments of a call (ke_attach.h; DESIGN.md §3, the staging block): per kind what its ke_pod_* entry
+  // point staged for the next call and what the call in progress took -- node set ids, score table ids, spread group
+  // ids, spread domain group ids, spread term records (§4t: one packed record a pod, over the spread groups' counts)
+  // -- and `att`, the kinds the call in progress carries.
+  AttachSlot<int32_t> pod_sets, pod_scores, pod_groups, pod_domains;
+  AttachSlot<PodTerms> pod_terms;
+  CallAttach att;
   // the KE_RSV_MATCHED pod of the current segment: its nodes with matched reservations, their
   // (node, ScoreReservation of the nominated one, smallest order) for the device pick, the nominated index
   std::vector<int32_t> rsv_nodes;

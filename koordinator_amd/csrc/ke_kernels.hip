@@ -96,6 +96,8 @@ struct SoA {
   // a KE_RSV_MATCHED segment's allocate-from-reservation decisions (RsvOvr) for its NF_RSV_CS nodes
   const RsvOvr* rovr;
   int32_t n_rovr;
+  // The call's per-pod attachments: ns_ids, sg_ids, sd_ids and st_rec point into the staging block behind its DevPod
+  // records (its sections and which of them a call has), nullptr without the section.
   // per-pod node eligibility sets: ns_wps words a row covering the node capacity, row 0 all ones
   // (set id 0 = every node), row s = set s; the current call's set id per pod, parallel to its DevPod array.
   // Read only by the NS instantiations, which the host launches for a call that carries a non-zero id.
@@ -131,11 +133,7 @@ struct SoA {
   // instantiations; the one-wave replay of a grouped batch increments the count of every (member, node) it Reserves.
   const PodTerms* st_rec;
 };
-// NS, the template mode of every kernel that makes a score or key: 0 = the call has no per-pod ids, NS_SETS = its
-// ns_ids words are node set ids, NS_SCORES = they are (score table id << 16) | node set id, NS_GROUPS = NS_SCORES and
-// the pods' spread groups (sg_ids) besides, NS_DOMAINS = NS_GROUPS and the pods' spread domain groups (sd_ids),
-// NS_TERMS = NS_DOMAINS and the pods' spread term records (st_rec)
-constexpr int NS_SETS = 1, NS_SCORES = 2, NS_GROUPS = 3, NS_DOMAINS = 4, NS_TERMS = 5;
+// (NS, the template mode of every kernel that makes a score or key: ke_attach.h)
 // node `node` is in the set of id word `idw` (NS instantiations; every node < 64 * ns_wps is in bounds, the ids
 // checked by the host)
 template <int NS>
@@ -3381,10 +3379,9 @@ __device__ __forceinline__ EvalOut classify_pair(const SoA& s, const NodeRegs& n
 
 // parity mode: the full status / score matrices of `out`, every pair classified by classify_pair (an empty slot by
 // eval_pair's own NF_VALID test, behind the node-set gate).
-// IDS: the call carries per-pod ids (SoA::ns_ids): the low half of a word is the pod's node set (the high half, a
-// score table id, is k_parity_finalize's).  GRP: it carries spread group ids too (NS_GROUPS); DOM: and spread domain
-// group ids (NS_DOMAINS); TRM: and spread term records (NS_TERMS).
-template <bool NUMA, bool CPU, bool IDS = false, bool GRP = false, bool DOM = false, bool TRM = false>
+// NS: 0, NS_SCORES (the call carries per-pod ids, SoA::ns_ids: the low half of a word is the pod's node set; the high
+// half, a score table id, is k_parity_finalize's), NS_GROUPS, NS_DOMAINS or NS_TERMS.
+template <bool NUMA, bool CPU, int NS = 0>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, const DevPod* __restrict__ pods, int n_pods,
                                                             int pods_per_block, KArgs k, ParityOut out,
                                                             uint64_t* defer_list, uint32_t* defer_cnt) {
@@ -3405,7 +3402,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_parity(SoA s, const DevPod*
     uint32_t m = 0;
     bool deferred = false;
     if (live) {
-      const EvalOut o = classify_pair<NUMA, CPU, TRM ? NS_TERMS : DOM ? NS_DOMAINS : GRP ? NS_GROUPS : IDS ? NS_SCORES : 0>(s, n, expired, pods, p, k, i, nv, &deferred);
+      const EvalOut o = classify_pair<NUMA, CPU, NS>(s, n, expired, pods, p, k, i, nv, &deferred);
       out.store(p, i, o);
       m = o.total >= 0 ? (uint32_t)o.ds + 1 : 0u;
     }
@@ -8183,11 +8180,6 @@ static int spread_domains_sync(Context* ctx) {
   d->soa.sd_stride = (int32_t)S;
   return KE_OK;
 }
-// the mode of a call's kernels from its ids: spread domains (which read the other tables' row 0 at least), groups
-// (likewise), score tables, node sets, none
-static int call_ns(const Context* ctx) {
-  return ctx->st_call ? NS_TERMS : ctx->sd_call ? NS_DOMAINS : ctx->sg_call ? NS_GROUPS : ctx->nsc_call ? NS_SCORES : ctx->ns_call ? NS_SETS : 0;
-}
 // the tables a call of mode `ns` reads, brought up to date
 static int id_tables_sync(Context* ctx, int ns) {
   if (ns) RC_OK(node_sets_sync(ctx));
@@ -8201,34 +8193,16 @@ static void launch_domain_masks(DeviceState* d, int base, int n, hipStream_t st)
   if (n > 0) hipLaunchKernelGGL(k_domain_masks, dim3((unsigned)n), dim3(64), 0, st, d->soa, base, n);
 }
 
-// the int32 words of a call's per-pod ids and records behind its DevPod array (upload_pods lays them out): the packed
-// set / table id words, the spread group ids, the spread domain ids and the spread term records -- a later kind brings
-// the earlier ones' words with it
-static int64_t id_words(const Context* ctx, int64_t n_pods) {
-  const bool st = ctx->st_call, sd = st || ctx->sd_call, sg = sd || ctx->sg_call, ns = sg || ctx->ns_call || ctx->nsc_call;
-  return n_pods * ((ns ? 1 : 0) + (sg ? 1 : 0) + (sd ? 1 : 0) + (st ? 8 : 0));
-}
-
-// The call's upload block: the DevPod records, the node set ids when present (int32 each) and room for
-// tail_words more int32 words, laid out alike in the page-locked host_pods and in d_pods, so one copy carries
+// The call's upload block: the DevPod records, the staging block `lay` of the call's attachments and
+// room for tail_words more int32 words, laid out alike in the page-locked host_pods and in d_pods, so one copy carries
 // it.  Without `tail` the block is copied here; with it the caller fills *tail (ke_schedule's batch bases) and
 // copies *block_bytes itself.  *copies counts the copies enqueued (on the Reserve stream).
-static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t tail_words = 0, int32_t** tail = nullptr, int64_t* block_bytes = nullptr,
-                       int* copies = nullptr) {
+static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, const AttachLayout& lay, int64_t tail_words = 0,
+                       int32_t** tail = nullptr, int64_t* block_bytes = nullptr, int* copies = nullptr) {
   DeviceState* d = ctx->dev;
   PinnedVec<DevPod>& dp = d->call.host_pods;
-  // the call's node set ids and score table ids (a non-zero one among either): one word per pod behind the
-  // records, the set id alone or -- in a call with table ids -- (table id << 16) | set id
-  // -- and in a call with spread group ids those words (zero without set / table ids) and the group ids behind them
-  // -- and in a call with spread domain ids both of those (zero where the call has none) and the domain ids behind them
-  const int32_t* ns = ctx->ns_call;
-  const int32_t* sc = ctx->nsc_call;
-  const int32_t* sg = ctx->sg_call;
-  const int32_t* sd = ctx->sd_call;
-  // -- and in a call with spread term lists all three (zero where the call has none; never group ids) and the pods'
-  // eight-word records behind them
-  const PodTerms* tr = ctx->st_call;
-  const int64_t ns_words = id_words(ctx, n_pods);
+  const CallAttach& a = ctx->att;
+  const int64_t ns_words = lay.total;
   if (!dp.resize((size_t)n_pods, sizeof(int32_t) * (size_t)(ns_words + tail_words)))
     return fail(KE_ERR_DEVICE, "hipHostMalloc of the pod staging buffer");
   std::vector<DevPodHint>& ph = d->host_ph;  // the hinted pods' records; DevPod::ring_bw = slot
@@ -8251,32 +8225,31 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t
   // (whole records: the id and tail words round up)
   RC_OK(d->call.d_pods.reserve((size_t)std::max<int64_t>((bytes + (int64_t)sizeof(DevPod) - 1) / (int64_t)sizeof(DevPod), 1)));
   int32_t* const h_words = reinterpret_cast<int32_t*>(dp.data() + n_pods);
-  d->soa.ns_ids = nullptr;
-  d->soa.sg_ids = nullptr;
-  d->soa.sd_ids = nullptr;
+  int32_t* const d_words = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods);
+  // one id section: the host fill (the call's ids, zero where it has none) and the device pointer, from one offset
+  auto section = [&](int64_t off, const int32_t* ids) -> int32_t* {
+    if (off < 0) return nullptr;
+    if (ids) std::copy(ids, ids + n_pods, h_words + off);
+    else std::fill(h_words + off, h_words + off + n_pods, 0);
+    return d_words + off;
+  };
+  d->soa.sg_ids = section(lay.groups, a.groups);
+  d->soa.sd_ids = section(lay.domains, a.domains);
   d->soa.sd_mask = nullptr;
-  d->soa.st_rec = nullptr;
-  if (sg || sd || tr) {
-    if (sg) std::copy(sg, sg + n_pods, h_words + n_pods);
-    else std::fill(h_words + n_pods, h_words + 2 * (int64_t)n_pods, 0);
-    d->soa.sg_ids = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods) + n_pods;
-  }
-  if (tr) {
-    static_assert(sizeof(PodTerms) == 8 * sizeof(int32_t), "id_words");
-    std::memcpy(h_words + 3 * (int64_t)n_pods, tr, sizeof(PodTerms) * (size_t)n_pods);
-    d->soa.st_rec = reinterpret_cast<const PodTerms*>(reinterpret_cast<int32_t*>(d->call.d_pods + n_pods) + 3 * (int64_t)n_pods);
-  }
-  if (sd || tr) {
-    if (sd) std::copy(sd, sd + n_pods, h_words + 2 * (int64_t)n_pods);
-    else std::fill(h_words + 2 * (int64_t)n_pods, h_words + 3 * (int64_t)n_pods, 0);
-    d->soa.sd_ids = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods) + 2 * (int64_t)n_pods;
+  if (lay.domains >= 0) {
     RC_OK(d->call.d_sd_mask.reserve((size_t)std::max<int32_t>(n_pods, 1)));
     d->soa.sd_mask = d->call.d_sd_mask;
   }
-  if (ns || sc || sg || sd || tr) {
+  d->soa.st_rec = nullptr;
+  if (lay.terms >= 0) {
+    std::memcpy(h_words + lay.terms, a.terms, sizeof(PodTerms) * (size_t)n_pods);
+    d->soa.st_rec = reinterpret_cast<const PodTerms*>(d_words + lay.terms);
+  }
+  d->soa.ns_ids = nullptr;
+  if (lay.ids >= 0) {
     static_assert(KE_MAX_NODE_SETS < (1 << 16) && KE_MAX_NODE_SCORE_TABLES < (1 << 15), "the packed id word");
-    for (int32_t p = 0; p < n_pods; p++) h_words[p] = (ns ? ns[p] : 0) | (sc ? sc[p] << 16 : 0);
-    d->soa.ns_ids = reinterpret_cast<int32_t*>(d->call.d_pods + n_pods);
+    for (int32_t p = 0; p < n_pods; p++) h_words[lay.ids + p] = (a.sets ? a.sets[p] : 0) | (a.scores ? a.scores[p] << 16 : 0);
+    d->soa.ns_ids = d_words + lay.ids;
   }
   if (tail) *tail = h_words + ns_words;
   if (block_bytes) *block_bytes = bytes;
@@ -8329,17 +8302,16 @@ static auto with_nsg_ext(int ns, bool ext, F&& f) {
   return with_ns_ext(ns, ext, f);
 }
 
-// NUMA x CPU x "the call carries ids" (node sets or score tables: the kernel reads a word's set half either way)
+// NUMA x CPU x NS
 using EvalParityFn = decltype(&k_eval_parity<false, false>);
 static EvalParityFn pick_eval_parity(bool numa, bool cpu, int ns) {
-  return with_bool(ns != 0, [&](auto IDS) {
-    return with_bool(numa, [&](auto NUMA) {
-      return with_bool(cpu, [&](auto CPU) -> EvalParityFn {
-        if (ns == NS_TERMS) return k_eval_parity<KV(NUMA), KV(CPU), true, true, true, true>;
-        if (ns == NS_DOMAINS) return k_eval_parity<KV(NUMA), KV(CPU), true, true, true>;
-        if (ns == NS_GROUPS) return k_eval_parity<KV(NUMA), KV(CPU), true, true>;
-        return k_eval_parity<KV(NUMA), KV(CPU), KV(IDS)>;
-      });
+  return with_bool(numa, [&](auto NUMA) {
+    return with_bool(cpu, [&](auto CPU) -> EvalParityFn {
+      if (ns == NS_TERMS) return k_eval_parity<KV(NUMA), KV(CPU), NS_TERMS>;
+      if (ns == NS_DOMAINS) return k_eval_parity<KV(NUMA), KV(CPU), NS_DOMAINS>;
+      if (ns == NS_GROUPS) return k_eval_parity<KV(NUMA), KV(CPU), NS_GROUPS>;
+      if (ns != 0) return k_eval_parity<KV(NUMA), KV(CPU), NS_SCORES>;  // (set ids alone too: it reads a word's set half)
+      return k_eval_parity<KV(NUMA), KV(CPU)>;
     });
   });
 }
@@ -8410,18 +8382,16 @@ template <class Out>
 static auto pick_numa_finish(bool cpu) {
   return cpu ? k_numa_finish<Out, true> : k_numa_finish<Out, false>;
 }
-// ke_diagnose: NUMA x CPU x node sets (score table ids are not part of a diagnosis)
+// ke_diagnose: NUMA x CPU x NS (CallAttach::ns_filter: score table ids are not part of a diagnosis)
 using DiagEvalFn = decltype(&k_diag_eval<false, false>);
 static DiagEvalFn pick_diag_eval(bool numa, bool cpu, int ns) {
-  if (ns == NS_SCORES) return nullptr;
-  return with_bool(ns != 0, [&](auto SETS) {
-    return with_bool(numa, [&](auto NUMA) {
-      return with_bool(cpu, [&](auto CPU) -> DiagEvalFn {
-        if (ns == NS_TERMS) return k_diag_eval<KV(NUMA), KV(CPU), NS_TERMS>;
-        if (ns == NS_DOMAINS) return k_diag_eval<KV(NUMA), KV(CPU), NS_DOMAINS>;
-        if (ns == NS_GROUPS) return k_diag_eval<KV(NUMA), KV(CPU), NS_GROUPS>;
-        return k_diag_eval<KV(NUMA), KV(CPU), KV(SETS) ? NS_SETS : 0>;
-      });
+  return with_bool(numa, [&](auto NUMA) {
+    return with_bool(cpu, [&](auto CPU) -> DiagEvalFn {
+      if (ns == NS_TERMS) return k_diag_eval<KV(NUMA), KV(CPU), NS_TERMS>;
+      if (ns == NS_DOMAINS) return k_diag_eval<KV(NUMA), KV(CPU), NS_DOMAINS>;
+      if (ns == NS_GROUPS) return k_diag_eval<KV(NUMA), KV(CPU), NS_GROUPS>;
+      if (ns == NS_SETS) return k_diag_eval<KV(NUMA), KV(CPU), NS_SETS>;
+      return ns == 0 ? k_diag_eval<KV(NUMA), KV(CPU)> : nullptr;
     });
   });
 }
@@ -8474,7 +8444,7 @@ static int pair_pass_begin(Context* ctx, int32_t n_pods, const ke_pod* pods, int
   int rc = device_refresh(ctx, now);
   if (rc || n_pods == 0) return rc;
   if ((rc = id_tables_sync(ctx, ns))) return rc;
-  if ((rc = upload_pods(ctx, n_pods, pods))) return rc;
+  if ((rc = upload_pods(ctx, n_pods, pods, AttachLayout(ctx->att, n_pods)))) return rc;
   if (ns >= NS_DOMAINS) launch_domain_masks(d, 0, n_pods, d->stream);  // (ke_eval / ke_diagnose: one wave per pod of the call)
   HIP_OK(hipMemsetAsync(d->soa.kerr, 0, sizeof(int32_t), d->stream));
   pp->k = make_kargs(ctx, now);
@@ -8503,8 +8473,7 @@ static int pair_pass_end(Context* ctx, const PairPass& pp) {
 int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, uint8_t* status, uint8_t* reason,
                 int16_t* la, int16_t* numa, int16_t* ds, int16_t* total, int32_t* best) {
   DeviceState* d = ctx->dev;
-  // pods with node sets (NS_SETS) or score tables (NS_SCORES, which reads the set table too: id 0 = its row 0)
-  const int ns = call_ns(ctx);  // (NS_GROUPS: spread group ids, with or without the others)
+  const int ns = ctx->att.ns();
   PairPass pp;
   int rc = pair_pass_begin(ctx, n_pods, pods, now, ns, &pp);
   if (rc || n_pods == 0) return rc;
@@ -8556,8 +8525,7 @@ int device_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, u
 int device_diagnose(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, ke_pod_diagnosis* out,
                     int32_t words_per_pod, uint64_t* const* bits) {
   DeviceState* d = ctx->dev;
-  // (score table ids do not filter: ke_diagnose drops them; spread groups do)
-  const int ns = ctx->st_call ? NS_TERMS : ctx->sd_call ? NS_DOMAINS : ctx->sg_call ? NS_GROUPS : ctx->ns_call ? NS_SETS : 0;
+  const int ns = ctx->att.ns_filter();  // (score table ids do not filter: ke_diagnose's take drops them)
   PairPass pp;
   int rc = pair_pass_begin(ctx, n_pods, pods, now, ns, &pp);
   if (rc || n_pods == 0) return rc;
@@ -8679,9 +8647,7 @@ struct Completion {
   bool behind;  // (ke_schedule_submit: enqueued behind a call in flight)
   int64_t copies, fills;
   int n_pipelined;
-  std::vector<int32_t> groups;  // the call's spread group ids (empty: none): the host copy takes its placements' increments
-  std::vector<int32_t> domains;  // ... and its spread domain group ids
-  std::vector<PodTerms> terms;   // ... and its spread term records: every member of a placement
+  PlacedAttach placed;  // the call's attachments whose Reserves the host tables follow (apply_placements)
 };
 
 static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
@@ -8731,31 +8697,7 @@ static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
     return fail(KE_ERR_DEVICE, (kerr & KERR_LDS_WAIT) ? "internal: a replay LDS wait expired (placements invalid)"
                                                       : "internal: a hinted pod reached a kernel without the hint path");
   }
-  // spread groups: the increments the device's Reserves made, on the host copy (placements of an unsharded context:
-  // chosen is the node index)
-  for (size_t p = 0; p < c.groups.size(); p++) {
-    const int32_t g = c.groups[p], node = chosen[p];
-    if (g > 0 && g <= ctx->sg_n && node >= 0 && (int64_t)node < ctx->sg_stride)
-      ctx->sg_cnt[(size_t)((int64_t)(g - 1) * ctx->sg_stride + node)]++;
-  }
-  // spread terms: every member of a placement, saturating as the device's Reserve does
-  for (size_t p = 0; p < c.terms.size(); p++) {
-    const int32_t node = chosen[p];
-    if (node < 0 || (int64_t)node >= ctx->sg_stride) continue;
-    for (int m = 0; m < POD_MEMBERS; m++) {
-      const int g = st_member(c.terms[p], m);
-      if (g < 1 || g > ctx->sg_n) continue;
-      uint16_t& v = ctx->sg_cnt[(size_t)((int64_t)(g - 1) * ctx->sg_stride + node)];
-      if (v < 65535) v++;
-    }
-  }
-  // spread domains: likewise, on the count of the placement's domain in the group's map
-  for (size_t p = 0; p < c.domains.size(); p++) {
-    const int32_t g = c.domains[p], node = chosen[p];
-    if (g < 1 || g > ctx->sd_n || node < 0 || (int64_t)node >= ctx->sd_stride) continue;
-    const uint16_t dom = ctx->sd_map[(size_t)((int64_t)(ctx->sd_gmap[(size_t)g - 1] - 1) * ctx->sd_stride + node)];
-    if (dom < KE_MAX_SPREAD_DOMAINS) ctx->sd_cnt[(size_t)(g - 1) * KE_MAX_SPREAD_DOMAINS + dom]++;
-  }
+  apply_placements(*ctx, c.placed, chosen);
   float ms = 0;
   HIP_OK(hipEventElapsedTime(&ms, c.e0, c.e1));
   std::vector<float> samples;  // (eval, select) per sampled batch
@@ -8814,15 +8756,11 @@ struct ScheduleCall {
   const bool quota;    // ElasticQuota admission + Reserve in the Reserve kernels
   const bool sharded;
   const bool matched;  // one matched pod (ke_schedule's segment of its own, or the fused one): the Reservation plugin
-  // a call with node set ids (a plain queue, ke_capi.cpp take_node_sets): the NS instantiations of every kernel that
-  // turns a (pod, node) pair into a score or key (NS_SETS), or with score table ids (NS_SCORES: these read the set
-  // table too, id 0 = its all-ones row 0).  A call with spread group ids keeps that mode for its
-  // batches without a grouped pod; a grouped batch runs the NS_GROUPS instantiations (batch_ns), serially.
-  // A call with spread domain ids likewise: its batches holding a pod with such an id are grouped and
-  // run the NS_DOMAINS instantiations, the others what they ran before.
-  const int ns;
-  // A call with spread term lists likewise: NS_TERMS for the batches holding a pod with a list.
-  const bool groups, domains, terms;
+  // the call's attachments (a plain queue, ke_capi.cpp take_node_sets) and their staging block: a batch without a
+  // grouped pod runs the NS_SETS / NS_SCORES instantiations of every kernel that turns a (pod, node) pair into a score
+  // or key, a grouped batch the NS_GROUPS / NS_DOMAINS / NS_TERMS ones, serially (batch_ns)
+  const CallAttach& att;
+  const AttachLayout lay;
   // the plan
   bool fixup = false, two_es = false, ahead = false;  // the schedule of the call's pipelined runs (plan())
   std::vector<Batch> batches;
@@ -8858,10 +8796,9 @@ struct ScheduleCall {
   ScheduleCall(Context* ctx_, int32_t n, const ke_pod* p, bool ws)
       : ctx(ctx_), d(ctx_->dev), c(d->call), n_pods(n), pods(p), want_score(ws), N(ctx_->n_nodes), fused(ctx_->rsv_fused),
         numa(d->has(ST_NUMA)), quota(!ctx_->quotas.empty()), sharded(d->world > 1 || d->comm || d->host_fn),
-        matched(!ctx_->rsv_pairs.empty() || ctx_->rsv_affinity),
-        ns(ctx_->nsc_call ? NS_SCORES : ctx_->ns_call ? NS_SETS : 0), groups(ctx_->sg_call != nullptr),
-        domains(ctx_->sd_call != nullptr), terms(ctx_->st_call != nullptr) {}
-  int batch_ns(int b) const { return !batches[(size_t)b].grouped ? ns : terms ? NS_TERMS : domains ? NS_DOMAINS : NS_GROUPS; }
+        matched(!ctx_->rsv_pairs.empty() || ctx_->rsv_affinity), att(ctx_->att), lay(ctx_->att, n) {}
+  int batch_ns(int b) const { return att.batch_ns(batches[(size_t)b].grouped); }
+  int run_ns() const { return att.batch_ns(false); }  // (a pipelined run holds no grouped batch)
 
   hipError_t copy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
     n_copies++;
@@ -8876,19 +8813,9 @@ struct ScheduleCall {
   // bases (at most one batch per pod, and the end) -- copied once the bases are known (begin())
   int stage() {
     int rc;
-    if (ns) {
-      if ((ctx->ns_call && (int64_t)ctx->ns_call_ids.size() != n_pods) ||
-          (ctx->nsc_call && (int64_t)ctx->nsc_call_ids.size() != n_pods))
-        return fail(KE_ERR_DEVICE, "internal: node set / score table ids of another call");
-    }
-    if (groups && (int64_t)ctx->sg_call_ids.size() != n_pods)
-      return fail(KE_ERR_DEVICE, "internal: spread group ids of another call");
-    if (domains && (int64_t)ctx->sd_call_ids.size() != n_pods)
-      return fail(KE_ERR_DEVICE, "internal: spread domain ids of another call");
-    if (terms && (int64_t)ctx->st_call_recs.size() != n_pods)
-      return fail(KE_ERR_DEVICE, "internal: spread term lists of another call");
-    if ((rc = id_tables_sync(ctx, terms ? NS_TERMS : domains ? NS_DOMAINS : groups ? NS_GROUPS : ns))) return rc;
-    return upload_pods(ctx, n_pods, pods, (int64_t)n_pods + 1, &h_bases, &upload_bytes, &n_copies);
+    if (att.ns() && att.n_pods != n_pods) return fail(KE_ERR_DEVICE, "internal: per-pod attachments of another call");
+    if ((rc = id_tables_sync(ctx, att.ns()))) return rc;
+    return upload_pods(ctx, n_pods, pods, lay, (int64_t)n_pods + 1, &h_bases, &upload_bytes, &n_copies);
   }
 
   // host only: batches, runs, each batch's select and the layouts
@@ -8897,7 +8824,7 @@ struct ScheduleCall {
     knob = select_knob(std::getenv("KOORDEVAL_SELECT_PARTS"));
     ctx->last_ds_cuts = 0;
     batches = plan_batches(c.host_pods.data(), n_pods, ctx->cfg.pod_batch, !sharded && !numa && N > 0, fused,
-                           terms ? ctx->st_listed.data() : ctx->sg_call, ctx->sd_call);  // (term lists mark a batch as group ids do)
+                           att.plan_groups(), att.plan_domains());
     for (const Batch& b : batches) any_cpu = any_cpu || b.cpu;
     if (any_cpu && !d->has(ST_CPU)) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
     n_batches = (int)batches.size();
@@ -9004,7 +8931,7 @@ struct ScheduleCall {
   // the bookkeeping words, the one copy of everything the call uploads, the call's events, and k_call_begin
   int begin() {
     RC_OK(c.d_sched.reserve((size_t)sl.total));
-    d_bases = reinterpret_cast<int32_t*>(c.d_pods + n_pods) + id_words(ctx, n_pods);
+    d_bases = reinterpret_cast<int32_t*>(c.d_pods + n_pods) + lay.total;
     d_ready = c.d_sched + sl.ready, d_done = c.d_sched + sl.done, d_tready = c.d_sched + sl.tready;
     d_sstart = c.d_sched + sl.sstart, d_rres = c.d_sched + sl.rres, d_tlist = c.d_sched + sl.tlist;
     d_tmx = reinterpret_cast<uint32_t*>(c.d_sched + sl.tmx);
@@ -9100,7 +9027,7 @@ struct ScheduleCall {
       // the nodes batch b-2 changed, once it is done (k_patch waits for the flag; folding it into the split select
       // was measured slower: 256 select workgroups spinning on the flag)
       if (a.pwait)
-        hipLaunchKernelGGL(pick_patch(ext, ns), dim3((unsigned)bp), dim3(64), d->excl_lds, es, d->soa, c.d_pods, bbase, k,
+        hipLaunchKernelGGL(pick_patch(ext, run_ns()), dim3((unsigned)bp), dim3(64), d->excl_lds, es, d->soa, c.d_pods, bbase, k,
                            a.ptl, eb.scores, d->capacity, a.pwait, d_err);  // (a run's batch: never grouped)
       if (ds && sharded && !d->loopback) {  // DefaultNormalizeScore's max over the feasible nodes of all ranks
         if ((rc = coll_all_reduce(d, d->d_dsmax, 1, KE_COLL_U32, KE_COLL_MAX, es))) return rc;
@@ -9229,7 +9156,7 @@ struct ScheduleCall {
     const THelp th{d_tlist, d_tmx, d_tready, fixup ? 0 : d->t_helpers, d->t_help_ignore, d_rres + r0};
     bool sorted = true;  // (every batch's lists descending: k_fixlist's always are)
     for (int q = r0; q < e; q++) sorted = sorted && sel[(size_t)q].sorted;
-    const auto resolve = pick_resolve_run(quota, ext, ns);
+    const auto resolve = pick_resolve_run(quota, ext, run_ns());
     if (!resolve) return no_variant("k_resolve_run with node sets and quota");
     hipLaunchKernelGGL(resolve, dim3(1 + th.H), dim3(res_threads<false>()), 0, d->stream, d->soa, c.d_pods, d_bases, r0,
                        e - r0, k, d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score, ctx->cfg.global_node_offset, d_st,
@@ -9245,7 +9172,7 @@ struct ScheduleCall {
       EvalSelect a{q, d->estream};
       if (fixup) {  // stale lists, made exact by k_fixup behind batch q-1
         if ((rc = eval_select(a))) return rc;
-        hipLaunchKernelGGL(pick_fixup(ext, ns), dim3((unsigned)bp), dim3(FIX_BLOCK), 0, d->estream, d->soa, c.d_pods,
+        hipLaunchKernelGGL(pick_fixup(ext, run_ns()), dim3((unsigned)bp), dim3(FIX_BLOCK), 0, d->estream, d->soa, c.d_pods,
                            d_bases + q, k, stale, stale_cnt, d->d_trows, d->d_tcnt, d->d_cand, d->d_cand_cnt, d_done,
                            q == r0 ? -1 : q - 1, d_ready + q, d_err, d_fst + 2 * q);
         continue;
@@ -9262,11 +9189,11 @@ struct ScheduleCall {
         const SelectPlan& sp = sel[(size_t)q];
         const int32_t* const done2 = q - 2 >= r0 ? d_done + (q - 2) : nullptr;
         if (d->fix_merge && sp.parts > 1)  // the select left its parts unmerged in the split buffer: the fix merges them
-          hipLaunchKernelGGL(pick_fixlist(ext, true, ns), dim3((unsigned)bp), dim3(FIXL_PARTS_BLOCK), 0, a.es, d->soa,
+          hipLaunchKernelGGL(pick_fixlist(ext, true, run_ns()), dim3((unsigned)bp), dim3(FIXL_PARTS_BLOCK), 0, a.es, d->soa,
                              c.d_pods, d_bases + q, k, a.alt ? d->d_split2 : d->d_split, nullptr, tl2, done2, stale,
                              stale_cnt, d_ready + q, d_err, (int64_t)gath_words(sp.L), sp.parts);
         else
-          hipLaunchKernelGGL(pick_fixlist(ext, false, ns), dim3((unsigned)bp), dim3(FIXL_BLOCK), 0, a.es, d->soa, c.d_pods,
+          hipLaunchKernelGGL(pick_fixlist(ext, false, run_ns()), dim3((unsigned)bp), dim3(FIXL_BLOCK), 0, a.es, d->soa, c.d_pods,
                              d_bases + q, k, d->d_pre + (size_t)(q & 1) * MAX_BATCH * KSTALE2,
                              reinterpret_cast<const int32_t*>(d->d_pre + (size_t)2 * MAX_BATCH * KSTALE2) + (q & 1) * MAX_BATCH,
                              tl2, done2, stale, stale_cnt, d_ready + q, d_err, (int64_t)0, 1);
@@ -9418,9 +9345,7 @@ struct ScheduleCall {
     cp.flush_ms = flush_ms;
     cp.entry = ctx->call_entry, cp.behind = ctx->call_behind;
     cp.copies = n_copies, cp.fills = n_fills, cp.n_pipelined = n_pipelined;
-    if (groups) cp.groups.assign(ctx->sg_call, ctx->sg_call + n_pods);
-    if (domains) cp.domains.assign(ctx->sd_call, ctx->sd_call + n_pods);
-    if (terms) cp.terms.assign(ctx->st_call, ctx->st_call + n_pods);
+    cp.placed = PlacedAttach(att, n_pods);
     *fin = [cp = std::move(cp)](int32_t* chosen, int32_t* score) { return complete_call(cp, chosen, score); };
     return KE_OK;
   }
@@ -9494,7 +9419,7 @@ int device_bench_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t 
   if (n_pods < 1 || n_pods > MAX_BATCH || iters < 1) return fail(KE_ERR_INVALID, "bench: 1 <= n_pods <= 64, iters >= 1");
   int rc = device_refresh(ctx, now);
   if (rc) return rc;
-  rc = upload_pods(ctx, n_pods, pods);
+  rc = upload_pods(ctx, n_pods, pods, AttachLayout(CallAttach{}, n_pods));  // (the bare records: its kernels run with NS = 0)
   if (rc) return rc;
   const int N = ctx->n_nodes;
   if (N == 0) return fail(KE_ERR_INVALID, "bench: no nodes");

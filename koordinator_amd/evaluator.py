@@ -492,13 +492,8 @@ class Evaluator:
         return lo.value, hi.value
 
     # ---- evaluation -------------------------------------------------------------------------
-    def eval(self, pods, now_ns, node_sets=None, node_scores=None, spread_groups=None, spread_domains=None,
-             spread_terms=None):
-        """ke_eval; `node_sets` (optional): the node set id per pod (0 = every node); `node_scores` (optional): the
-        score table id per pod (0 = no offset); `spread_groups` (optional): the spread group id per pod (0 = none);
-        `spread_domains` (optional): the spread domain group id per pod (0 = none); `spread_terms` (optional): the
-        pair (terms, members) of pod_spread_terms()."""
-        pods = as_pod_array(pods)
+    def _stage(self, node_sets, node_scores, spread_groups, spread_domains, spread_terms):
+        """The next call's per-pod attachments: each keyword that is not None goes through its pod_*() staging."""
         if node_sets is not None:
             self.pod_node_sets(node_sets)
         if node_scores is not None:
@@ -509,6 +504,15 @@ class Evaluator:
             self.pod_spread_domains(spread_domains)
         if spread_terms is not None:
             self.pod_spread_terms(*spread_terms)
+
+    def eval(self, pods, now_ns, node_sets=None, node_scores=None, spread_groups=None, spread_domains=None,
+             spread_terms=None):
+        """ke_eval; `node_sets` (optional): the node set id per pod (0 = every node); `node_scores` (optional): the
+        score table id per pod (0 = no offset); `spread_groups` (optional): the spread group id per pod (0 = none);
+        `spread_domains` (optional): the spread domain group id per pod (0 = none); `spread_terms` (optional): the
+        pair (terms, members) of pod_spread_terms()."""
+        pods = as_pod_array(pods)
+        self._stage(node_sets, node_scores, spread_groups, spread_domains, spread_terms)
         P, N = len(pods), self.num_nodes
         out = {
             "status": np.zeros((P, N), np.uint8),
@@ -532,14 +536,7 @@ class Evaluator:
         `bitmaps` also the bool [P, N] matrices feasible, unschedulable, unresolvable.  `node_sets`, `spread_groups`,
         `spread_domains` and `spread_terms` (its filter kinds) as for eval()."""
         pods = as_pod_array(pods)
-        if node_sets is not None:
-            self.pod_node_sets(node_sets)
-        if spread_groups is not None:
-            self.pod_spread_groups(spread_groups)
-        if spread_domains is not None:
-            self.pod_spread_domains(spread_domains)
-        if spread_terms is not None:
-            self.pod_spread_terms(*spread_terms)
+        self._stage(node_sets, None, spread_groups, spread_domains, spread_terms)
         P, N = len(pods), self.num_nodes
         rec = np.zeros(P, abi.POD_DIAGNOSIS_DTYPE)
         wpp = (N + 63) // 64
@@ -562,16 +559,7 @@ class Evaluator:
         pods = as_pod_array(pods)
         if matches is not None:
             self.pod_reservations(matches)
-        if node_sets is not None:
-            self.pod_node_sets(node_sets)
-        if node_scores is not None:
-            self.pod_node_scores(node_scores)
-        if spread_groups is not None:
-            self.pod_spread_groups(spread_groups)
-        if spread_domains is not None:
-            self.pod_spread_domains(spread_domains)
-        if spread_terms is not None:
-            self.pod_spread_terms(*spread_terms)
+        self._stage(node_sets, node_scores, spread_groups, spread_domains, spread_terms)
         chosen = np.zeros(len(pods), np.int32)
         score = np.zeros(len(pods), np.int32)
         self._check(self.lib.ke_schedule(self.h, len(pods), abi.ptr(pods), int(now_ns), abi.ptr(chosen), abi.ptr(score)))
@@ -584,16 +572,7 @@ class Evaluator:
         it).  The pod array is kept alive here until then.  `node_sets`, `node_scores`, `spread_groups`,
         `spread_domains` and `spread_terms` as for schedule()."""
         pods = as_pod_array(pods)
-        if node_sets is not None:
-            self.pod_node_sets(node_sets)
-        if node_scores is not None:
-            self.pod_node_scores(node_scores)
-        if spread_groups is not None:
-            self.pod_spread_groups(spread_groups)
-        if spread_domains is not None:
-            self.pod_spread_domains(spread_domains)
-        if spread_terms is not None:
-            self.pod_spread_terms(*spread_terms)
+        self._stage(node_sets, node_scores, spread_groups, spread_domains, spread_terms)
         t = C.c_int64()
         self._check(self.lib.ke_schedule_submit(self.h, len(pods), abi.ptr(pods), int(now_ns), C.byref(t)))
         self._inflight[t.value] = pods

@@ -5,7 +5,10 @@
 // (byte flips, cuts, duplicated ranges, JSON fragments, numbers at the int64 / float64 edges, splices of two
 // seeds) and fed to every decoder, whatever its kind.  What decodes is then pushed through the informer-facing
 // entry points of a context (node / NodeMetric / device / NUMA / CPU ingestion, assign, release, the host row
-// derivation).  Any memory error, overflow or other undefined behaviour aborts the run (-fno-sanitize-recover).
+// derivation).  Every 16th iteration stages per-pod attachments (ke_pod_node_sets .. ke_pod_spread_terms; random
+// lengths, some ids out of range, sometimes a smaller table loaded in between) and takes them with a ke_eval or
+// ke_diagnose whose pod count sometimes differs.  Any memory error, overflow or other undefined behaviour aborts the
+// run (-fno-sanitize-recover).
 //
 // usage: ke_asan_fuzz <corpus: one "kind<TAB>json" per line> <iterations> <seed>
 #include <cstdio>
@@ -85,6 +88,98 @@ ke_pod_allocation random_alloc(std::mt19937_64& rng, int32_t node) {
   for (int w = 0; w < KE_MAX_NUMA * KE_NRES; w++) a.numa[w] = (int64_t)(rng() % 4) * (int64_t)(rng() % (1ull << 40));
   a.device_minors = rng() & rng() & 0xFFFFFFFFFFFFull;
   return a;
+}
+
+// the codes a call's admission may answer in a context without a device
+long g_admitted[6] = {0, 0, 0, 0, 0, 0};  // by -rc
+bool admitted(int rc, const char* what) {
+  if (rc <= 0 && rc >= -5) g_admitted[-rc]++;
+  if (rc == KE_OK || rc == KE_ERR_INVALID || rc == KE_ERR_UNSUPPORTED || rc == KE_ERR_NO_DEVICE) return true;
+  std::fprintf(stderr, "%s: unexpected return code %d (%s)\n", what, rc, ke_last_error());
+  return false;
+}
+
+// (re)load the four tables the per-pod ids index, `rows` of each at most (0: unload)
+bool load_tables(std::mt19937_64& rng, ke_ctx* ctx, int32_t rows, int32_t* limits) {
+  const int32_t n_nodes = (int32_t)(rng() % 65);
+  limits[0] = (int32_t)(rng() % (uint64_t)(rows + 1));
+  std::vector<uint64_t> bits((size_t)limits[0] + 1);
+  for (uint64_t& w : bits) w = rng();
+  bool ok = admitted(ke_node_sets_load(ctx, limits[0], 1, bits.data()), "ke_node_sets_load");
+  limits[1] = (int32_t)(rng() % (uint64_t)(rows + 1));
+  std::vector<uint16_t> scores((size_t)limits[1] * (size_t)n_nodes + 1);
+  for (uint16_t& v : scores) v = (uint16_t)(rng() % 60);
+  ok = ok && admitted(ke_node_scores_load(ctx, limits[1], n_nodes, scores.data()), "ke_node_scores_load");
+  limits[2] = (int32_t)(rng() % (uint64_t)(rows + 1));
+  std::vector<uint16_t> caps((size_t)limits[2] + 1);
+  for (uint16_t& v : caps) v = (uint16_t)(1 + rng() % 3);
+  ok = ok && admitted(ke_spread_groups_load(ctx, limits[2], n_nodes, nullptr, caps.data()), "ke_spread_groups_load");
+  limits[3] = (int32_t)(rng() % (uint64_t)(rows + 1));
+  std::vector<uint16_t> node_domain((size_t)n_nodes + 1);
+  for (uint16_t& v : node_domain) v = rng() % 8 ? (uint16_t)(rng() % 4) : (uint16_t)KE_DOMAIN_NONE;
+  std::vector<int32_t> gmap((size_t)limits[3] + 1, 1), skew((size_t)limits[3] + 1, 1);
+  std::vector<uint64_t> doms((size_t)limits[3] + 1, 0xFull);
+  ok = ok && admitted(ke_spread_domains_load(ctx, 1, n_nodes, node_domain.data(), limits[3], gmap.data(), doms.data(),
+                                             skew.data(), nullptr, nullptr),
+                      "ke_spread_domains_load");
+  return ok;
+}
+
+// One round of per-pod attachments: tables, the five stagings (each with probability 1/2, ids up to one past the
+// table), sometimes smaller tables behind the staging, then the call that takes them.
+bool attach_round(std::mt19937_64& rng, ke_ctx* ctx, const std::vector<ke_pod>& pool) {
+  int32_t limits[4];
+  if (!load_tables(rng, ctx, 3, limits)) return false;
+  const int32_t n = (int32_t)(rng() % 9);
+  typedef int (*StageFn)(ke_ctx*, int32_t, const int32_t*);
+  const StageFn stage[4] = {ke_pod_node_sets, ke_pod_node_scores, ke_pod_spread_groups, ke_pod_spread_domains};
+  const char* const names[4] = {"ke_pod_node_sets", "ke_pod_node_scores", "ke_pod_spread_groups", "ke_pod_spread_domains"};
+  for (int k = 0; k < 4; k++) {
+    if (rng() & 1) continue;
+    const int32_t len = rng() % 4 ? n : (int32_t)(rng() % 9);
+    std::vector<int32_t> ids((size_t)len + 1);
+    for (int32_t& id : ids) id = rng() % 16 ? (int32_t)(rng() % (uint64_t)(limits[k] + 1)) : limits[k] + 1;
+    if (!admitted(stage[k](ctx, len, ids.data()), names[k])) return false;
+  }
+  if (rng() & 1) {
+    const int32_t len = rng() % 4 ? n : (int32_t)(rng() % 9);
+    std::vector<int32_t> toff((size_t)len + 1, 0), moff((size_t)len + 1, 0), terms, members;
+    for (int32_t p = 0; p < len; p++) {
+      const int nt = (int)(rng() % (KE_MAX_POD_TERMS + 1)), nm = (int)(rng() % (KE_MAX_POD_MEMBERS + 1));
+      for (int t = 0; t < nt; t++) {
+        const int32_t kind = (int32_t)(KE_TERM_ANTI + rng() % 4);
+        const int32_t group = rng() % 16 ? (int32_t)(1 + rng() % (uint64_t)(limits[2] > 0 ? limits[2] : 1)) : limits[2] + 1;
+        terms.insert(terms.end(), {group, kind, (int32_t)(1 + rng() % 5),
+                                   kind >= KE_TERM_PREFER_FEWER ? (int32_t)(1 + rng() % 100) : 0});
+      }
+      for (int m = 0; m < nm; m++) members.push_back((int32_t)(1 + m));  // (distinct; beyond the table when it is small)
+      toff[(size_t)p + 1] = (int32_t)(terms.size() / 4);
+      moff[(size_t)p + 1] = (int32_t)members.size();
+    }
+    terms.push_back(0), members.push_back(0);  // (non-null data() for empty lists)
+    if (!admitted(ke_pod_spread_terms(ctx, len, toff.data(), terms.data(), moff.data(), members.data()), "ke_pod_spread_terms"))
+      return false;
+  }
+  if (rng() % 4 == 0 && !load_tables(rng, ctx, (int32_t)(rng() % 2), limits)) return false;  // smaller, behind the staging
+  const int32_t n_call = rng() % 4 ? n : (int32_t)(rng() % 9);
+  std::vector<ke_pod> pods((size_t)n_call + 1, ke_pod{});
+  for (ke_pod& q : pods)
+    if (!pool.empty()) q = pool[rng() % pool.size()];
+  const size_t cells = (size_t)n_call * (size_t)ke_num_nodes(ctx) + 1;
+  if (rng() & 1) {
+    std::vector<uint8_t> status(cells), reason(cells);
+    std::vector<int16_t> la(cells), numa(cells), ds(cells), total(cells);
+    std::vector<int32_t> best((size_t)n_call + 1);
+    return admitted(ke_eval(ctx, n_call, pods.data(), 1700000000000000000LL, status.data(), reason.data(), la.data(),
+                            numa.data(), ds.data(), total.data(), best.data()),
+                    "ke_eval");
+  }
+  std::vector<ke_pod_diagnosis> out((size_t)n_call + 1);
+  const int32_t wpp = (ke_num_nodes(ctx) + 63) / 64;
+  std::vector<uint64_t> bits((size_t)n_call * (size_t)wpp + 1);
+  return admitted(ke_diagnose(ctx, n_call, pods.data(), 1700000000000000000LL, out.data(), wpp,
+                              rng() & 1 ? bits.data() : nullptr, nullptr, nullptr),
+                  "ke_diagnose");
 }
 
 }  // namespace
@@ -182,6 +277,7 @@ int main(int argc, char** argv) {
       const ke_pod_allocation a = random_alloc(rng, rng() % 8 ? node : -1);
       ke_pod_release(ctx, &q, &a, (int32_t)(rng() % 2));
     }
+    if (it % 16 == 15 && !attach_round(rng, ctx, pods)) return 1;
     if (it % 64 == 63) {  // the host folding of every node (no device rows)
       std::vector<unsigned char> rows((size_t)ke_num_nodes(ctx) * 152 + 1);
       ke_debug_rows(ctx, ke_num_nodes(ctx), 1700000000000000000LL + it, nullptr, rows.data());
@@ -192,5 +288,7 @@ int main(int argc, char** argv) {
   }
   ke_destroy(ctx);
   std::printf("fuzz ok: %ld iterations, %ld decoded objects, %ld rejected node documents\n", iters, decoded, rejected);
+  std::printf("attachment rounds: %ld calls accepted, %ld invalid, %ld unsupported, %ld reached the missing device\n",
+              g_admitted[0], g_admitted[-KE_ERR_INVALID], g_admitted[-KE_ERR_UNSUPPORTED], g_admitted[-KE_ERR_NO_DEVICE]);
   return 0;
 }
