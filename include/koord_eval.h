@@ -1086,6 +1086,46 @@ int ke_pod_spread_domains(ke_ctx* ctx, int32_t n_pods, const int32_t* group_ids)
  * range, more than 4 terms or members for one pod, a repeated member, offsets that do not ascend from 0. */
 int ke_pod_spread_terms(ke_ctx* ctx, int32_t n_pods, const int32_t* term_offsets, const int32_t* terms,
                         const int32_t* member_offsets, const int32_t* members);
+/* ---- spread domain terms: zone-level affinity, anti-affinity, soft spread (additive: KE_ABI_VERSION stays 14) ---
+ * A spread domain group id is one shape of constraint above the hostname: the pod is filtered on the group it
+ * increments, by skew.  Spread domain terms open the spread domain tables (ke_spread_domains_load / _add / _node_set /
+ * _get, unchanged) to the rest of what InterPodAffinity and PodTopologySpread do on a zone or rack: ScheduleAnyway
+ * spreading, required and preferred affinity / anti-affinity between workloads, several constraints on one pod, a
+ * placement that counts for several groups.  The semantics are upstream's, fixed here by convention like the other
+ * in-tree plugins.  A pod of a call may carry two lists over spread domain groups 1..n_groups; with
+ * d = map_of_group[node] and count = count[group][d]:
+ *  - Terms, up to KE_MAX_POD_TERMS, each (group, kind, param, weight):
+ *      KE_TERM_SKEW          the spread domain filter of the group: its domains, max_skew and      param 0, weight 0
+ *                            min_domains (the only kind that reads them); a KE_DOMAIN_NONE node is filtered
+ *      KE_TERM_ANTI          node filtered when count >= param; a KE_DOMAIN_NONE node passes       weight 0
+ *      KE_TERM_AFFINITY      node filtered when count <  param; a KE_DOMAIN_NONE node is filtered  weight 0
+ *      KE_TERM_PREFER_FEWER  feasible total += weight * (param - min(count, param)); NONE adds 0   weight 1..100
+ *      KE_TERM_PREFER_MORE   feasible total += weight * min(count, param); NONE adds 0             weight 1..100
+ *    param in 1..65535 for the four kinds shared with spread terms.  A filtered pair reports exactly as a spread
+ *    domain / spread term filtered pair (KE_REASON_NODE_SET, unresolvable, scores 0, total -1, outside best[] and
+ *    DeviceShare's NormalizeScore maximum, never deferred); the test follows the spread terms' filter terms and precedes
+ *    every koordinator filter.  The bonus goes where the spread terms' bonus goes (in ke_eval behind the normalisation).
+ *    ke_diagnose applies the filter kinds only.
+ *  - Members, up to KE_MAX_POD_MEMBERS distinct groups: a placement on node n does count[m][map_m[n]] += 1 for every
+ *    member m whose domain there is not KE_DOMAIN_NONE (members may use different maps; no saturation, as with spread
+ *    domain ids).  Later batches, later calls and slices submitted ahead see it: a batch ends before a pod one of whose
+ *    term groups is a member group of an earlier pod of that batch.  ke_unreserve / ke_pod_release do NOT touch counts.
+ * A spread domain id g is the special case terms = {SKEW(g)}, members = {g}; a spread group id has the spread term form
+ * given above.  Staged together with ke_pod_spread_domains ids or ke_pod_spread_groups ids the call is KE_ERR_INVALID:
+ * write those ids as lists.  Together with set ids, table ids and spread term lists they are allowed.
+ * Key range: the spread terms' check sums weight * param over a pod's spread terms and spread domain score terms
+ * against the same cap; the message begins "spread domain terms: " whenever the call carries a domain list.
+ * A ke_schedule / ke_schedule_submit call with a non-empty list must be a plain queue exactly as one with a non-zero
+ * node set id; anything else is KE_ERR_UNSUPPORTED before any state changes ("spread domain terms: ...", or an earlier
+ * kind's message when the call carries one). */
+#define KE_TERM_SKEW 5
+/* The lists per pod, CSR as ke_pod_spread_terms takes them, with its lifecycle: for the NEXT ke_eval / ke_diagnose /
+ * ke_schedule / ke_schedule_submit of exactly n_pods pods, consumed by that call whether it succeeds or not; does not
+ * wait for calls in flight.  KE_ERR_INVALID: a group outside 1..n_groups of the spread domain table (or no table
+ * loaded), an unknown kind, KE_TERM_SKEW with a non-zero param or weight, a param or weight outside its range, more
+ * than 4 terms or members for one pod, a repeated member, offsets that do not ascend from 0. */
+int ke_pod_spread_domain_terms(ke_ctx* ctx, int32_t n_pods, const int32_t* term_offsets, const int32_t* terms,
+                               const int32_t* member_offsets, const int32_t* members);
 /* ---- FitError diagnosis of unschedulable pods (additive: KE_ABI_VERSION stays 14) -------------------
  * A pod ke_schedule left at chosen = -1 must go back to the queue with a framework.FitError.  The reference reads
  * three parts of it, all reductions of the Filter status map (framework.NodeToStatusMap) findNodesThatFitPod fills:

@@ -81,6 +81,7 @@ MAX_SPREAD_DOMAIN_MAPS = 8
 MAX_POD_TERMS = 4
 MAX_POD_MEMBERS = 4
 TERM_ANTI, TERM_AFFINITY, TERM_PREFER_FEWER, TERM_PREFER_MORE = 1, 2, 3, 4
+TERM_SKEW = 5  # ke_pod_spread_domain_terms alone
 DOMAIN_NONE = 0xFFFF
 # ke_pod.gpu_required_topology_scope (apiext.DeviceTopologyScope -> level)
 SCOPE_NONE, SCOPE_NODE, SCOPE_NUMA, SCOPE_PCIE, SCOPE_DEVICE, SCOPE_UNKNOWN = range(6)
@@ -602,6 +603,7 @@ EXPORTS = {
     "ke_spread_domains_get": (C.c_int, [C.c_void_p, i32, C.c_void_p]),
     "ke_pod_spread_domains": (C.c_int, [C.c_void_p, i32, C.c_void_p]),
     "ke_pod_spread_terms": (C.c_int, [C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ke_pod_spread_domain_terms": (C.c_int, [C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ke_node_info_requested": (C.c_int, [C.c_void_p, i32, C.POINTER(i64), C.POINTER(i64)]),
     "ke_decode_pod_device_hints": (C.c_int, [C.c_char_p, i64, C.POINTER(PodDeviceHints), C.POINTER(i32)]),
     "ke_decode_device_flags": (C.c_int, [C.c_char_p, i64, C.c_char_p, i64, C.POINTER(i32), C.POINTER(i32)]),

@@ -865,45 +865,67 @@ static_assert(KE_MAX_POD_TERMS == POD_TERMS && KE_MAX_POD_MEMBERS == POD_MEMBERS
                   KE_TERM_AFFINITY == ST_AFFINITY && KE_TERM_PREFER_FEWER == ST_PREFER_FEWER &&
                   KE_TERM_PREFER_MORE == ST_PREFER_MORE && KE_MAX_SPREAD_GROUPS < (1 << 16),
               "the packed record");
-int ke_pod_spread_terms(ke_ctx* ctx, int32_t n_pods, const int32_t* term_offsets, const int32_t* terms,
-                        const int32_t* member_offsets, const int32_t* members) {
-  if (!ctx || n_pods < 0 || !term_offsets || !member_offsets) return fail(KE_ERR_INVALID, "ke_pod_spread_terms arguments");
+// ke_pod_spread_terms and ke_pod_spread_domain_terms share the CSR checks and the packed record:
+// `name` leads every message, `n_groups` is the table the groups are checked against, `max_kind` the last kind
+// (KE_TERM_SKEW, param and weight 0, only over the spread domain table).
+static int stage_term_lists(ke_ctx* ctx, int32_t n_pods, const int32_t* term_offsets, const int32_t* terms,
+                            const int32_t* member_offsets, const int32_t* members, const char* name,
+                            int32_t Context::*n_groups, int32_t max_kind, AttachSlot<PodTerms> Context::*slot) {
+  auto bad = [name](const char* what) { return fail(KE_ERR_INVALID, std::string(name) + what); };
+  if (!ctx || n_pods < 0 || !term_offsets || !member_offsets) return bad(" arguments");
   Context& c = ctx->c;
-  if (term_offsets[0] != 0 || member_offsets[0] != 0) return fail(KE_ERR_INVALID, "ke_pod_spread_terms: offsets do not start at 0");
+  const int32_t limit = c.*n_groups;
+  if (term_offsets[0] != 0 || member_offsets[0] != 0) return bad(": offsets do not start at 0");
   for (int32_t p = 0; p < n_pods; p++) {
     if (term_offsets[p + 1] < term_offsets[p] || member_offsets[p + 1] < member_offsets[p])
-      return fail(KE_ERR_INVALID, "ke_pod_spread_terms: offsets do not ascend");
+      return bad(": offsets do not ascend");
     if (term_offsets[p + 1] - term_offsets[p] > KE_MAX_POD_TERMS)
-      return fail(KE_ERR_INVALID, "ke_pod_spread_terms: more than KE_MAX_POD_TERMS terms for one pod");
+      return bad(": more than KE_MAX_POD_TERMS terms for one pod");
     if (member_offsets[p + 1] - member_offsets[p] > KE_MAX_POD_MEMBERS)
-      return fail(KE_ERR_INVALID, "ke_pod_spread_terms: more than KE_MAX_POD_MEMBERS members for one pod");
+      return bad(": more than KE_MAX_POD_MEMBERS members for one pod");
   }
   if ((term_offsets[n_pods] > 0 && !terms) || (member_offsets[n_pods] > 0 && !members))
-    return fail(KE_ERR_INVALID, "ke_pod_spread_terms arguments");
+    return bad(" arguments");
   std::vector<PodTerms> recs((size_t)n_pods, PodTerms{});
   for (int32_t p = 0; p < n_pods; p++) {
     PodTerms& r = recs[(size_t)p];
     for (int32_t q = term_offsets[p], t = 0; q < term_offsets[p + 1]; q++, t++) {
       const int32_t group = terms[4 * q], kind = terms[4 * q + 1], param = terms[4 * q + 2], weight = terms[4 * q + 3];
-      if (group < 1 || group > c.sg_n) return fail(KE_ERR_INVALID, "ke_pod_spread_terms: a term's group outside 1..n_groups");
-      if (kind < KE_TERM_ANTI || kind > KE_TERM_PREFER_MORE) return fail(KE_ERR_INVALID, "ke_pod_spread_terms: unknown term kind");
-      if (param < 1 || param > 65535) return fail(KE_ERR_INVALID, "ke_pod_spread_terms: a param outside 1..65535");
-      const bool score = kind >= KE_TERM_PREFER_FEWER;
+      if (group < 1 || group > limit) return bad(": a term's group outside 1..n_groups");
+      if (kind < KE_TERM_ANTI || kind > max_kind) return bad(": unknown term kind");
+      if (kind == KE_TERM_SKEW) {
+        if (param != 0 || weight != 0) return bad(": KE_TERM_SKEW with a non-zero param or weight");
+        r.tw[t] = (uint32_t)group | (uint32_t)kind << 16;
+        continue;
+      }
+      if (param < 1 || param > 65535) return bad(": a param outside 1..65535");
+      const bool score = kind == KE_TERM_PREFER_FEWER || kind == KE_TERM_PREFER_MORE;
       if (score ? (weight < 1 || weight > 100) : weight != 0)
-        return fail(KE_ERR_INVALID, "ke_pod_spread_terms: a weight outside 1..100 (score terms) or not 0 (filter terms)");
+        return bad(": a weight outside 1..100 (score terms) or not 0 (filter terms)");
       r.tw[t] = (uint32_t)group | (uint32_t)kind << 16 | (uint32_t)weight << 24;
       r.tp[t >> 1] |= (uint32_t)param << ((t & 1) * 16);
     }
     for (int32_t q = member_offsets[p], m = 0; q < member_offsets[p + 1]; q++, m++) {
       const int32_t group = members[q];
-      if (group < 1 || group > c.sg_n) return fail(KE_ERR_INVALID, "ke_pod_spread_terms: a member outside 1..n_groups");
+      if (group < 1 || group > limit) return bad(": a member outside 1..n_groups");
       for (int32_t u = member_offsets[p]; u < q; u++)
-        if (members[u] == group) return fail(KE_ERR_INVALID, "ke_pod_spread_terms: a repeated member");
+        if (members[u] == group) return bad(": a repeated member");
       r.mem[m >> 1] |= (uint32_t)group << ((m & 1) * 16);
     }
   }
-  c.pod_terms.stage(recs);
+  (c.*slot).stage(recs);
   return KE_OK;
+}
+int ke_pod_spread_terms(ke_ctx* ctx, int32_t n_pods, const int32_t* term_offsets, const int32_t* terms,
+                        const int32_t* member_offsets, const int32_t* members) {
+  return stage_term_lists(ctx, n_pods, term_offsets, terms, member_offsets, members, "ke_pod_spread_terms", &Context::sg_n,
+                          KE_TERM_PREFER_MORE, &Context::pod_terms);
+}
+static_assert(KE_TERM_SKEW == ST_SKEW && KE_MAX_SPREAD_DOMAIN_GROUPS < (1 << 16), "the packed record");
+int ke_pod_spread_domain_terms(ke_ctx* ctx, int32_t n_pods, const int32_t* term_offsets, const int32_t* terms,
+                               const int32_t* member_offsets, const int32_t* members) {
+  return stage_term_lists(ctx, n_pods, term_offsets, terms, member_offsets, members, "ke_pod_spread_domain_terms",
+                          &Context::sd_n, KE_TERM_SKEW, &Context::pod_dterms);
 }
 
 // The ke_pod_node_sets, ke_pod_node_scores, ke_pod_spread_groups and ke_pod_spread_domains ids of this call, all
@@ -914,7 +936,9 @@ int ke_pod_spread_terms(ke_ctx* ctx, int32_t n_pods, const int32_t* term_offsets
 // names the sets when a set id is non-zero, else the scores when a table id is, else the spread groups, else the spread
 // domains, else the spread terms.  ke_pod_spread_terms' lists go the same way: att.terms = the call's
 // records when one of them is not empty; staged together with group ids they are KE_ERR_INVALID, and a pod whose score
-// terms could push total + 1 out of the key's 10 bits is KE_ERR_UNSUPPORTED.  `filter_only` (ke_diagnose): the call
+// terms could push total + 1 out of the key's 10 bits is KE_ERR_UNSUPPORTED.  ke_pod_spread_domain_terms' lists (§4u)
+// likewise: att.dterms; staged together with group ids or spread domain ids they are KE_ERR_INVALID, and their score
+// terms count against the same cap, summed per pod with its §4t score terms.  `filter_only` (ke_diagnose): the call
 // is checked as any other and then goes on without its score table ids, which do not filter.
 // The id kinds, in the order of every check and of the message prefix:
 enum { AK_SETS, AK_SCORES, AK_GROUPS, AK_DOMAINS, N_ID_KINDS };
@@ -936,16 +960,26 @@ static const struct {
 static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool sched, bool filter_only = false) {
   Context& c = ctx->c;
   c.att.reset();
-  if (!(c.pod_sets.on || c.pod_scores.on || c.pod_groups.on || c.pod_domains.on || c.pod_terms.on)) return KE_OK;
+  if (!(c.pod_sets.on || c.pod_scores.on || c.pod_groups.on || c.pod_domains.on || c.pod_terms.on || c.pod_dterms.on))
+    return KE_OK;
   bool on[N_ID_KINDS], any[N_ID_KINDS] = {false, false, false, false};
   for (int k = 0; k < N_ID_KINDS; k++) on[k] = (c.*ID_KINDS[k].slot).take();
   const bool terms_on = c.pod_terms.take();
+  const bool dterms_on = c.pod_dterms.take();
   for (int k = 0; k < N_ID_KINDS; k++)
     if (on[k] && (int32_t)(c.*ID_KINDS[k].slot).call.size() != n_pods) return fail(KE_ERR_INVALID, ID_KINDS[k].mismatch);
   if (terms_on && (int32_t)c.pod_terms.call.size() != n_pods)
     return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_spread_terms lists'");
   if (terms_on && on[AK_GROUPS])
     return fail(KE_ERR_INVALID, "a call with both ke_pod_spread_groups ids and ke_pod_spread_terms lists staged");
+  if (dterms_on && (int32_t)c.pod_dterms.call.size() != n_pods)
+    return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_spread_domain_terms lists'");
+  if (dterms_on && on[AK_GROUPS])
+    return fail(KE_ERR_INVALID, "a call with both ke_pod_spread_groups ids and ke_pod_spread_domain_terms lists staged: "
+                                "write group g as ke_pod_spread_terms {ANTI(g, cap)} + {g}");
+  if (dterms_on && on[AK_DOMAINS])
+    return fail(KE_ERR_INVALID, "a call with both ke_pod_spread_domains ids and ke_pod_spread_domain_terms lists staged: "
+                                "write group g as {KE_TERM_SKEW(g)} + {g}");
   for (int k = 0; k < N_ID_KINDS; k++)
     for (int32_t id : (c.*ID_KINDS[k].slot).call) {
       if (id < 0 || id > c.*ID_KINDS[k].limit) return fail(KE_ERR_INVALID, ID_KINDS[k].outside);
@@ -965,8 +999,29 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
     c.att.listed.push_back(st_empty(r) ? 0 : 1);
     any_st = any_st || !st_empty(r);
   }
+  // the domain term lists: over the spread domain table; a pod's score terms of both kinds add up against one cap
+  bool any_dt = false;
+  if (dterms_on) c.att.listed.resize((size_t)n_pods, 0);
+  for (size_t p = 0; p < c.pod_dterms.call.size(); p++) {
+    const PodTerms& r = c.pod_dterms.call[p];
+    int32_t sum = 0;
+    for (int t = 0; t < POD_TERMS; t++) {
+      if (st_group(r, t) > c.sd_n) return fail(KE_ERR_INVALID, "a staged spread domain term's group is outside the table loaded since");
+      if (st_kind(r, t) == ST_PREFER_FEWER || st_kind(r, t) == ST_PREFER_MORE) sum += st_weight(r, t) * (int32_t)st_param(r, t);
+    }
+    for (int m = 0; m < POD_MEMBERS; m++)
+      if (st_member(r, m) > c.sd_n) return fail(KE_ERR_INVALID, "a staged spread domain member is outside the table loaded since");
+    if (terms_on) {
+      const PodTerms& q = c.pod_terms.call[p];
+      for (int t = 0; t < POD_TERMS; t++)
+        if (st_kind(q, t) >= ST_PREFER_FEWER) sum += st_weight(q, t) * (int32_t)st_param(q, t);
+    }
+    st_sum = std::max(st_sum, sum);
+    if (!st_empty(r)) c.att.listed[p] = 1, any_dt = true;
+  }
   const bool any_sc = any[AK_SCORES];
-  const char* prefix = any_st ? "spread terms: " : nullptr;  // (the first kind present names a refusal)
+  // (the first kind present names a refusal)
+  const char* prefix = any_st ? "spread terms: " : any_dt ? "spread domain terms: " : nullptr;
   for (int k = N_ID_KINDS - 1; k >= 0; k--)
     if (any[k]) prefix = ID_KINDS[k].prefix;
   if (!prefix) return KE_OK;
@@ -988,17 +1043,18 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
       if (f & PF_CPUSET) return no("a cpuset pod in ke_schedule");
     }
   }
-  if (any_st) {
+  if (any_st || any_dt) {
     // the key holds total + 1 in 10 bits: the plugins' total, the largest table entry the call can add and the
     // largest bonus of a pod must fit together
     int32_t cap = node_score_cap(c.cfg);
     if (any_sc && !c.nsc_vals.empty()) cap -= (int32_t)*std::max_element(c.nsc_vals.begin(), c.nsc_vals.end());
     if (st_sum > cap)
-      return fail(KE_ERR_UNSUPPORTED, "spread terms: a pod's score terms can add " + std::to_string(st_sum) + ", above the cap " +
+      return fail(KE_ERR_UNSUPPORTED, std::string(any_dt ? "spread domain terms: " : "spread terms: ") + "a pod's score terms can add " + std::to_string(st_sum) + ", above the cap " +
                                           std::to_string(cap) + " = 1022 - 100 * (sum of the Score plugin weights)" +
                                           (any_sc ? " - the largest score table entry" : "") +
                                           ": total + 1 must fit the key's 10 bits");
-    c.att.terms = c.pod_terms.call.data();
+    if (any_st) c.att.terms = c.pod_terms.call.data();
+    if (any_dt) c.att.dterms = c.pod_dterms.call.data();
   }
   for (int k = 0; k < N_ID_KINDS; k++)
     if (any[k] && !(filter_only && k == AK_SCORES)) c.att.*ID_KINDS[k].view = (c.*ID_KINDS[k].slot).call.data();

@@ -264,9 +264,10 @@ struct Context {
   // The per-pod attachments of a call (ke_attach.h; DESIGN.md §3, the staging block): per kind what its ke_pod_* entry
   // point staged for the next call and what the call in progress took -- node set ids, score table ids, spread group
   // ids, spread domain group ids, spread term records (§4t: one packed record a pod, over the spread groups' counts)
-  // -- and `att`, the kinds the call in progress carries.
+  // and spread domain term records (§4u: the same record over the spread domain groups' counts) -- and `att`, the
+  // kinds the call in progress carries.
   AttachSlot<int32_t> pod_sets, pod_scores, pod_groups, pod_domains;
-  AttachSlot<PodTerms> pod_terms;
+  AttachSlot<PodTerms> pod_terms, pod_dterms;
   CallAttach att;
   // the KE_RSV_MATCHED pod of the current segment: its nodes with matched reservations, their
   // (node, ScoreReservation of the nominated one, smallest order) for the device pick, the nominated index

@@ -126,12 +126,26 @@ struct SoA {
   const uint16_t* sd_map;
   uint32_t* sd_cnt;
   const SdGroup* sd_par;
-  const int32_t* sd_ids;
-  uint64_t* sd_mask;
+  // (a call carries spread domain ids or spread domain term lists, never both, so the two kinds share words:
+  // upload_pods sets sd_ids / sd_mask for the first kind and dt_rec / dt_tbl for the second, never both pairs)
+  union {
+    const int32_t* sd_ids;
+    const PodTerms* dt_rec;  // §4u, below
+  };
+  union {
+    uint64_t* sd_mask;
+    uint16_t* dt_tbl;  // §4u, below
+  };
   // spread terms: the current call's term / member record per pod, parallel to its DevPod array, over
   // the spread groups' count table (sg_cnt; such a call's sg_ids are all zero).  Read only by the NS_TERMS
   // instantiations; the one-wave replay of a grouped batch increments the count of every (member, node) it Reserves.
   const PodTerms* st_rec;
+  // spread domain terms: dt_rec, the current call's domain term / member record per pod, over the
+  // spread domain tables, and dt_tbl, the pods' per-slot, per-domain tables ([pod][slot][64] cells, dt_cell), which
+  // k_domain_terms computes ahead of every eval that reads them.  They lie in sd_ids' and sd_mask's words: such a call
+  // carries no spread domain ids (and no spread group ids: its sg_ids are all zero), and its NS_DTERMS instantiations
+  // -- the only readers -- skip the §4s sites (ns_sd).  The one-wave replay of a grouped batch increments the count of
+  // every (member, domain) it Reserves.
 };
 // (NS, the template mode of every kernel that makes a score or key: ke_attach.h)
 // node `node` is in the set of id word `idw` (NS instantiations; every node < 64 * ns_wps is in bounds, the ids
@@ -169,6 +183,22 @@ __device__ __forceinline__ bool st_eval(const SoA& s, const PodTerms& r, int nod
 #pragma unroll
   for (int t = 0; t < POD_TERMS; t++) st_apply(r, t, c[t], &filtered, bonus);
   return filtered;
+}
+// the spread domain terms of pod `p` of the call, whose record is `r` (both wave-uniform), on `node` (NS_DTERMS;
+// node < sd_stride): per used slot the node's domain in the map of the term's group, and the pod's cell of that domain
+// (k_domain_terms wrote the table in an earlier launch on this stream; 512 B a pod, so the gathers stay in the cache).
+// Returns whether a filter term closes the node; *bonus = what the score terms add to a feasible total
+__device__ __forceinline__ bool dt_eval(const SoA& s, const PodTerms& r, int p, int node, int32_t* bonus) {
+  bool closed = false;
+  *bonus = 0;
+#pragma unroll
+  for (int t = 0; t < POD_TERMS; t++) {
+    if (!st_kind(r, t)) continue;  // (a wave-uniform test: an unused slot costs no load)
+    const uint32_t d = s.sd_map[(int64_t)s.sd_par[st_group(r, t)].map * s.sd_stride + node];
+    const uint16_t cell = d < 64u ? s.dt_tbl[((int64_t)p * POD_TERMS + t) * 64 + d] : (uint16_t)0;
+    dt_apply(r, t, d, cell, &closed, bonus);
+  }
+  return closed;
 }
 // a fresh key of (pod with set `sid`, node): 0 (filtered) outside the set
 template <int NS>
@@ -3326,18 +3356,47 @@ struct BatchOut {
 // max_skew no count reaches) gives all ones.  Launched on the stream of the eval that reads the masks, ahead of it and
 // behind the previous batch's Reserves, whose increments it sees at the kernel boundary; the counts of a group do not
 // change while a batch with a pod of it runs (one pod of a group per batch, ke_plan.h).
+// lane d of a whole wave: domain d is open to a pod of the group with parameters `gp`, whose count there is `cnt`
+__device__ __forceinline__ bool sd_open(const SdGroup& gp, uint32_t cnt, int lane) {
+  const bool in = (gp.domains >> lane) & 1ull;
+  // (min = ~max(~x); counts stay below 2^31, so count + 1 - min does not wrap)
+  uint32_t mn = ~wave_max_u32(in ? ~cnt : 0u);
+  if ((int)__popcll(gp.domains) < gp.min_domains) mn = 0;
+  return in && (int64_t)cnt + 1 - (int64_t)mn <= (int64_t)gp.max_skew;
+}
 __global__ __launch_bounds__(64) void k_domain_masks(SoA s, int base, int n) {
   if ((int)blockIdx.x >= n) return;
   const int p = base + (int)blockIdx.x, lane = threadIdx.x;
   const int g = s.sd_ids[p];
   const SdGroup gp = s.sd_par[g];
   const uint32_t cnt = ld_sc1(s.sd_cnt + (int64_t)g * 64 + lane);
-  const bool in = (gp.domains >> lane) & 1ull;
-  // (min = ~max(~x); counts stay below 2^31, so count + 1 - min does not wrap)
-  uint32_t mn = ~wave_max_u32(in ? ~cnt : 0u);
-  if ((int)__popcll(gp.domains) < gp.min_domains) mn = 0;
-  const uint64_t open = __ballot(in && (int64_t)cnt + 1 - (int64_t)mn <= (int64_t)gp.max_skew);
+  const uint64_t open = __ballot(sd_open(gp, cnt, lane));
   if (lane == 0) s.sd_mask[p] = open;
+}
+
+// Spread domain terms, k_domain_masks generalised: the per-slot, per-domain table of pods
+// [base, base + n) of the call, one wave a pod, lane = domain.  Per used slot lane d loads count[g][d] of the term's
+// group g and writes the pod's cell of (slot, d) (dt_cell: DT_CLOSED, or the slot's bonus there); SKEW takes
+// sd_open's wave minimum, the other kinds are lane-local.  An unused slot's cells are 0.  Launched where
+// k_domain_masks is: on the stream of the eval that reads the table, ahead of it and behind the previous batch's
+// Reserves; the counts of a group a pod of the batch reads do not change while the batch runs (ke_plan.h's cut rule).
+// (a template only so that the compiler emits it where it is first named: the end of this file)
+template <int = 0>
+__global__ __launch_bounds__(64) void k_domain_terms(SoA s, int base, int n) {
+  if ((int)blockIdx.x >= n) return;
+  const int p = base + (int)blockIdx.x, lane = threadIdx.x;
+  const PodTerms r = s.dt_rec[p];
+#pragma unroll
+  for (int t = 0; t < POD_TERMS; t++) {
+    uint16_t v = 0;
+    if (st_kind(r, t)) {  // (wave-uniform)
+      const int g = st_group(r, t);
+      const uint32_t cnt = ld_sc1(s.sd_cnt + (int64_t)g * 64 + lane);
+      const bool open = st_kind(r, t) == ST_SKEW ? sd_open(s.sd_par[g], cnt, lane) : true;
+      v = dt_cell(r, t, cnt, open);
+    }
+    s.dt_tbl[((int64_t)p * POD_TERMS + t) * 64 + lane] = v;
+  }
 }
 
 // The classification ke_eval and ke_diagnose share, of (pod p, node i) in the first pass: the pod's node set ahead of
@@ -3356,12 +3415,17 @@ __device__ __forceinline__ EvalOut classify_pair(const SoA& s, const NodeRegs& n
   if constexpr (NS >= NS_GROUPS) out_of_set = out_of_set || sg_capped(s, s.sg_ids[p], i);
   // NS_DOMAINS: so does a node whose domain is closed to the pod's spread domain group (64 consecutive domain ids of a
   // wave-uniform map row against the pod's mask)
-  if constexpr (NS >= NS_DOMAINS) out_of_set = out_of_set || !sd_ok(s, p, i);
+  if constexpr (ns_sd(NS)) out_of_set = out_of_set || !sd_ok(s, p, i);
   // NS_TERMS: and a node one of the pod's filter terms closes (the score terms are k_parity_finalize's; per term the
   // lanes read 64 consecutive counts of a wave-uniform row)
-  if constexpr (NS == NS_TERMS) {
+  if constexpr (NS >= NS_TERMS) {
     int32_t bonus;
     out_of_set = st_eval(s, s.st_rec[p], i, &bonus) || out_of_set;
+  }
+  // NS_DTERMS: and a node one of the pod's domain filter terms closes (the pod's table against the node's domains)
+  if constexpr (NS == NS_DTERMS) {
+    int32_t bonus;
+    out_of_set = dt_eval(s, s.dt_rec[p], p, i, &bonus) || out_of_set;
   }
   if (out_of_set) {
     EvalOut o;
@@ -3546,7 +3610,8 @@ __device__ __forceinline__ int32_t ds_norm(int32_t raw, uint32_t dsmax1) {
 // total here, after the normalisation and for the pairs the NUMA deferral finished too, ahead of the key
 // TRM: it carries spread term records (SoA::st_rec, NS_TERMS): a feasible pair's bonus goes in with the offset (a pair
 // a filter term closes has total -1 from classify_pair)
-template <bool SC = false, bool TRM = false>
+// DTR: it carries spread domain term records (SoA::dt_rec, NS_DTERMS): their bonus likewise
+template <bool SC = false, bool TRM = false, bool DTR = false>
 __global__ __launch_bounds__(EVAL_BLOCK) void k_parity_finalize(int n_nodes, KArgs k, const int16_t* ds,
                                                                 int16_t* total, const uint32_t* dsmax,
                                                                 uint32_t* best_key, SoA s) {
@@ -3562,6 +3627,11 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_parity_finalize(int n_nodes, KAr
       if constexpr (TRM) {
         int32_t bonus;
         st_eval(s, s.st_rec[p], i, &bonus);
+        t += bonus;
+      }
+      if constexpr (DTR) {
+        int32_t bonus;
+        dt_eval(s, s.dt_rec[p], p, i, &bonus);
         t += bonus;
       }
       total[o] = (int16_t)t;
@@ -3615,10 +3685,15 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_batch(SoA s, int lo, int hi
       if (NS && !ns_ok<NS>(s, s.ns_ids[base + p], i)) tot = -1;  // (wave-uniform word address)
       if constexpr (NS >= NS_SCORES) tot = tot >= 0 ? tot + ns_off<NS>(s, s.ns_ids[base + p], i) : tot;
       if constexpr (NS >= NS_GROUPS) tot = sg_capped(s, s.sg_ids[base + p], i) ? -1 : tot;  // (wave-uniform row)
-      if constexpr (NS >= NS_DOMAINS) tot = sd_ok(s, base + p, i) ? tot : -1;  // (wave-uniform map row and mask)
-      if constexpr (NS == NS_TERMS) {  // (wave-uniform record and rows)
+      if constexpr (ns_sd(NS)) tot = sd_ok(s, base + p, i) ? tot : -1;  // (wave-uniform map row and mask)
+      if constexpr (NS >= NS_TERMS) {  // (wave-uniform record and rows)
         int32_t bonus;
         const bool closed = st_eval(s, s.st_rec[base + p], i, &bonus);
+        tot = closed ? -1 : tot >= 0 ? tot + bonus : tot;
+      }
+      if constexpr (NS == NS_DTERMS) {  // (wave-uniform record and table)
+        int32_t bonus;
+        const bool closed = dt_eval(s, s.dt_rec[base + p], base + p, i, &bonus);
         tot = closed ? -1 : tot >= 0 ? tot + bonus : tot;
       }
       scores[(int64_t)p * score_stride + i] = (uint16_t)(tot + 1);
@@ -3696,7 +3771,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
   }
   // NS_DOMAINS: one more reason for bit q -- this lane's node's domain (in the map of pod q's spread domain group: the
   // pods of the group may use different maps) is outside pod q's eligible-domain mask (wave-uniform loads)
-  if constexpr (NS >= NS_DOMAINS) {
+  if constexpr (ns_sd(NS)) {
 #pragma unroll
     for (int q = 0; q < EVAL_PPB; q++)
       if (q < np && i < hi && !sd_ok(s, base + p0 + q, i)) capped |= 1u << q;
@@ -3704,7 +3779,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
   // NS_TERMS: per pod q this lane's node's count for each of the pod's terms (wave-uniform record and rows, coalesced
   // loads); the filter terms are one more reason for bit q, the score terms' bonus joins pod q's offset -- both go
   // into a feasible total before the store, and their sum stays within the key's range (take_node_sets)
-  if constexpr (NS == NS_TERMS) {
+  if constexpr (NS >= NS_TERMS) {
 #pragma unroll
     for (int q = 0; q < EVAL_PPB; q++)
       if (q < np && i < hi) {
@@ -3712,6 +3787,21 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
         if (st_eval(s, s.st_rec[base + p0 + q], i, &bonus)) capped |= 1u << q;
         off[q >> 2] += (uint64_t)(uint32_t)bonus << ((q & 3) * 16);
       }
+  }
+  // NS_DTERMS: the group's tables (k_domain_terms: [pod][slot][64] u16 cells, 4 KB for 8 pods, contiguous and 512-B
+  // aligned), its records and the map of every used slot (0: unused) go to LDS once per block; read behind the barrier
+  __shared__ uint32_t s_dt[NS == NS_DTERMS ? EVAL_PPB * POD_TERMS * 32 : 1];
+  __shared__ PodTerms s_dr[NS == NS_DTERMS ? EVAL_PPB : 1];
+  __shared__ uint8_t s_dm[NS == NS_DTERMS ? EVAL_PPB : 1][POD_TERMS];
+  if constexpr (NS == NS_DTERMS) {
+    const uint32_t* const src = reinterpret_cast<const uint32_t*>(s.dt_tbl + (int64_t)(base + p0) * POD_TERMS * 64);
+    for (int t = threadIdx.x; t < np * POD_TERMS * 32; t += (int)blockDim.x) s_dt[t] = src[t];
+    if ((int)threadIdx.x < np * AttachLayout::TERM_WORDS) {  // a record word a thread; the term words give the maps
+      const int q = threadIdx.x / AttachLayout::TERM_WORDS, w = threadIdx.x % AttachLayout::TERM_WORDS;
+      const uint32_t v = reinterpret_cast<const uint32_t*>(s.dt_rec + base + p0 + q)[w];
+      reinterpret_cast<uint32_t*>(&s_dr[q])[w] = v;
+      if (w < POD_TERMS) s_dm[q][w] = (v >> 16) & 0xffu ? (uint8_t)s.sd_par[v & 0xffffu].map : (uint8_t)0;
+    }
   }
   if ((int)threadIdx.x < 4 * np) {
     const int q = threadIdx.x >> 2, c = threadIdx.x & 3;
@@ -3728,6 +3818,42 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_plain(SoA s, int lo, int hi
   }
   __syncthreads();
   if (i >= hi) return;
+  // NS_DTERMS: this lane's node's domain in each distinct map the group's terms use, read once (coalesced u16 rows; a
+  // byte a map, 0xff = no topology key); per pod and used slot it picks the cell of the pod's table in LDS -- closed is
+  // one more reason for bit q, the bonus joins pod q's offset (wave-uniform q, slot and map throughout)
+  if constexpr (NS == NS_DTERMS) {
+    static_assert(KE_MAX_SPREAD_DOMAIN_MAPS == 8, "a byte a map in one register pair");
+    uint32_t used = 0;
+#pragma unroll
+    for (int q = 0; q < EVAL_PPB; q++)
+#pragma unroll
+      for (int sl = 0; sl < POD_TERMS; sl++)
+        if (q < np) used |= 1u << s_dm[q][sl];
+    uint64_t dom = ~0ull;
+#pragma unroll
+    for (int m = 1; m <= KE_MAX_SPREAD_DOMAIN_MAPS; m++)
+      if ((used >> m) & 1u) {
+        const uint32_t d = s.sd_map[(int64_t)m * s.sd_stride + i];
+        dom = (dom & ~(0xffull << (8 * (m - 1)))) | ((uint64_t)(d < 64u ? d : 0xffu) << (8 * (m - 1)));
+      }
+    const uint16_t* const cells = reinterpret_cast<const uint16_t*>(s_dt);
+#pragma unroll
+    for (int q = 0; q < EVAL_PPB; q++)
+      if (q < np) {
+        bool closed = false;
+        int32_t bonus = 0;
+#pragma unroll
+        for (int sl = 0; sl < POD_TERMS; sl++) {
+          const int m = s_dm[q][sl];
+          if (!m) continue;
+          const uint32_t d = (uint32_t)(dom >> (8 * (m - 1))) & 0xffu;
+          const uint16_t cell = d < 64u ? cells[(q * POD_TERMS + sl) * 64 + d] : (uint16_t)0;
+          dt_apply(s_dr[q], sl, d, cell, &closed, &bonus);
+        }
+        if (closed) capped |= 1u << q;
+        off[q >> 2] += (uint64_t)(uint32_t)bonus << ((q & 3) * 16);
+      }
+  }
   NodeFast f;
   rec_load_plain(s.rec + (int64_t)i * NUM_RW, f);
   if (EXT && (k.flags & AF_EXT)) ext_load(s, i, k, f);
@@ -5901,7 +6027,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
   int dgid = 0, dmap = 0;
   uint64_t dmask = ~0ull;
   uint32_t ddom = 0;
-  if constexpr (NS >= NS_DOMAINS) {
+  if constexpr (ns_sd(NS)) {
     dgid = s.sd_ids[base];
     dmap = s.sd_par[dgid].map;
     dmask = s.sd_mask[base];
@@ -5909,7 +6035,13 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
   // NS_TERMS: pod j's record (wave-uniform) and this lane's node's counts for its terms (lane < n_chg)
   PodTerms tr = {};
   uint32_t tc[POD_TERMS] = {0u, 0u, 0u, 0u};
-  if constexpr (NS == NS_TERMS) tr = s.st_rec[base];
+  if constexpr (NS >= NS_TERMS) tr = s.st_rec[base];
+  // NS_DTERMS: pod j's domain term record (wave-uniform: its members), and what pod j's table says of this lane's node
+  // (lane < n_chg; no node is changed at j = 0)
+  PodTerms dr = {};
+  bool dclosed = false;
+  int32_t dbonus = 0;
+  if constexpr (NS == NS_DTERMS) dr = s.dt_rec[base];
   RPROF_DECL
   for (int j = 0; j < B; j++) {
     const bool more = j + 1 < B;
@@ -5923,13 +6055,15 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
     }
     int dgid_n = 0, dmap_n = 0;
     uint64_t dmask_n = ~0ull;
-    if constexpr (NS >= NS_DOMAINS) {
+    if constexpr (ns_sd(NS)) {
       dgid_n = s.sd_ids[base + jn];
       dmap_n = s.sd_par[dgid_n].map;
       dmask_n = s.sd_mask[base + jn];
     }
     PodTerms tr_n = {};
-    if constexpr (NS == NS_TERMS) tr_n = s.st_rec[base + jn];
+    if constexpr (NS >= NS_TERMS) tr_n = s.st_rec[base + jn];
+    PodTerms dr_n = {};
+    if constexpr (NS == NS_DTERMS) dr_n = s.dt_rec[base + jn];
     const double pdd_n[4] = {L.pd[jn][0], L.pd[jn][1], L.pd[jn][2], L.pd[jn][3]};
     const double estd[2] = {pdd[0], pdd[1]}, reqd[2] = {pdd[2], pdd[3]};
     const uint32_t ck_n = more ? s_cand[(j + 1) * KMAX + lane] : 0u;
@@ -5967,16 +6101,21 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
         tot = fast_total<EXT>(fast, pod, estd, reqd, k);
       }
       bool closed = false;  // NS_TERMS: a filter term of pod j closes this node at its current counts
-      if constexpr (NS == NS_TERMS) {
+      if constexpr (NS >= NS_TERMS) {
         int32_t bonus = 0;
 #pragma unroll
         for (int t = 0; t < POD_TERMS; t++) st_apply(tr, t, tc[t], &closed, &bonus);
         tot = tot >= 0 ? tot + bonus : tot;
       }
+      // NS_DTERMS: pod j's table is the batch's snapshot's, so a changed node takes what an unchanged one took
+      if constexpr (NS == NS_DTERMS) {
+        closed = closed || dclosed;
+        tot = tot >= 0 ? tot + dbonus : tot;
+      }
       kc = ns_mkkey<NS>(s, nsid_of<NS>(L, j), my_node, tot);
-      if constexpr (NS == NS_TERMS) kc = closed ? 0u : kc;
+      if constexpr (NS >= NS_TERMS) kc = closed ? 0u : kc;
       if constexpr (NS >= NS_GROUPS) kc = gcnt >= gcap ? 0u : kc;  // the group is at its cap on this node now
-      if constexpr (NS >= NS_DOMAINS) kc = ddom < 64u && ((dmask >> ddom) & 1ull) ? kc : 0u;  // the domain is closed to pod j
+      if constexpr (ns_sd(NS)) kc = ddom < 64u && ((dmask >> ddom) & 1ull) ? kc : 0u;  // the domain is closed to pod j
     }
     RPROF(2)
     const uint32_t bc = wave_max_u32(kc);
@@ -6056,7 +6195,20 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
             st_sc1(cnt, (uint16_t)(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1));
           }
         }
-        if constexpr (NS == NS_TERMS) {  // every member's count on this node, saturating (plain vector stores)
+        if constexpr (NS == NS_DTERMS) {
+          // every domain member's count of this node's domain in the member's map.  Two pods of the batch may hit one
+          // (group, domain) cell from different owner lanes: a relaxed agent-scope vector atomic add.  No pod of the
+          // batch reads a cell the batch writes (the cut rule); the next batch's k_domain_terms does, at a kernel boundary
+#pragma unroll
+          for (int m = 0; m < POD_MEMBERS; m++) {
+            const int g = st_member(dr, m);
+            if (g) {
+              const uint32_t dm = s.sd_map[(int64_t)s.sd_par[g].map * s.sd_stride + my_node];
+              if (dm < 64u) __hip_atomic_fetch_add(s.sd_cnt + (int64_t)g * 64 + dm, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+          }
+        }
+        if constexpr (NS >= NS_TERMS) {  // every member's count on this node, saturating (plain vector stores)
 #pragma unroll
           for (int m = 0; m < POD_MEMBERS; m++) {
             const int g = st_member(tr, m);
@@ -6067,7 +6219,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
             }
           }
         }
-        if constexpr (NS >= NS_DOMAINS) {  // the spread domain group's count of this node's domain (a winner's is open)
+        if constexpr (ns_sd(NS)) {  // the spread domain group's count of this node's domain (a winner's is open)
           if (dgid) {
             const uint32_t d = s.sd_map[(int64_t)dmap * s.sd_stride + my_node];
             uint32_t* const cnt = s.sd_cnt + (int64_t)dgid * 64 + d;
@@ -6123,13 +6275,18 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
       gid = gid_n;
       gcap = gcap_n;
     }
-    if constexpr (NS >= NS_DOMAINS) {  // this lane's node's domain in the map of pod j+1's group
+    if constexpr (ns_sd(NS)) {  // this lane's node's domain in the map of pod j+1's group
       ddom = lane < n_chg ? (uint32_t)s.sd_map[(int64_t)dmap_n * s.sd_stride + my_node] : 0u;
       dgid = dgid_n;
       dmap = dmap_n;
       dmask = dmask_n;
     }
-    if constexpr (NS == NS_TERMS) {  // this lane's node's counts for pod j+1's terms, behind pod j's increments
+    if constexpr (NS == NS_DTERMS) {  // what pod j+1's table says of this lane's node (the new owner's included)
+      dclosed = false, dbonus = 0;
+      if (lane < n_chg) dclosed = dt_eval(s, dr_n, base + jn, my_node, &dbonus);  // (the record fetched a pod ahead)
+      dr = dr_n;
+    }
+    if constexpr (NS >= NS_TERMS) {  // this lane's node's counts for pod j+1's terms, behind pod j's increments
 #pragma unroll
       for (int t = 0; t < POD_TERMS; t++)
         tc[t] = lane < n_chg && st_kind(tr_n, t) ? __hip_atomic_load(s.sg_cnt + (int64_t)st_group(tr_n, t) * s.sg_stride + my_node,
@@ -7392,6 +7549,7 @@ struct CallBufs {
   DevBuf<int32_t> d_sched;       // ke_schedule bookkeeping (SchedLayout): hand-off flags, the T helpers' lists
   PinnedVec<uint8_t> h_out;      // the read-back staging (HostOutLayout)
   DevBuf<uint64_t> d_sd_mask;    // [n_pods] eligible-domain masks of a call with spread domain ids (k_domain_masks)
+  DevBuf<uint16_t> d_dt_tbl;     // [n_pods][POD_TERMS][64] cells of a call with spread domain term lists (k_domain_terms)
   std::vector<hipEvent_t> tev;   // the call's events (pool): span, the call's end per stream, samples
 };
 
@@ -8188,9 +8346,14 @@ static int id_tables_sync(Context* ctx, int ns) {
   if (ns >= NS_DOMAINS) RC_OK(spread_domains_sync(ctx));  // (NS_TERMS without domain groups: row 0 alone)
   return KE_OK;
 }
-// the eligible-domain masks of pods [base, base + n) of a call with spread domain ids, on stream `st`
-static void launch_domain_masks(DeviceState* d, int base, int n, hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(k_domain_masks, dim3((unsigned)n), dim3(64), 0, st, d->soa, base, n);
+// the eligible-domain masks of pods [base, base + n) of a call with spread domain ids, on stream `st`; of a call with
+// spread domain term lists (ns == NS_DTERMS) the pods' per-domain tables instead
+using DomainTablesFn = decltype(&k_domain_masks);
+static DomainTablesFn pick_domain_terms();  // (with the NS_DTERMS instantiations, at the end of this file)
+static void launch_domain_tables(DeviceState* d, int ns, int base, int n, hipStream_t st) {
+  if (n <= 0) return;
+  if (ns == NS_DTERMS) hipLaunchKernelGGL(pick_domain_terms(), dim3((unsigned)n), dim3(64), 0, st, d->soa, base, n);
+  else hipLaunchKernelGGL(k_domain_masks, dim3((unsigned)n), dim3(64), 0, st, d->soa, base, n);
 }
 
 // The call's upload block: the DevPod records, the staging block `lay` of the call's attachments and
@@ -8236,14 +8399,21 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, const A
   d->soa.sg_ids = section(lay.groups, a.groups);
   d->soa.sd_ids = section(lay.domains, a.domains);
   d->soa.sd_mask = nullptr;
-  if (lay.domains >= 0) {
+  if (lay.domains >= 0 && lay.dterms < 0) {  // (a call with domain lists has no masks: dt_tbl takes the word, below)
     RC_OK(d->call.d_sd_mask.reserve((size_t)std::max<int32_t>(n_pods, 1)));
     d->soa.sd_mask = d->call.d_sd_mask;
   }
   d->soa.st_rec = nullptr;
   if (lay.terms >= 0) {
-    std::memcpy(h_words + lay.terms, a.terms, sizeof(PodTerms) * (size_t)n_pods);
+    if (a.terms) std::memcpy(h_words + lay.terms, a.terms, sizeof(PodTerms) * (size_t)n_pods);
+    else std::memset(h_words + lay.terms, 0, sizeof(PodTerms) * (size_t)n_pods);  // (a call with domain lists alone)
     d->soa.st_rec = reinterpret_cast<const PodTerms*>(d_words + lay.terms);
+  }
+  if (lay.dterms >= 0) {  // (in sd_ids' and sd_mask's words: the call's domain id section is all zero and unread)
+    std::memcpy(h_words + lay.dterms, a.dterms, sizeof(PodTerms) * (size_t)n_pods);
+    d->soa.dt_rec = reinterpret_cast<const PodTerms*>(d_words + lay.dterms);
+    RC_OK(d->call.d_dt_tbl.reserve((size_t)std::max<int32_t>(n_pods, 1) * POD_TERMS * 64));
+    d->soa.dt_tbl = d->call.d_dt_tbl;
   }
   d->soa.ns_ids = nullptr;
   if (lay.ids >= 0) {
@@ -8273,6 +8443,10 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, const A
 // exist is written here and nowhere else: a launch site names the family and passes flags.  A combination without
 // an instantiation gives nullptr (the launch site fails with KE_ERR_DEVICE), never a neighbouring kernel; ke_capi.cpp
 // (take_node_sets) refuses those calls first, so none arrives.  Each function is a few compares and a pointer.
+// The NS_DTERMS instantiations are named by the *_dterms functions at the end of this file and nowhere
+// else.  The compiler emits kernels in the order their instantiations are first named, so every kernel that existed
+// before them keeps its place and its address in the code object: a call without domain lists runs the same code at the
+// same addresses as before.
 #define KV(c) decltype(c)::value
 template <class F>
 static auto with_bool(bool v, F&& f) {
@@ -8304,7 +8478,9 @@ static auto with_nsg_ext(int ns, bool ext, F&& f) {
 
 // NUMA x CPU x NS
 using EvalParityFn = decltype(&k_eval_parity<false, false>);
+static EvalParityFn pick_eval_parity_dterms(bool numa, bool cpu);
 static EvalParityFn pick_eval_parity(bool numa, bool cpu, int ns) {
+  if (ns == NS_DTERMS) return pick_eval_parity_dterms(numa, cpu);
   return with_bool(numa, [&](auto NUMA) {
     return with_bool(cpu, [&](auto CPU) -> EvalParityFn {
       if (ns == NS_TERMS) return k_eval_parity<KV(NUMA), KV(CPU), NS_TERMS>;
@@ -8315,7 +8491,10 @@ static EvalParityFn pick_eval_parity(bool numa, bool cpu, int ns) {
     });
   });
 }
-static auto pick_parity_finalize(int ns) {
+using ParityFinalizeFn = decltype(&k_parity_finalize<false>);
+static ParityFinalizeFn pick_parity_finalize_dterms();
+static ParityFinalizeFn pick_parity_finalize(int ns) {
+  if (ns == NS_DTERMS) return pick_parity_finalize_dterms();
   if (ns == NS_TERMS) return k_parity_finalize<true, true>;
   return with_bool(ns >= NS_SCORES, [](auto SC) { return k_parity_finalize<KV(SC)>; });
 }
@@ -8323,7 +8502,9 @@ static auto pick_parity_finalize(int ns) {
 // hinted pod without a DeviceShare request is evaluated without it, as a plain pod is).  EXT is the plain
 // instantiation's alone: eval_pair reads AF_EXT at run time.
 using EvalBatchFn = decltype(&k_eval_batch<false, false, false>);
+static EvalBatchFn pick_eval_batch_dterms(bool ext);
 static EvalBatchFn pick_eval_batch(bool ds, bool numa, bool cpu, bool hint, bool ext, int ns) {
+  if (!ds && !numa && !cpu && ns == NS_DTERMS) return pick_eval_batch_dterms(ext);
   if (!ds && !numa && !cpu)
     return with_nsg_ext(ns, ext, [](auto NS, auto EXT) -> EvalBatchFn {
       return k_eval_batch<false, false, false, KV(EXT), false, KV(NS)>;
@@ -8336,7 +8517,10 @@ static EvalBatchFn pick_eval_batch(bool ds, bool numa, bool cpu, bool hint, bool
     });
   });
 }
-static auto pick_eval_plain(bool ext, int ns) {
+using EvalPlainFn = decltype(&k_eval_plain<false>);
+static EvalPlainFn pick_eval_plain_dterms(bool ext);
+static EvalPlainFn pick_eval_plain(bool ext, int ns) {
+  if (ns == NS_DTERMS) return pick_eval_plain_dterms(ext);
   return with_nsg_ext(ns, ext, [](auto NS, auto EXT) { return k_eval_plain<KV(EXT), KV(NS)>; });
 }
 static auto pick_patch(bool ext, int ns) {
@@ -8353,7 +8537,9 @@ static auto pick_fixlist(bool ext, bool parts, int ns) {
 }
 // DS x NUMA x QUOTA, and NS for the plain instantiation
 using ResolveFn = decltype(&k_resolve<false, false, false>);
+static ResolveFn pick_resolve_dterms();
 static ResolveFn pick_resolve(bool ds, bool numa, bool quota, int ns) {
+  if (!ds && !numa && !quota && ns == NS_DTERMS) return pick_resolve_dterms();
   if (!ds && !numa && !quota)
     return with_nsg_ext(ns, false, [](auto NS, auto) -> ResolveFn { return k_resolve<false, false, false, KV(NS)>; });
   if (ns) return nullptr;
@@ -8384,7 +8570,9 @@ static auto pick_numa_finish(bool cpu) {
 }
 // ke_diagnose: NUMA x CPU x NS (CallAttach::ns_filter: score table ids are not part of a diagnosis)
 using DiagEvalFn = decltype(&k_diag_eval<false, false>);
+static DiagEvalFn pick_diag_eval_dterms(bool numa, bool cpu);
 static DiagEvalFn pick_diag_eval(bool numa, bool cpu, int ns) {
+  if (ns == NS_DTERMS) return pick_diag_eval_dterms(numa, cpu);
   return with_bool(numa, [&](auto NUMA) {
     return with_bool(cpu, [&](auto CPU) -> DiagEvalFn {
       if (ns == NS_TERMS) return k_diag_eval<KV(NUMA), KV(CPU), NS_TERMS>;
@@ -8445,7 +8633,7 @@ static int pair_pass_begin(Context* ctx, int32_t n_pods, const ke_pod* pods, int
   if (rc || n_pods == 0) return rc;
   if ((rc = id_tables_sync(ctx, ns))) return rc;
   if ((rc = upload_pods(ctx, n_pods, pods, AttachLayout(ctx->att, n_pods)))) return rc;
-  if (ns >= NS_DOMAINS) launch_domain_masks(d, 0, n_pods, d->stream);  // (ke_eval / ke_diagnose: one wave per pod of the call)
+  if (ns >= NS_DOMAINS) launch_domain_tables(d, ns, 0, n_pods, d->stream);  // (ke_eval / ke_diagnose: one wave per pod of the call)
   HIP_OK(hipMemsetAsync(d->soa.kerr, 0, sizeof(int32_t), d->stream));
   pp->k = make_kargs(ctx, now);
   for (const DevPod& q : d->call.host_pods) pp->cpu = pp->cpu || (q.flags & PF_CPUSET);
@@ -8824,7 +9012,7 @@ struct ScheduleCall {
     knob = select_knob(std::getenv("KOORDEVAL_SELECT_PARTS"));
     ctx->last_ds_cuts = 0;
     batches = plan_batches(c.host_pods.data(), n_pods, ctx->cfg.pod_batch, !sharded && !numa && N > 0, fused,
-                           att.plan_groups(), att.plan_domains());
+                           att.plan_groups(), att.plan_domains(), att.plan_dterms());
     for (const Batch& b : batches) any_cpu = any_cpu || b.cpu;
     if (any_cpu && !d->has(ST_CPU)) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
     n_batches = (int)batches.size();
@@ -9051,7 +9239,7 @@ struct ScheduleCall {
     const DeferBufs df{defer.list, defer.fb, numa ? defer.cnt + b : nullptr};  // (the batch's own counter)
     // a grouped batch of a call with spread domain ids: its pods' eligible-domain masks from the counts as the previous
     // batch's Reserves left them (a serial batch: this stream ran them)
-    if (batch_ns(b) >= NS_DOMAINS) launch_domain_masks(d, bases[b], bp, a.es);
+    if (batch_ns(b) >= NS_DOMAINS) launch_domain_tables(d, batch_ns(b), bases[b], bp, a.es);
     if (plain_rec) {  // plain batch: the record-based evaluation
       hipLaunchKernelGGL(pick_eval_plain(ext, batch_ns(b)), grid, dim3(blk), 0, a.es, d->soa, lo, hi, c.d_pods, bbase, bp, k,
                          eb.scores, d->capacity, stamp, dwait, d_err);
@@ -9539,6 +9727,23 @@ int device_debug_rows(Context* ctx, int32_t n, Row* out) {
   HIP_OK(hipMemcpyAsync(out, tmp, sizeof(Row) * n, hipMemcpyDeviceToHost, d->stream));
   HIP_OK(hipStreamSynchronize(d->stream));
   return KE_OK;
+}
+
+// ---- the NS_DTERMS instantiations (the dispatcher above says why they are named here) -----------------
+static DomainTablesFn pick_domain_terms() { return k_domain_terms<>; }
+static EvalParityFn pick_eval_parity_dterms(bool numa, bool cpu) {
+  if (numa) return cpu ? k_eval_parity<true, true, NS_DTERMS> : k_eval_parity<true, false, NS_DTERMS>;
+  return cpu ? k_eval_parity<false, true, NS_DTERMS> : k_eval_parity<false, false, NS_DTERMS>;
+}
+static ParityFinalizeFn pick_parity_finalize_dterms() { return k_parity_finalize<true, true, true>; }
+static EvalBatchFn pick_eval_batch_dterms(bool ext) {
+  return ext ? k_eval_batch<false, false, false, true, false, NS_DTERMS> : k_eval_batch<false, false, false, false, false, NS_DTERMS>;
+}
+static EvalPlainFn pick_eval_plain_dterms(bool ext) { return ext ? k_eval_plain<true, NS_DTERMS> : k_eval_plain<false, NS_DTERMS>; }
+static ResolveFn pick_resolve_dterms() { return k_resolve<false, false, false, NS_DTERMS>; }
+static DiagEvalFn pick_diag_eval_dterms(bool numa, bool cpu) {
+  if (numa) return cpu ? k_diag_eval<true, true, NS_DTERMS> : k_diag_eval<true, false, NS_DTERMS>;
+  return cpu ? k_diag_eval<false, true, NS_DTERMS> : k_diag_eval<false, false, NS_DTERMS>;
 }
 
 }  // namespace ke

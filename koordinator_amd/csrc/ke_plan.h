@@ -88,9 +88,23 @@ struct Batch {
 // of any spread domain group -- it ends before a pod whose non-zero id already occurs in it, so the group's domain
 // counts during the batch are those of the batch's snapshot -- and a batch holding such a pod is `grouped` too.  With
 // every id zero the plan is the one without them.
+// `dterms` (the call's spread domain term record per pod; nullptr: none): a batch ends before a pod one
+// of whose term groups is a member group of an earlier pod of that batch, so every group a pod reads keeps its snapshot
+// counts for the whole batch (reads after reads, writes after writes and writes after reads share a batch).  The
+// `grouped` mark of such a batch comes with `group_ids`.  With every record empty the plan is the one without them.
 inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bool ds_batch, bool fused,
-                                       const int32_t* group_ids = nullptr, const int32_t* domain_ids = nullptr) {
+                                       const int32_t* group_ids = nullptr, const int32_t* domain_ids = nullptr,
+                                       const PodTerms* dterms = nullptr) {
   std::vector<Batch> batches;
+  // pod p0 + bp reads a spread domain group that one of the bp pods from p0 on is a member of
+  auto reads_written = [&](int p0, int bp) {  // (called with domain lists only)
+    const PodTerms& r = dterms[p0 + bp];
+    for (int t = 0; t < POD_TERMS && st_kind(r, t); t++)
+      for (int q = 0; q < bp; q++)
+        for (int m = 0; m < POD_MEMBERS; m++)
+          if (st_member(dterms[p0 + q], m) == st_group(r, t)) return true;
+    return false;
+  };
   // pod p0 + bp names a spread domain group that one of the bp pods from p0 on names already
   auto repeats = [&](int p0, int bp) {
     const int32_t id = domain_ids ? domain_ids[p0 + bp] : 0;
@@ -110,7 +124,7 @@ inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bo
     int bp = 0;
     bool has_ds = false;
     while (p + bp < n_pods && bp < B && !(fused && p + bp == n_pods - 1) && !alone(pods[p + bp].flags) &&
-           !repeats(p, bp)) {
+           !repeats(p, bp) && (!dterms || !reads_written(p, bp))) {
       has_ds = has_ds || (pods[p + bp].flags & PF_DS);
       bp++;
     }

@@ -488,4 +488,28 @@ KE_HD inline void st_apply(const PodTerms& r, int t, uint32_t c, bool* filtered,
   else if (kind == ST_PREFER_MORE) *bonus += st_weight(r, t) * (int32_t)cl;
 }
 
+// Spread domain terms (ke_pod_spread_domain_terms): the same record over the spread domain tables, with
+// one more kind.  A term's group is a spread domain group, `c` the count of a node's domain in the group's map.
+constexpr int ST_SKEW = 5;  // == KE_TERM_SKEW: §4s's filter with the group's domains / max_skew / min_domains
+constexpr uint16_t DT_CLOSED = 0xFFFF;
+// The cell of term t for a domain whose count is `c` (k_domain_terms' table, one per pod, slot and domain): DT_CLOSED
+// where a filter term closes the domain, else what a score term adds.  `skew_open`: §4s's test of the domain, read by
+// SKEW alone.  The other kinds are st_apply's arithmetic on the domain's count.
+KE_HD inline uint16_t dt_cell(const PodTerms& r, int t, uint32_t c, bool skew_open) {
+  if (st_kind(r, t) == ST_SKEW) return skew_open ? (uint16_t)0 : DT_CLOSED;
+  bool closed = false;
+  int32_t bonus = 0;
+  st_apply(r, t, c, &closed, &bonus);
+  return closed ? DT_CLOSED : (uint16_t)(bonus < 0xFFFE ? bonus : 0xFFFE);  // (an admitted call's bonus is below 1022)
+}
+// What term t does on a node whose domain in the term's map is `dom`, with the cell of that domain: a node without the
+// topology key (dom >= 64, KE_DOMAIN_NONE) is closed to SKEW and AFFINITY, open to ANTI, and takes no bonus.
+KE_HD inline void dt_apply(const PodTerms& r, int t, uint32_t dom, uint16_t cell, bool* closed, int32_t* bonus) {
+  const int kind = st_kind(r, t);
+  if (!kind) return;
+  if (dom >= 64u) *closed = *closed || kind == ST_SKEW || kind == ST_AFFINITY;
+  else if (cell == DT_CLOSED) *closed = true;
+  else *bonus += (int32_t)cell;
+}
+
 }  // namespace ke

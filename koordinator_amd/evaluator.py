@@ -384,6 +384,19 @@ class Evaluator:
         kind, param) for abi.TERM_ANTI / TERM_AFFINITY, (group, kind, param, weight) for TERM_PREFER_FEWER /
         TERM_PREFER_MORE -- and a list of member groups, over the spread groups' counts; both lists of a plain pod are
         empty.  Packed here into the entry point's four CSR arrays."""
+        self._check(self.lib.ke_pod_spread_terms(
+            *self._term_lists(terms, members, (3, 4), "a term is (group, kind, param[, weight])")))
+
+    def pod_spread_domain_terms(self, terms, members):
+        """ke_pod_spread_domain_terms: pod_spread_terms' lists over the spread domain groups' counts -- zone-level
+        affinity, anti-affinity and soft spread; besides its four kinds (group, abi.TERM_SKEW) is the group's maxSkew
+        filter.  A placement increments every member's count of the node's domain in the member's map."""
+        self._check(self.lib.ke_pod_spread_domain_terms(
+            *self._term_lists(terms, members, (2, 3, 4), "a term is (group, kind[, param[, weight]])")))
+
+    def _term_lists(self, terms, members, lengths, what):
+        """The arguments of ke_pod_spread_terms / ke_pod_spread_domain_terms: per-pod lists packed into CSR arrays; a
+        term of a length outside `lengths` is a ValueError (`what`)."""
         if len(terms) != len(members):
             raise ValueError("one term list and one member list per pod")
         t_off = np.zeros(len(terms) + 1, np.int32)
@@ -392,15 +405,16 @@ class Evaluator:
         for p, (tl, ml) in enumerate(zip(terms, members)):
             for t in tl:
                 t = tuple(int(v) for v in t)
-                if len(t) not in (3, 4):
-                    raise ValueError("a term is (group, kind, param[, weight])")
-                t_flat.append(t if len(t) == 4 else t + (0,))
+                if len(t) not in lengths:
+                    raise ValueError(what)
+                t_flat.append(t + (0,) * (4 - len(t)))
             m_flat.extend(int(m) for m in ml)
             t_off[p + 1], m_off[p + 1] = len(t_flat), len(m_flat)
         t_arr = np.ascontiguousarray(np.asarray(t_flat, np.int32).reshape(-1, 4))
         m_arr = np.ascontiguousarray(m_flat, np.int32)
-        self._check(self.lib.ke_pod_spread_terms(self.h, len(terms), abi.ptr(t_off), abi.ptr(t_arr) if len(t_arr) else None,
-                                                 abi.ptr(m_off), abi.ptr(m_arr) if len(m_arr) else None))
+        self._lists = (t_off, t_arr, m_off, m_arr)  # (alive through the call)
+        return (self.h, len(terms), abi.ptr(t_off), abi.ptr(t_arr) if len(t_arr) else None, abi.ptr(m_off),
+                abi.ptr(m_arr) if len(m_arr) else None)
 
     def debug_spread_domains_check(self):
         """ke_debug_spread_domains_check: counts and map entries of the device's spread domain tables that differ from
@@ -492,7 +506,7 @@ class Evaluator:
         return lo.value, hi.value
 
     # ---- evaluation -------------------------------------------------------------------------
-    def _stage(self, node_sets, node_scores, spread_groups, spread_domains, spread_terms):
+    def _stage(self, node_sets, node_scores, spread_groups, spread_domains, spread_terms, spread_domain_terms=None):
         """The next call's per-pod attachments: each keyword that is not None goes through its pod_*() staging."""
         if node_sets is not None:
             self.pod_node_sets(node_sets)
@@ -504,15 +518,18 @@ class Evaluator:
             self.pod_spread_domains(spread_domains)
         if spread_terms is not None:
             self.pod_spread_terms(*spread_terms)
+        if spread_domain_terms is not None:
+            self.pod_spread_domain_terms(*spread_domain_terms)
 
     def eval(self, pods, now_ns, node_sets=None, node_scores=None, spread_groups=None, spread_domains=None,
-             spread_terms=None):
+             spread_terms=None, spread_domain_terms=None):
         """ke_eval; `node_sets` (optional): the node set id per pod (0 = every node); `node_scores` (optional): the
         score table id per pod (0 = no offset); `spread_groups` (optional): the spread group id per pod (0 = none);
         `spread_domains` (optional): the spread domain group id per pod (0 = none); `spread_terms` (optional): the
-        pair (terms, members) of pod_spread_terms()."""
+        pair (terms, members) of pod_spread_terms(); `spread_domain_terms` (optional): that of
+        pod_spread_domain_terms()."""
         pods = as_pod_array(pods)
-        self._stage(node_sets, node_scores, spread_groups, spread_domains, spread_terms)
+        self._stage(node_sets, node_scores, spread_groups, spread_domains, spread_terms, spread_domain_terms)
         P, N = len(pods), self.num_nodes
         out = {
             "status": np.zeros((P, N), np.uint8),
@@ -529,14 +546,14 @@ class Evaluator:
         return out
 
     def diagnose(self, pods, now_ns, node_sets=None, bitmaps=False, spread_groups=None, spread_domains=None,
-                 spread_terms=None):
+                 spread_terms=None, spread_domain_terms=None):
         """ke_diagnose: per pod the reductions of eval()'s status / reason over every node, computed on the device
         with nothing per pair copied back -- int32 [P] arrays n_nodes, n_absent, n_feasible, n_unschedulable,
         n_unresolvable, n_error, uint32 [P] plugins (abi.PLUGIN_* bits), int32 [P, 128] reason_nodes; with
         `bitmaps` also the bool [P, N] matrices feasible, unschedulable, unresolvable.  `node_sets`, `spread_groups`,
-        `spread_domains` and `spread_terms` (its filter kinds) as for eval()."""
+        `spread_domains`, `spread_terms` and `spread_domain_terms` (their filter kinds) as for eval()."""
         pods = as_pod_array(pods)
-        self._stage(node_sets, None, spread_groups, spread_domains, spread_terms)
+        self._stage(node_sets, None, spread_groups, spread_domains, spread_terms, spread_domain_terms)
         P, N = len(pods), self.num_nodes
         rec = np.zeros(P, abi.POD_DIAGNOSIS_DTYPE)
         wpp = (N + 63) // 64
@@ -550,16 +567,17 @@ class Evaluator:
         return out
 
     def schedule(self, pods, now_ns, matches=None, node_sets=None, node_scores=None, spread_groups=None,
-                 spread_domains=None, spread_terms=None):
+                 spread_domains=None, spread_terms=None, spread_domain_terms=None):
         """ke_schedule; `matches` (optional): per pod the reservation indices it matches (KE_RSV_MATCHED pods);
         `node_sets` (optional): the node set id per pod (0 = every node); `node_scores` (optional): the score table
         id per pod (0 = no offset); `spread_groups` (optional): the spread group id per pod (0 = none);
         `spread_domains` (optional): the spread domain group id per pod (0 = none); `spread_terms` (optional): the
-        pair (terms, members) of pod_spread_terms()."""
+        pair (terms, members) of pod_spread_terms(); `spread_domain_terms` (optional): that of
+        pod_spread_domain_terms()."""
         pods = as_pod_array(pods)
         if matches is not None:
             self.pod_reservations(matches)
-        self._stage(node_sets, node_scores, spread_groups, spread_domains, spread_terms)
+        self._stage(node_sets, node_scores, spread_groups, spread_domains, spread_terms, spread_domain_terms)
         chosen = np.zeros(len(pods), np.int32)
         score = np.zeros(len(pods), np.int32)
         self._check(self.lib.ke_schedule(self.h, len(pods), abi.ptr(pods), int(now_ns), abi.ptr(chosen), abi.ptr(score)))
@@ -567,12 +585,12 @@ class Evaluator:
         return chosen, score
 
     def submit(self, pods, now_ns, node_sets=None, node_scores=None, spread_groups=None, spread_domains=None,
-               spread_terms=None):
+               spread_terms=None, spread_domain_terms=None):
         """ke_schedule_submit: enqueue a queue slice behind the calls in flight; returns its ticket (wait() collects
         it).  The pod array is kept alive here until then.  `node_sets`, `node_scores`, `spread_groups`,
-        `spread_domains` and `spread_terms` as for schedule()."""
+        `spread_domains`, `spread_terms` and `spread_domain_terms` as for schedule()."""
         pods = as_pod_array(pods)
-        self._stage(node_sets, node_scores, spread_groups, spread_domains, spread_terms)
+        self._stage(node_sets, node_scores, spread_groups, spread_domains, spread_terms, spread_domain_terms)
         t = C.c_int64()
         self._check(self.lib.ke_schedule_submit(self.h, len(pods), abi.ptr(pods), int(now_ns), C.byref(t)))
         self._inflight[t.value] = pods
