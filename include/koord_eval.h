@@ -1176,6 +1176,115 @@ int ke_diagnose(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns,
 const char* ke_reason_message(int32_t reason);  /* the plugin's message, "" for an unknown code; never NULL */
 uint32_t ke_reason_plugin(int32_t reason);      /* KE_PLUGIN_* of a reason, 0 for NONE / unknown */
 
+/* ---- dry-run preemption: ElasticQuota's PostFilter victim selection (additive: KE_ABI_VERSION stays 14) ----
+ * ke_preempt runs, per pending pod, what elasticquota/preempt.go runs per node (SelectVictimsOnNode, :111-215:
+ * remove every potential victim, re-filter, reprieve them one by one) on every node that preemption might help, and
+ * picks one candidate; only the decision comes back.  Each pod is evaluated on its own against the state at the
+ * call: no pod sees another pod's victims, and nothing changes state.
+ *
+ * Resident pods.  Which pods sit on a node is a statement by the caller (the informer's pod add / delete), kept
+ * beside the node rows and never folded into them: the table does not touch Requested, pod_count or any row, a pod
+ * ke_schedule placed is not listed until the caller adds it, and an unlisted pod is simply never a victim.
+ * ke_node_delete drops the node's list.  Each node's list is kept in util.MoreImportantPod order -- priority
+ * descending, then the earlier start_ns first; that upstream helper is outside the reference tree and restated from
+ * the published algorithm (parity-unpinned, as NodeResourcesFit is).  Go's sort.Slice leaves ties unordered: they
+ * are broken by uid ascending, by convention.
+ *  - ke_resident_pods_load replaces the whole table: node i's pods are pods[offsets[i] .. offsets[i+1]), in any
+ *    order; n_nodes <= node_capacity, nodes at and beyond n_nodes have none.
+ *  - More than KE_MAX_RESIDENT_PODS on a node is KE_ERR_UNSUPPORTED (load and add).  A uid listed twice on a node,
+ *    a negative request, a cpu request >= 2^47, a quota outside 0..KE_MAX_QUOTAS, n_pdb > 2, a pdb id of 0 within
+ *    n_pdb or the same id twice are KE_ERR_INVALID; ke_resident_pod_remove of an unknown uid is KE_ERR_NOT_FOUND.
+ *    A refused call changes nothing.
+ *  - pdb[] ids are 1 + the index into the ke_pdbs_load array; an id beyond the loaded array is KE_ERR_INVALID at
+ *    the next ke_preempt.  Matching a PDB's selector and leaving out the PDBs whose Status.DisruptedPods names the
+ *    pod (preempt.go:228-258) are the caller's. */
+#define KE_MAX_RESIDENT_PODS 128   /* per node; more is KE_ERR_UNSUPPORTED at load / add */
+typedef struct ke_resident_pod {
+  int64_t uid;
+  int64_t start_ns;            /* pod.Status.StartTime (util.GetPodStartTime); MoreImportantPod's tie-break */
+  int64_t requests[KE_NRES];   /* resourceapi.PodRequests cpu (milli) / memory: what NodeInfo.RemovePod subtracts */
+  int32_t priority;            /* corev1helpers.PodPriority */
+  int16_t quota;               /* as ke_pod.quota */
+  uint8_t non_preemptible;     /* extension.IsPodNonPreemptible */
+  uint8_t n_pdb;               /* 0..2 */
+  uint16_t pdb[2];             /* 1 + index into ke_pdbs_load of the PDBs whose selector matches and whose
+                                  DisruptedPods does not name the pod (preempt.go:228-258); the caller resolves both */
+} ke_resident_pod;
+int ke_resident_pods_load(ke_ctx* ctx, int32_t n_nodes, const int32_t* offsets /*[n_nodes+1]*/,
+                          const ke_resident_pod* pods);
+int ke_resident_pod_add(ke_ctx* ctx, int32_t node, const ke_resident_pod* pod);
+int ke_resident_pod_remove(ke_ctx* ctx, int32_t node, int64_t uid);
+/* The node's list in its kept order: *n = its length, the first min(*n, cap) records into out (out may be NULL
+ * when cap is 0). */
+int ke_resident_pods_get(ke_ctx* ctx, int32_t node, int32_t cap, ke_resident_pod* out, int32_t* n);
+/* Status.DisruptionsAllowed of every PodDisruptionBudget the resident records name; n <= 65535. */
+int ke_pdbs_load(ke_ctx* ctx, int32_t n, const int32_t* disruptions_allowed);
+
+/* The call.  Per (pod p, populated node i):
+ *  1. The pair is classified exactly as ke_diagnose classifies it (node sets included).  An
+ *     UnschedulableAndUnresolvable or KE_CODE_ERROR node is not tried (n_skipped); every other populated node is,
+ *     feasible ones too (upstream's nodesWherePreemptionMightHelp keeps nodes without a map entry).
+ *  2. Potential victims: the node's listed pods with canPreempt (preempt.go:283-304): not non_preemptible,
+ *     priority < priorities[p], quota == pods[p].quota (as integers, 0 == 0), and not
+ *     (disable_default_quota_preemption and the victim's quota == default_quota).  None: n_no_victims.
+ *  3. All of them removed -- pod_count - 1 and Requested cpu / memory - requests (not below 0) per pod, which is
+ *     all that NodeResourcesFit's Filter reads; LoadAware keeps no per-pod NodeInfo state, so its verdict and every
+ *     other filter's stand as they are on the node -- the pod must pass: every filter other than NodeResourcesFit's
+ *     on the node as it is, and NodeResourcesFit's on the adjusted figures (vacuous without ke_fit_args.filter).
+ *     Otherwise n_unfit.
+ *  4. filterPodsWithPDBViolation (:222-267): the potential victims in list order against per-PDB budgets that
+ *     start at disruptions_allowed for this (pod, node); each listed pdb id takes one, a pod is violating when one
+ *     of its budgets goes below 0.
+ *  5. The reprieve (:175-213), violating victims first, then the others, each group in list order: add the pod
+ *     back; fits = the test of step 3; if it does not fit it is removed and is a victim.  Then, whatever fits was,
+ *     the quota check: used (the quota's used at the call, minus every removed pod's request, plus every
+ *     added-back pod's, masked as plugin.go:294-297,315-318 and never below 0) + the pod's request against the
+ *     used limit on the limit's keys, the comparison ke_schedule's admission makes; quota 0 always passes.  A pod
+ *     that fails it is removed and recorded as a victim.  The reference's double removal is kept: a victim that
+ *     neither fits nor passes the quota check is removed twice, the second NodeInfo.RemovePod errs and the node
+ *     returns an error status (n_error, no candidate).  numViolatingVictim counts the violating victims that did
+ *     not fit.  There is no final quota test, as the reference has none.
+ * The pick among the candidates -- upstream's pickOneNodeForPreemption, outside the reference tree and restated from
+ * the published algorithm (parity-unpinned) -- is, in order: the fewest PDB violations; the lowest highest-victim
+ * priority; the smallest sum of (priority + 2^31 + 1) over the victims; the fewest victims; the latest
+ * earliest-start_ns among the node's highest-priority victims; the lowest node index (the selectHost convention).  A
+ * candidate without victims counts as highest priority -2^31 and start INT64_MAX, so it wins criterion 2.
+ * victim_uids[p * victims_cap ..] holds the picked node's victims in the order the reference appends them (the
+ * first min(n_victims, victims_cap); the rest of the row is 0).  `candidates` (optional) is a bitmap in
+ * ke_diagnose's layout: bit i of row p = node i is a candidate of pod p.
+ *
+ * Admission: preemptors are plain pods -- a cpuset, NUMA-policy, DeviceShare, reservation-matched / ignored /
+ * affinity pod, or one with a non-zero request for a scalar in ke_fit_args.scalars, is KE_ERR_UNSUPPORTED
+ * (NodeNUMAResource's and DeviceShare's own AddPod / RemovePod extensions are not modelled), as are a context with
+ * NUMA topology policy state or CPU bind policy nodes, a node-sharded context, and staged spread group / spread
+ * domain ids or term lists.  The call completes the calls in flight and consumes staged ke_pod_node_sets ids and
+ * ke_pod_node_scores ids (dropped) as ke_diagnose does.  A null out / priorities / victim_uids with n_pods > 0,
+ * victims_cap < 1, a pod quota outside the loaded tree and, with `candidates`, words_per_pod <
+ * ceil(ke_num_nodes/64) are KE_ERR_INVALID; a context without a device is KE_ERR_NO_DEVICE after these checks.
+ * Left to the caller: PodEligibleToPreemptOthers (preempt.go:61-94), nominated pods in
+ * RunFilterPluginsWithNominatedPods, and the eviction itself. */
+typedef struct ke_preempt_args {
+  int16_t default_quota;                    /* 1 + index of the default quota, 0 = none */
+  uint8_t disable_default_quota_preemption; /* ElasticQuotaArgs.DisableDefaultQuotaPreemption (preempt.go:298-301) */
+  uint8_t pad[5];
+} ke_preempt_args;
+typedef struct ke_preemption {
+  int32_t node;             /* the picked candidate, -1 = none */
+  int32_t n_victims;        /* on that node (may exceed victims_cap; the list is then its first victims_cap) */
+  int32_t n_pdb_violations; /* numViolatingVictim of that node */
+  int32_t n_candidates;     /* nodes where SelectVictimsOnNode succeeds */
+  int32_t n_skipped;        /* populated nodes not tried: UnschedulableAndUnresolvable or KE_CODE_ERROR */
+  int32_t n_no_victims;     /* "No victims found on node" (preempt.go:150-153) */
+  int32_t n_unfit;          /* the pod does not pass the filters with every potential victim gone (:161-163) */
+  int32_t n_error;          /* the simulation errs (the double removal) */
+} ke_preemption;            /* n_candidates + n_skipped + n_no_victims + n_unfit + n_error == populated nodes */
+int ke_preempt(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, const int32_t* priorities, int64_t now_ns,
+               const ke_preempt_args* args /* NULL = all zero */, ke_preemption* out, int32_t victims_cap,
+               int64_t* victim_uids, int32_t words_per_pod, uint64_t* candidates);
+/* sizeof of ke_resident_pod, ke_preempt_args, ke_preemption (in that order), as ke_abi_struct_sizes reports the
+ * structs before them; returns their count. */
+int ke_abi_preempt_struct_sizes(int32_t* sizes, int32_t n);
+
 /* NodeInfo.Requested / NonZeroRequested (MilliCPU, Memory) of `node` as the plugins see it for a pod that
  * matches no reservation (after the restore above and the Reserves of past ke_schedule calls). */
 int ke_node_info_requested(ke_ctx* ctx, int32_t node, int64_t* requested /*[2]*/, int64_t* non_zero /*[2]*/);
@@ -1320,8 +1429,9 @@ int ke_unreserve(ke_ctx* ctx, const ke_pod* pod, int32_t queue_pos);
  *    shrinks totalResourceExceptSystemAndDefaultUsed (updateClusterTotalResourceNoLock,
  *    group_quota_manager.go:127-151,268-271) and every later pod of the call sees runtime limits
  *    refreshed from the smaller total.
- * Not modelled: guaranteed usage (feature gate ElasticQuotaGuaranteeUsage, default off), hook plugins, quota-overuse revocation, preemption
- * (PostFilter); a zero-valued pod request counts as an absent key (checkQuotaRecursive masks on
+ * Not modelled: guaranteed usage (feature gate ElasticQuotaGuaranteeUsage, default off), hook plugins, quota-overuse
+ * revocation.  The PostFilter's dry-run victim selection is ke_preempt (below); the eviction stays the caller's.
+ * A zero-valued pod request counts as an absent key (checkQuotaRecursive masks on
  * ResourceNames(PodRequests), which keeps explicit zeros — ke_pod carries values, not key sets).
  * Resources: cpu (milli, getQuantityValue) and memory (bytes).  Values >= 0. */
 #define KE_MAX_QUOTAS 255 /* ke_pod.quota - 1 fits a byte on the device */

@@ -448,6 +448,28 @@ STRUCTS = [Config, Node, NodeMetric, PodMetric, AggregatedUsage, Pod, ResourceMa
            PodAllocation, PodDeviceHints, GpuTemplate, Reservation, ReservationAlloc, ReservationResource,
            PodDiagnosis]
 POD_DIAGNOSIS_DTYPE = np.dtype(PodDiagnosis)
+
+MAX_RESIDENT_PODS = 128  # KE_MAX_RESIDENT_PODS
+
+
+class ResidentPod(C.Structure):  # ke_resident_pod
+    _fields_ = [("uid", i64), ("start_ns", i64), ("requests", i64 * NRES), ("priority", i32), ("quota", C.c_int16),
+                ("non_preemptible", C.c_uint8), ("n_pdb", C.c_uint8), ("pdb", C.c_uint16 * 2)]
+
+
+class PreemptArgs(C.Structure):  # ke_preempt_args
+    _fields_ = [("default_quota", C.c_int16), ("disable_default_quota_preemption", C.c_uint8), ("pad", C.c_uint8 * 5)]
+
+
+class Preemption(C.Structure):  # ke_preemption
+    _fields_ = [("node", i32), ("n_victims", i32), ("n_pdb_violations", i32), ("n_candidates", i32), ("n_skipped", i32),
+                ("n_no_victims", i32), ("n_unfit", i32), ("n_error", i32)]
+
+
+# ke_abi_preempt_struct_sizes' list (ke_abi_struct_sizes' ends with ke_pod_diagnosis and stays as it is)
+PREEMPT_STRUCTS = [ResidentPod, PreemptArgs, Preemption]
+RESIDENT_POD_DTYPE = np.dtype(ResidentPod)
+PREEMPTION_DTYPE = np.dtype(Preemption)
 RESERVATION_DTYPE = np.dtype(Reservation)
 RESERVATION_RESOURCE_DTYPE = np.dtype(ReservationResource)
 RESERVATION_ALLOC_DTYPE = np.dtype(ReservationAlloc)
@@ -557,6 +579,14 @@ EXPORTS = {
     "ke_diagnose": (C.c_int, [C.c_void_p, i32, C.c_void_p, i64, C.c_void_p, i32] + [C.c_void_p] * 3),
     "ke_reason_message": (C.c_char_p, [i32]),
     "ke_reason_plugin": (C.c_uint32, [i32]),
+    "ke_resident_pods_load": (C.c_int, [C.c_void_p, i32, C.c_void_p, C.c_void_p]),
+    "ke_resident_pod_add": (C.c_int, [C.c_void_p, i32, C.c_void_p]),
+    "ke_resident_pod_remove": (C.c_int, [C.c_void_p, i32, i64]),
+    "ke_resident_pods_get": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p, C.POINTER(i32)]),
+    "ke_pdbs_load": (C.c_int, [C.c_void_p, i32, C.c_void_p]),
+    "ke_preempt": (C.c_int, [C.c_void_p, i32, C.c_void_p, C.c_void_p, i64, C.c_void_p, C.c_void_p, i32, C.c_void_p, i32,
+                             C.c_void_p]),
+    "ke_abi_preempt_struct_sizes": (C.c_int, [C.POINTER(i32), i32]),
     "ke_node_devices_set": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
     "ke_node_gpu_partitions": (C.c_int, [C.c_void_p, i32, i32, i32, i32, C.c_void_p]),
     "ke_node_devices_delete": (C.c_int, [C.c_void_p, i32]),
@@ -675,6 +705,12 @@ def load_library(path=LIB_PATH):
     sizes = (i32 * len(STRUCTS))()
     lib.ke_abi_struct_sizes(sizes, len(STRUCTS))
     for s, n in zip(STRUCTS, sizes):
+        if C.sizeof(s) != n:
+            raise RuntimeError(f"ABI layout mismatch for {s.__name__}: python {C.sizeof(s)} != C {n}")
+    sizes = (i32 * len(PREEMPT_STRUCTS))()
+    if lib.ke_abi_preempt_struct_sizes(sizes, len(PREEMPT_STRUCTS)) != len(PREEMPT_STRUCTS):
+        raise RuntimeError("ABI mismatch: the preemption structs' count")
+    for s, n in zip(PREEMPT_STRUCTS, sizes):
         if C.sizeof(s) != n:
             raise RuntimeError(f"ABI layout mismatch for {s.__name__}: python {C.sizeof(s)} != C {n}")
     if path == LIB_PATH:

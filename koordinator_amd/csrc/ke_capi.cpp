@@ -37,6 +37,9 @@ int device_check_records(Context* ctx, int64_t now, int64_t* bad);
 // (weak: a host-only build of this file, without ke_kernels.hip, links without it -- there is no device copy to check)
 int device_spread_groups_check(Context* ctx, int64_t* bad) __attribute__((weak));
 int device_spread_domains_check(Context* ctx, int64_t* bad) __attribute__((weak));
+int device_preempt(Context* ctx, int32_t n_pods, const ke_pod* pods, const PreemptPod* pre, int64_t now, ke_preemption* out,
+                   int32_t victims_cap, int64_t* victim_uids, int32_t words_per_pod, uint64_t* candidates)
+    __attribute__((weak));
 int device_bench_eval(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t now, int32_t iters, double* avg_ms);
 int device_comm_unique_id(uint8_t* id);
 int device_shard_init(Context* ctx, int rank, int world, const uint8_t* id);
@@ -311,6 +314,7 @@ int ke_create(const ke_config* cfg, ke_ctx** out) {
   Context& c = ctx->c;
   c.cfg = *cfg;
   c.nodes.resize((size_t)cfg->node_capacity);
+  c.residents.nodes.resize((size_t)cfg->node_capacity);
   for (int32_t i = 0; i < cfg->node_capacity; i++) c.nodes[(size_t)i].dirty.bind(i, &c.dirty_list);
   KArgs& k = c.kargs_template;
   const ke_loadaware_args& a = cfg->loadaware;
@@ -459,6 +463,7 @@ int ke_node_delete(ke_ctx* ctx, int32_t node) {
   if (ctx) flush_mirror(ctx->c);  // pending Reserves on it first: the object state stays (koord_eval.h)
   if (rc) return rc;
   NodeState& ns = ctx->c.nodes[node];
+  resident_drop(ctx->c.residents, node);  // its resident pods go with it (ke_preempt.h)
   if (!ns.valid) return KE_OK;
   ctx->c.n_bind_nodes -= ns.node.cpu_bind_policy != KE_NODE_CPU_BIND_NONE;
   ctx->c.n_policy_nodes -= ns.node.numa_topology_policy != KE_NUMA_POLICY_NONE;
@@ -1389,6 +1394,115 @@ int ke_diagnose(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns,
 }
 const char* ke_reason_message(int32_t reason) { return diag_reason_message(reason); }
 uint32_t ke_reason_plugin(int32_t reason) { return diag_reason_plugin(reason); }
+
+// ---- resident pods, PDB budgets and ke_preempt (the table logic is ke_preempt.h's) -----------------------
+int ke_resident_pods_load(ke_ctx* ctx, int32_t n_nodes, const int32_t* offsets, const ke_resident_pod* pods) {
+  if (ctx) async_drain(ctx);
+  if (!ctx) return fail(KE_ERR_INVALID, "null context");
+  const char* why = "";
+  const int rc = resident_load(ctx->c.residents, n_nodes, offsets, pods, &why);
+  return rc ? fail(rc, why) : KE_OK;
+}
+int ke_resident_pod_add(ke_ctx* ctx, int32_t node, const ke_resident_pod* pod) {
+  if (ctx) async_drain(ctx);
+  if (!ctx) return fail(KE_ERR_INVALID, "null context");
+  const char* why = "";
+  const int rc = resident_add(ctx->c.residents, node, pod, &why);
+  return rc ? fail(rc, why) : KE_OK;
+}
+int ke_resident_pod_remove(ke_ctx* ctx, int32_t node, int64_t uid) {
+  if (ctx) async_drain(ctx);
+  if (!ctx) return fail(KE_ERR_INVALID, "null context");
+  const char* why = "";
+  const int rc = resident_remove(ctx->c.residents, node, uid, &why);
+  return rc ? fail(rc, why) : KE_OK;
+}
+int ke_resident_pods_get(ke_ctx* ctx, int32_t node, int32_t cap, ke_resident_pod* out, int32_t* n) {
+  if (ctx) async_drain(ctx);
+  if (!ctx) return fail(KE_ERR_INVALID, "null context");
+  const char* why = "";
+  const int rc = resident_get(ctx->c.residents, node, cap, out, n, &why);
+  return rc ? fail(rc, why) : KE_OK;
+}
+int ke_pdbs_load(ke_ctx* ctx, int32_t n, const int32_t* disruptions_allowed) {
+  if (ctx) async_drain(ctx);
+  if (!ctx || n < 0 || n > 65535 || (n > 0 && !disruptions_allowed)) return fail(KE_ERR_INVALID, "ke_pdbs_load arguments");
+  ctx->c.pdb_allowed.assign(disruptions_allowed, disruptions_allowed + n);
+  ctx->c.pdb_dirty = true;
+  return KE_OK;
+}
+int ke_abi_preempt_struct_sizes(int32_t* sizes, int32_t n) {
+  const int32_t all[] = {(int32_t)sizeof(ke_resident_pod), (int32_t)sizeof(ke_preempt_args), (int32_t)sizeof(ke_preemption)};
+  const int32_t m = (int32_t)(sizeof(all) / sizeof(all[0]));
+  for (int32_t i = 0; i < n && i < m; i++) sizes[i] = all[i];
+  return m;
+}
+
+// ke_diagnose's admission in its order (the staged ids are consumed first, whatever follows), then this call's own
+// arguments and the refusals of everything but a plain preemptor; the per-preemptor uniforms are the host's.
+int ke_preempt(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, const int32_t* priorities, int64_t now_ns,
+               const ke_preempt_args* args, ke_preemption* out, int32_t victims_cap, int64_t* victim_uids,
+               int32_t words_per_pod, uint64_t* candidates) {
+  if (ctx) async_drain(ctx);
+  if (!ctx) return fail(KE_ERR_INVALID, "null context");
+  Context& c = ctx->c;
+  flush_mirror(c);
+  int rc = take_node_sets(ctx, n_pods, pods, false, /*filter_only=*/true);  // (score offsets do not filter)
+  if (rc) return rc;
+  if (n_pods > 0 && (!out || !priorities || !victim_uids)) return fail(KE_ERR_INVALID, "preempt: null out, priorities or victim_uids");
+  if (victims_cap < 1) return fail(KE_ERR_INVALID, "preempt: victims_cap below 1");
+  if (candidates && words_per_pod < (c.n_nodes + 63) / 64)
+    return fail(KE_ERR_INVALID, "preempt: words_per_pod below ceil(ke_num_nodes / 64)");
+  const ke_preempt_args none{};
+  const ke_preempt_args& a = args ? *args : none;
+  if (a.default_quota < 0 || a.default_quota > (int32_t)c.quotas.size())
+    return fail(KE_ERR_INVALID, "preempt: ke_preempt_args.default_quota outside the loaded ElasticQuota tree");
+  rc = check_pods(pods, n_pods, &c);
+  if (rc) return rc;
+  for (int32_t p = 0; p < n_pods; p++)
+    if (pods[p].quota < 0 || pods[p].quota > (int32_t)c.quotas.size())
+      return fail(KE_ERR_INVALID, "ke_pod.quota outside the loaded ElasticQuota tree");
+  auto no = [](const char* what) { return fail(KE_ERR_UNSUPPORTED, std::string("preempt: ") + what); };
+  if (c.cfg.global_node_offset != 0 || (c.dev && device_sharded(&c))) return no("a node-sharded context");
+  if (c.att.groups || c.att.domains || c.att.terms || c.att.dterms) return no("staged spread group / spread domain ids or term lists");
+  if (c.numa_enabled || c.n_policy_nodes > 0) return no("a context with NUMA topology policy state");
+  if (c.n_bind_nodes > 0) return no("a context with CPU bind policy nodes");
+  for (int32_t p = 0; p < n_pods; p++) {
+    if (pods[p].numa_topology_policy != KE_NUMA_POLICY_NONE) return no("a NUMA-policy pod");
+    const DevPod dp = make_dev_pod(c.cfg, pods[p], pod_hints(c, pods[p]), &c.tmpl);
+    if (dp.flags & (PF_DS | PF_DS_HINT | PF_DS_INVALID)) return no("a DeviceShare pod");
+    if (dp.flags & (PF_CPUSET | PF_CPU_INVALID)) return no("a cpuset pod");
+    for (int q = 0; q < NUM_XS; q++)
+      if (((c.kargs_template.fit_scalar >> q) & 1) && dp.xreq[q] != 0)
+        return no("a pod with a non-zero request for a scalar in ke_fit_args.scalars");
+  }
+  rc = check_cpuset(ctx, pods, n_pods);  // (stages the DevPod records; no pod of the call binds CPUs)
+  if (rc) return rc;
+  rc = require_device(ctx);
+  if (rc) return rc;
+  if (!device_preempt) return fail(KE_ERR_NO_DEVICE, "preempt: built without the device half");
+  if (!c.quotas.empty() && (rc = device_quota_sync(&c))) return rc;  // the device holds the current used after a ke_schedule
+  std::vector<PreemptPod> pre((size_t)n_pods);
+  for (int32_t p = 0; p < n_pods; p++) {
+    PreemptPod& u = pre[(size_t)p];
+    u = PreemptPod{};
+    u.priority = priorities[p];
+    u.quota = (int16_t)pods[p].quota;
+    u.blocked_quota = a.disable_default_quota_preemption ? a.default_quota : (int16_t)0;
+    if (u.quota > 0) {
+      const size_t qi = (size_t)u.quota - 1;
+      const ke_quota& q = c.quotas[qi];
+      for (int r = 0; r < KE_NRES; r++) {
+        u.used[r] = q.used[r];
+        u.lim[r] = c.qlimit[qi * KE_NRES + r];
+        if (c.qlimit_has[qi * KE_NRES + r]) u.lim_has |= (uint8_t)(1u << r);
+        if (q.has_max[r]) u.max_has |= (uint8_t)(1u << r);
+        u.req[r] = q.has_max[r] ? pods[p].requests[r == 0 ? KE_RES_CPU : KE_RES_MEMORY] : 0;
+      }
+    }
+  }
+  return device_preempt(&c, n_pods, pods, pre.data(), now_ns, out, victims_cap, victim_uids, words_per_pod, candidates);
+}
 
 static int schedule_sync(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns, int32_t* chosen, int32_t* score) {
   if (!ctx || (n_pods > 0 && !chosen)) return fail(KE_ERR_INVALID, "ke_schedule arguments");

@@ -13,6 +13,7 @@
 
 #include "../../include/koord_eval.h"
 #include "ke_attach.h"
+#include "ke_preempt.h"
 #include "ke_types.h"
 
 namespace ke {
@@ -269,6 +270,12 @@ struct Context {
   AttachSlot<int32_t> pod_sets, pod_scores, pod_groups, pod_domains;
   AttachSlot<PodTerms> pod_terms, pod_dterms;
   CallAttach att;
+  // Resident pods and PDB budgets (ke_resident_pods_load / ke_pdbs_load; ke_preempt.h): the caller's
+  // statement of which pods sit on which node, beside the rows and never folded into them.  The device copies are
+  // uploaded whole by the next ke_preempt after a change (residents.dirty / pdb_dirty).
+  ResidentTable residents;
+  std::vector<int32_t> pdb_allowed;
+  bool pdb_dirty = true;
   // the KE_RSV_MATCHED pod of the current segment: its nodes with matched reservations, their
   // (node, ScoreReservation of the nominated one, smallest order) for the device pick, the nominated index
   std::vector<int32_t> rsv_nodes;

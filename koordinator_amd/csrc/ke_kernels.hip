@@ -3599,6 +3599,267 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_diag_eval(SoA s, int n_nodes, co
   }
 }
 
+// ---- ke_preempt -------------------------------------------------------------------------------------
+// ElasticQuota's dry-run victim selection (elasticquota/preempt.go:111-215, SelectVictimsOnNode) for every (pod, node)
+// pair and the pick among the candidates.  One wave per node, lane = resident pod (lane l holds entries l and 64 + l of
+// the node's list, which the host keeps in MoreImportantPod order), the group's preemptors looped wave-uniformly as
+// k_eval_batch loops its pods.  The tables come through the kernels' own arguments: SoA does not grow.
+extern "C" __device__ int64_t __ockl_wfred_add_i64(int64_t);
+struct PreTab {
+  const DevResident* rec;  // the CSR's records, list order within a node
+  const int32_t* off;      // [n_nodes + 1]
+  const int64_t* uid;      // parallel to rec
+  const int32_t* pdb;      // disruptions_allowed of PDB id - 1
+};
+constexpr int PRE_BLOCK = 256, PRE_WAVES = PRE_BLOCK / 64, PRE_PPB = 8;
+constexpr int PRE_MAX_PARTS = 512;  // node blocks of k_preempt_sim: a pod's partial keys for k_preempt_pick
+struct PreOut {
+  uint32_t* tally;    // [pods][PRE_WORDS], zeroed by the host
+  PreemptKey* part;   // [pods][n_part]: each node block's best key of the pod
+  int32_t n_part;
+  uint64_t* cand;     // the candidate bitmap, zeroed by the host (nullptr: not asked for)
+  int32_t wpp;
+  ke_preemption* out; // [pods] (k_preempt_pick)
+  int64_t* victims;   // [pods][cap], zeroed by the host (k_preempt_pick)
+  int32_t cap;
+};
+// a node's resident list in one wave's registers
+struct ResLanes {
+  int64_t start[2], mem[2], cpu[2];
+  int32_t prio[2];
+  uint32_t pdb0[2], pdb1[2], quota[2];
+  bool on[2], np[2];
+};
+__device__ __forceinline__ void res_load(const PreTab& t, int i, int lane, ResLanes& R, int* base) {
+  const int b = t.off[i], c = t.off[i + 1] - b;
+  *base = b;
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const int e = lane + 64 * h;
+    R.on[h] = e < c;
+    DevResident r{};
+    if (R.on[h]) r = t.rec[b + e];
+    R.start[h] = r.start_ns, R.mem[h] = r.mem, R.cpu[h] = dr_cpu(r), R.prio[h] = r.priority;
+    R.pdb0[h] = dr_pdb0(r), R.pdb1[h] = r.pdb1, R.quota[h] = r.quota, R.np[h] = (r.flags & RF_NON_PREEMPTIBLE) != 0;
+  }
+}
+__device__ __forceinline__ int64_t nonneg(int64_t x) { return x < 0 ? 0 : x; }  // (RemovePod and SubtractWithNonNegativeResult)
+struct PrePair {
+  int cls;  // PRE_CANDIDATE / PRE_SKIPPED / PRE_NO_VICTIMS / PRE_UNFIT / PRE_ERROR
+  PreemptKey key;
+};
+// One (pod, node) pair, every lane of the wave with the same answer.  REC: the victims' uids go to `rec` (lane 0, the
+// first `cap` of them) in the order the reference appends them.
+template <int NS, bool REC>
+__device__ __forceinline__ PrePair preempt_pair(const SoA& s, const NodeRegs& n, bool expired, const DevPod* pods, int p,
+                                                const KArgs& k, int i, const PreTab& t, const ResLanes& R, int base,
+                                                const PreemptPod& u, int lane, int64_t* rec, int cap) {
+  PrePair out;
+  out.key = preempt_key_none();
+  // 1. the pair as ke_diagnose classifies it; "every other filter" = the same evaluation without NodeResourcesFit's
+  // Filter, needed only where that filter is the one that failed
+  NumaNode nv;
+  bool deferred;
+  const EvalOut o = classify_pair<false, false, NS>(s, n, expired, pods, p, k, i, nv, &deferred);
+  if (o.status == KE_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE || o.status == KE_CODE_ERROR) return out.cls = PRE_SKIPPED, out;
+  const bool fit_on = (k.flags & AF_FIT_FILTER) != 0;
+  bool others = o.status == KE_CODE_SUCCESS;
+  if (!others && fit_on && o.reason >= KE_REASON_FIT_TOO_MANY_PODS && o.reason <= KE_REASON_FIT_INSUFFICIENT_SCALAR) {
+    KArgs k2 = k;
+    k2.flags &= ~(uint32_t)AF_FIT_FILTER;
+    others = eval_pair<true, false, false, false, false, true>(n, expired, pods[p], k2, s, i, nv).status == KE_CODE_SUCCESS;
+  }
+  // 2. canPreempt (preempt.go:283-304)
+  bool v[2];
+#pragma unroll
+  for (int h = 0; h < 2; h++)
+    v[h] = R.on[h] && !R.np[h] && R.prio[h] < u.priority && (int)R.quota[h] == (int)u.quota &&
+           !(u.blocked_quota != 0 && (int)R.quota[h] == (int)u.blocked_quota);
+  const uint64_t bv0 = __ballot(v[0]), bv1 = __ballot(v[1]);
+  const int n_pot = __popcll(bv0) + __popcll(bv1);
+  if (n_pot == 0) return out.cls = PRE_NO_VICTIMS, out;
+  // 3. all of them removed: what NodeResourcesFit's Filter reads, and the quota's used
+  const DevPod& pod = pods[p];
+  const int64_t all_cpu = __ockl_wfred_add_i64((v[0] ? R.cpu[0] : 0) + (v[1] ? R.cpu[1] : 0));
+  const int64_t all_mem = __ockl_wfred_add_i64((v[0] ? R.mem[0] : 0) + (v[1] ? R.mem[1] : 0));
+  const bool m0 = (u.max_has & 1) != 0, m1 = (u.max_has & 2) != 0;
+  int64_t cur0 = nonneg(n.nreq[0] - all_cpu), cur1 = nonneg(n.nreq[1] - all_mem);
+  int64_t room = fit_on ? s.xf[XF_PODS * s.stride + i] + n_pot : 0;
+  int64_t used0 = nonneg(u.used[0] - (m0 ? all_cpu : 0)), used1 = nonneg(u.used[1] - (m1 ? all_mem : 0));
+  auto fits = [&](int64_t rm, int64_t c0, int64_t c1) {
+    if (!fit_on) return true;
+    const bool co = pod.req[0] > 0 && pod.req[0] > n.nalloc[0] - c0;
+    const bool mo = pod.req[1] > 0 && pod.req[1] > n.nalloc[1] - c1;
+    return fit_filter_gen<true>(rm, ExtSoaGet{s, i}, co, mo, pod, k) == 0;  // (a plain preemptor requests no filtered scalar)
+  };
+  if (!(others && fits(room, cur0, cur1))) return out.cls = PRE_UNFIT, out;
+  // 4. filterPodsWithPDBViolation (:222-267): per lane the potential victims up to and including its own entry that
+  // name each of its PDBs, against the budgets of this (pod, node) run
+  uint32_t c0[2] = {0, 0}, c1[2] = {0, 0};
+#pragma unroll
+  for (int hh = 0; hh < 2; hh++) {
+    uint64_t m = __ballot(v[hh] && (R.pdb0[hh] | R.pdb1[hh]) != 0);
+    while (m) {
+      const int j = __ffsll((unsigned long long)m) - 1;
+      m &= m - 1;
+      const uint32_t x0 = (uint32_t)__builtin_amdgcn_readlane((int)R.pdb0[hh], j);
+      const uint32_t x1 = (uint32_t)__builtin_amdgcn_readlane((int)R.pdb1[hh], j);
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const bool upto = j + 64 * hh <= lane + 64 * h;
+        c0[h] += upto && R.pdb0[h] != 0 && (x0 == R.pdb0[h] || x1 == R.pdb0[h]);
+        c1[h] += upto && R.pdb1[h] != 0 && (x0 == R.pdb1[h] || x1 == R.pdb1[h]);
+      }
+    }
+  }
+  bool viol[2];
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    viol[h] = false;
+    if (v[h] && R.pdb0[h] != 0) viol[h] = (int64_t)t.pdb[R.pdb0[h] - 1] - (int64_t)c0[h] < 0;
+    if (v[h] && R.pdb1[h] != 0) viol[h] = viol[h] || (int64_t)t.pdb[R.pdb1[h] - 1] - (int64_t)c1[h] < 0;
+  }
+  // 5. the reprieve (:175-213): the violating victims, then the others, each group in list order
+  int n_vict = 0, n_viol = 0, hi = INT32_MIN;
+  int64_t hi_start = INT64_MAX;
+  uint64_t prio_sum = 0;
+  bool err = false;
+#pragma unroll
+  for (int g = 0; g < 2; g++) {
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      uint64_t m = __ballot(v[h] && viol[h] == (g == 0));
+      while (m && !err) {
+        const int j = __ffsll((unsigned long long)m) - 1;
+        m &= m - 1;
+        const int64_t cpu = readlane64(R.cpu[h], j), mem = readlane64(R.mem[h], j), start = readlane64(R.start[h], j);
+        const int prio = __builtin_amdgcn_readlane(R.prio[h], j);
+        const int64_t q0 = m0 ? cpu : 0, q1 = m1 ? mem : 0;
+        auto remove = [&]() {  // NodeInfo.RemovePod + the plugin's RemovePod, and the pod is a victim
+          cur0 = nonneg(cur0 - cpu), cur1 = nonneg(cur1 - mem), room += 1;
+          used0 = nonneg(used0 - q0), used1 = nonneg(used1 - q1);
+          if (REC && lane == 0 && n_vict < cap) rec[n_vict] = t.uid[base + j + 64 * h];
+          n_vict++;
+          prio_sum += (uint64_t)((int64_t)prio + 2147483649LL);
+          if (prio > hi) hi = prio, hi_start = start;
+          else if (prio == hi) hi_start = start < hi_start ? start : hi_start;
+        };
+        cur0 += cpu, cur1 += mem, room -= 1, used0 += q0, used1 += q1;  // addPod
+        const bool fit = fits(room, cur0, cur1);
+        if (!fit) {
+          remove();
+          n_viol += g == 0;
+        }
+        const bool quota_ok = u.quota == 0 || (!((u.lim_has & 1) && used0 + u.req[0] > u.lim[0]) &&
+                                               !((u.lim_has & 2) && used1 + u.req[1] > u.lim[1]));
+        if (!quota_ok) {
+          if (!fit) err = true;  // the second NodeInfo.RemovePod of one pod errs: the node returns an error status
+          else remove();
+        }
+      }
+    }
+  }
+  if (err) return out.cls = PRE_ERROR, out;
+  out.cls = PRE_CANDIDATE;
+  out.key = preempt_key(n_viol, hi, prio_sum, n_vict, hi_start, i);
+  return out;
+}
+
+// The simulation of every pair.  Grid: node blocks (x) x groups of PRE_PPB pods (y); wave w of block b takes nodes
+// 4b + w, then strides by the grid.  Per pod a wave keeps its best key and its class counts in its own LDS rows; the
+// block folds the waves' keys into one partial per pod and adds the counts to the global tallies.
+template <int NS = 0>
+__global__ __launch_bounds__(PRE_BLOCK) void k_preempt_sim(SoA s, int n_nodes, const DevPod* __restrict__ pods, int n_pods,
+                                                           KArgs k, PreTab t, const PreemptPod* __restrict__ pre, PreOut out) {
+  __shared__ PreemptKey s_best[PRE_WAVES][PRE_PPB];
+  __shared__ uint32_t s_t[PRE_WAVES][PRE_PPB][PRE_WORDS];
+  for (int q = threadIdx.x; q < PRE_WAVES * PRE_PPB; q += PRE_BLOCK) (&s_best[0][0])[q] = preempt_key_none();
+  for (int q = threadIdx.x; q < PRE_WAVES * PRE_PPB * PRE_WORDS; q += PRE_BLOCK) (&s_t[0][0][0])[q] = 0u;
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int p0 = blockIdx.y * PRE_PPB, p1 = min(n_pods, p0 + PRE_PPB);
+  for (int i = blockIdx.x * PRE_WAVES + wave; i < n_nodes; i += gridDim.x * PRE_WAVES) {
+    NodeRegs n;
+    load_row(s, i, n);
+    if (!(n.flags & NF_VALID)) {  // an empty slot: absent, whatever a pod's set says
+      if (lane == 0)
+        for (int p = p0; p < p1; p++) s_t[wave][p - p0][PRE_ABSENT]++;
+      continue;
+    }
+    prepare_row(n);
+    const bool expired = node_expired(n, k);
+    ResLanes R;
+    int base;
+    res_load(t, i, lane, R, &base);
+    for (int p = p0; p < p1; p++) {
+      const PrePair r = preempt_pair<NS, false>(s, n, expired, pods, p, k, i, t, R, base, pre[p], lane, nullptr, 0);
+      if (lane == 0) {
+        s_t[wave][p - p0][r.cls]++;
+        if (r.cls == PRE_CANDIDATE) {
+          if (preempt_key_less(r.key, s_best[wave][p - p0])) s_best[wave][p - p0] = r.key;
+          if (out.cand)
+            atomicOr(reinterpret_cast<unsigned long long*>(out.cand + (int64_t)p * out.wpp + (i >> 6)), 1ull << (i & 63));
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < p1 - p0) {
+    const int q = threadIdx.x;
+    PreemptKey b = s_best[0][q];
+    for (int w = 1; w < PRE_WAVES; w++)
+      if (preempt_key_less(s_best[w][q], b)) b = s_best[w][q];
+    out.part[(int64_t)(p0 + q) * out.n_part + blockIdx.x] = b;
+  }
+  for (int q = threadIdx.x; q < (p1 - p0) * PRE_WORDS; q += PRE_BLOCK) {
+    uint32_t c = 0;
+    for (int w = 0; w < PRE_WAVES; w++) c += (&s_t[w][0][0])[q];
+    if (c) atomicAdd(&out.tally[(int64_t)p0 * PRE_WORDS + q], c);
+  }
+}
+
+// The pick: one wave per pod takes the node blocks' partial keys to the pod's best candidate, runs that pair again
+// with the victims recorded, and writes the pod's ke_preemption from it and from the tallies.
+template <int NS = 0>
+__global__ __launch_bounds__(64) void k_preempt_pick(SoA s, const DevPod* __restrict__ pods, int n_pods, KArgs k, PreTab t,
+                                                     const PreemptPod* __restrict__ pre, PreOut out) {
+  const int p = blockIdx.x, lane = threadIdx.x;
+  if (p >= n_pods) return;
+  PreemptKey b = preempt_key_none();
+  for (int q = lane; q < out.n_part; q += 64) {
+    const PreemptKey c = out.part[(int64_t)p * out.n_part + q];
+    if (preempt_key_less(c, b)) b = c;
+  }
+  for (int d = 32; d; d >>= 1) {
+    PreemptKey c;
+#pragma unroll
+    for (int w = 0; w < 4; w++) c.w[w] = (uint64_t)__shfl_xor((unsigned long long)b.w[w], d, 64);
+    if (preempt_key_less(c, b)) b = c;
+  }
+  ke_preemption r{};
+  r.node = -1;
+  if (!preempt_key_is_none(b)) {
+    const int i = preempt_key_node(b);
+    NodeRegs n;
+    load_row(s, i, n);
+    prepare_row(n);
+    ResLanes R;
+    int base;
+    res_load(t, i, lane, R, &base);
+    const PrePair again = preempt_pair<NS, true>(s, n, node_expired(n, k), pods, p, k, i, t, R, base, pre[p], lane,
+                                                 out.victims + (int64_t)p * out.cap, out.cap);
+    if (again.cls == PRE_CANDIDATE) {  // (the same pair: the same key)
+      r.node = i;
+      r.n_victims = preempt_key_victims(again.key);
+      r.n_pdb_violations = preempt_key_violations(again.key);
+    }
+  }
+  const uint32_t* c = out.tally + (int64_t)p * PRE_WORDS;
+  r.n_candidates = (int32_t)c[PRE_CANDIDATE], r.n_skipped = (int32_t)c[PRE_SKIPPED], r.n_no_victims = (int32_t)c[PRE_NO_VICTIMS];
+  r.n_unfit = (int32_t)c[PRE_UNFIT], r.n_error = (int32_t)c[PRE_ERROR];
+  if (lane == 0) out.out[p] = r;
+}
+
 // DeviceShare NormalizeScore (DefaultNormalizeScore(MaxNodeScore, false): score*100/max when max > 0)
 __device__ __forceinline__ int32_t ds_norm(int32_t raw, uint32_t dsmax1) {
   const int32_t mx = dsmax1 > 0 ? (int32_t)dsmax1 - 1 : 0;
@@ -7623,6 +7884,17 @@ struct DeviceState {
   // ke_diagnose: the raw tallies [pods][DIAG_WORDS] u32, then the bitmaps asked for ([pods][words_per_pod] u64 each)
   DevBuf<uint8_t> d_diag;
   bool diag_xcd = true;  // k_diag_eval's XCD-aware block mapping (KOORDEVAL_DIAG_XCD=0: the plain one, an A/B; §4q)
+  // ke_preempt: the resident pods as a CSR of 32-byte records in list order (offsets over res_nodes
+  // nodes, the uids in a parallel array) and the PDB budgets, uploaded whole when the host tables changed; a call's
+  // per-preemptor uniforms; and one block for its tallies, results, partial keys, victim lists and bitmap
+  DevBuf<DevResident> d_res;
+  DevBuf<int32_t> d_res_off;
+  DevBuf<int64_t> d_res_uid;
+  DevBuf<int32_t> d_pdb;
+  int32_t res_nodes = -1;
+  DevBuf<PreemptPod> d_prepods;
+  DevBuf<uint8_t> d_preempt;
+  double res_upload_ms = 0;  // host wall time of the last table upload (pack + copies enqueued)
   int profile_every = 0;
   // node sharding (ke_shard_init): this rank evaluates/selects nodes shard_range(rank); the per-shard
   // candidate lists meet in d_gath through an RCCL all-gather (or, loopback, all shards run here)
@@ -8761,6 +9033,91 @@ int device_diagnose(Context* ctx, int32_t n_pods, const ke_pod* pods, int64_t no
   return KE_OK;
 }
 
+// ke_preempt: the pass begun as device_diagnose's; the resident table and the PDB budgets uploaded whole
+// when they changed since the last call; the preemptors' uniforms; one zeroed block (tallies, results, victim lists,
+// the bitmap when asked for) with the partial keys behind it; k_preempt_sim and k_preempt_pick; one copy back per output.
+using PreemptSimFn = void (*)(SoA, int, const DevPod*, int, KArgs, PreTab, const PreemptPod*, PreOut);
+using PreemptPickFn = void (*)(SoA, const DevPod*, int, KArgs, PreTab, const PreemptPod*, PreOut);
+static PreemptSimFn pick_preempt_sim(int ns);    // (named at the end of this file, with the kernels' instantiations)
+static PreemptPickFn pick_preempt_pick(int ns);
+int device_preempt(Context* ctx, int32_t n_pods, const ke_pod* pods, const PreemptPod* pre, int64_t now, ke_preemption* out,
+                   int32_t victims_cap, int64_t* victim_uids, int32_t words_per_pod, uint64_t* candidates) {
+  DeviceState* d = ctx->dev;
+  const int ns = ctx->att.ns_filter();  // (0 or NS_SETS: the admission refused the other kinds)
+  PairPass pp;
+  int rc = pair_pass_begin(ctx, n_pods, pods, now, ns, &pp);
+  if (rc || n_pods == 0) return rc;
+  const int64_t N = ctx->n_nodes, P = n_pods;
+  std::vector<int32_t> off;
+  std::vector<DevResident> recs;
+  std::vector<int64_t> uids;
+  if (ctx->residents.dirty || ctx->pdb_dirty || d->res_nodes != (int32_t)N) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const char* why = "";
+    if ((rc = resident_pack(ctx->residents, (int32_t)N, (int32_t)ctx->pdb_allowed.size(), off, recs, uids, &why))) return fail(rc, why);
+    RC_OK(d->d_res_off.reserve(off.size()));
+    RC_OK(d->d_res.reserve(std::max<size_t>(recs.size(), 1)));
+    RC_OK(d->d_res_uid.reserve(std::max<size_t>(uids.size(), 1)));
+    RC_OK(d->d_pdb.reserve(std::max<size_t>(ctx->pdb_allowed.size(), 1)));
+    HIP_OK(hipMemcpyAsync(d->d_res_off, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice, d->stream));
+    if (!recs.empty()) {
+      HIP_OK(hipMemcpyAsync(d->d_res, recs.data(), sizeof(DevResident) * recs.size(), hipMemcpyHostToDevice, d->stream));
+      HIP_OK(hipMemcpyAsync(d->d_res_uid, uids.data(), sizeof(int64_t) * uids.size(), hipMemcpyHostToDevice, d->stream));
+    }
+    if (!ctx->pdb_allowed.empty())
+      HIP_OK(hipMemcpyAsync(d->d_pdb, ctx->pdb_allowed.data(), sizeof(int32_t) * ctx->pdb_allowed.size(), hipMemcpyHostToDevice, d->stream));
+    HIP_OK(hipStreamSynchronize(d->stream));  // (the staging vectors are this call's; the time below is the upload's)
+    d->res_nodes = (int32_t)N;
+    ctx->residents.dirty = ctx->pdb_dirty = false;
+    d->res_upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  RC_OK(d->d_prepods.reserve((size_t)P));
+  HIP_OK(hipMemcpyAsync(d->d_prepods, pre, sizeof(PreemptPod) * P, hipMemcpyHostToDevice, d->stream));
+  // the block: tallies, results, victim lists, bitmap (zeroed together), then the partial keys (every one written)
+  const int n_part = (int)std::max<int64_t>(1, std::min<int64_t>((N + PRE_WAVES - 1) / PRE_WAVES, PRE_MAX_PARTS));
+  const int64_t wpp = candidates ? words_per_pod : 0;
+  const int64_t tally_b = (int64_t)sizeof(uint32_t) * PRE_WORDS * P, out_b = (int64_t)sizeof(ke_preemption) * P;
+  const int64_t vict_b = (int64_t)sizeof(int64_t) * P * victims_cap, cand_b = (int64_t)sizeof(uint64_t) * P * wpp;
+  const int64_t zero_b = tally_b + out_b + vict_b + cand_b, part_b = (int64_t)sizeof(PreemptKey) * P * n_part;
+  static_assert(sizeof(uint32_t) * PRE_WORDS % 8 == 0 && sizeof(ke_preemption) % 8 == 0, "the block's sections are 8-byte aligned");
+  RC_OK(d->d_preempt.reserve((size_t)(zero_b + part_b)));
+  HIP_OK(hipMemsetAsync(d->d_preempt, 0, (size_t)zero_b, d->stream));
+  PreOut po{};
+  po.tally = reinterpret_cast<uint32_t*>(d->d_preempt.get());
+  po.out = reinterpret_cast<ke_preemption*>(d->d_preempt + tally_b);
+  po.victims = reinterpret_cast<int64_t*>(d->d_preempt + tally_b + out_b);
+  po.cand = candidates ? reinterpret_cast<uint64_t*>(d->d_preempt + tally_b + out_b + vict_b) : nullptr;
+  po.part = reinterpret_cast<PreemptKey*>(d->d_preempt + zero_b);
+  po.n_part = n_part, po.wpp = (int32_t)wpp, po.cap = victims_cap;
+  const PreTab tab{d->d_res, d->d_res_off, d->d_res_uid, d->d_pdb};
+  const auto sim = pick_preempt_sim(ns);
+  const auto pick = pick_preempt_pick(ns);
+  if (!sim || !pick) return no_variant("k_preempt_sim");
+  if (N > 0) {
+    const dim3 grid((unsigned)n_part, (unsigned)((P + PRE_PPB - 1) / PRE_PPB));
+    hipLaunchKernelGGL(sim, grid, dim3(PRE_BLOCK), 0, d->stream, d->soa, (int)N, d->call.d_pods, (int)P, pp.k, tab, d->d_prepods, po);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(pick, dim3((unsigned)P), dim3(64), 0, d->stream, d->soa, d->call.d_pods, (int)P, pp.k, tab, d->d_prepods, po);
+    HIP_OK(hipGetLastError());
+  }
+  std::vector<uint32_t> raw((size_t)(PRE_WORDS * P));
+  HIP_OK(hipMemcpyAsync(raw.data(), po.tally, (size_t)tally_b, hipMemcpyDeviceToHost, d->stream));
+  HIP_OK(hipMemcpyAsync(out, po.out, (size_t)out_b, hipMemcpyDeviceToHost, d->stream));
+  HIP_OK(hipMemcpyAsync(victim_uids, po.victims, (size_t)vict_b, hipMemcpyDeviceToHost, d->stream));
+  if (candidates) HIP_OK(hipMemcpyAsync(candidates, po.cand, (size_t)cand_b, hipMemcpyDeviceToHost, d->stream));
+  if ((rc = pair_pass_end(ctx, pp))) return rc;
+  for (int64_t p = 0; p < P; p++) {
+    if (N == 0) out[p].node = -1;
+    int64_t sum = 0;
+    for (int c = 0; c <= PRE_ABSENT; c++) sum += raw[(size_t)(p * PRE_WORDS + c)];
+    const ke_preemption& r = out[p];
+    if (sum != N || (int64_t)r.n_candidates + r.n_skipped + r.n_no_victims + r.n_unfit + r.n_error + raw[(size_t)(p * PRE_WORDS + PRE_ABSENT)] != N ||
+        (r.node < 0) != (r.n_candidates == 0))
+      return fail(KE_ERR_DEVICE, "internal: the preemption tallies of a pod do not add up");
+  }
+  return KE_OK;
+}
+
 // The other call's buffers become this context's (ke_schedule_submit with a call in flight; host_pods, the pods,
 // outputs, stamps, hand-off words, readback staging and events are per call).
 void device_swap_call_buffers(Context* ctx) {
@@ -9745,5 +10102,9 @@ static DiagEvalFn pick_diag_eval_dterms(bool numa, bool cpu) {
   if (numa) return cpu ? k_diag_eval<true, true, NS_DTERMS> : k_diag_eval<true, false, NS_DTERMS>;
   return cpu ? k_diag_eval<false, true, NS_DTERMS> : k_diag_eval<false, false, NS_DTERMS>;
 }
+
+// ---- ke_preempt's kernels: named here alone, so they lie behind every kernel that existed before -----
+static PreemptSimFn pick_preempt_sim(int ns) { return ns == NS_SETS ? k_preempt_sim<NS_SETS> : ns == 0 ? k_preempt_sim<> : nullptr; }
+static PreemptPickFn pick_preempt_pick(int ns) { return ns == NS_SETS ? k_preempt_pick<NS_SETS> : ns == 0 ? k_preempt_pick<> : nullptr; }
 
 }  // namespace ke

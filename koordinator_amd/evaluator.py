@@ -566,6 +566,63 @@ class Evaluator:
             out[k] = unpack_node_sets(w, N)
         return out
 
+    # ---- dry-run preemption ---------------------------------------------------
+    def resident_pods_load(self, per_node):
+        """ke_resident_pods_load: `per_node` is, per node index from 0, an array / list of RESIDENT_POD_DTYPE records
+        (any order; the library keeps each list in MoreImportantPod order).  Replaces the whole table."""
+        parts = [np.ascontiguousarray(np.asarray(x, abi.RESIDENT_POD_DTYPE).reshape(-1)) for x in per_node]
+        off = np.zeros(len(parts) + 1, np.int32)
+        off[1:] = np.cumsum([len(x) for x in parts])
+        recs = np.concatenate(parts) if off[-1] else np.zeros(1, abi.RESIDENT_POD_DTYPE)
+        recs = np.ascontiguousarray(recs)
+        self._check(self.lib.ke_resident_pods_load(self.h, len(parts), abi.ptr(off), abi.ptr(recs)))
+
+    def resident_pod_add(self, node, pod):
+        """ke_resident_pod_add: one RESIDENT_POD_DTYPE record onto `node`'s list."""
+        rec = np.ascontiguousarray(np.asarray(pod, abi.RESIDENT_POD_DTYPE).reshape(1))
+        self._check(self.lib.ke_resident_pod_add(self.h, int(node), abi.ptr(rec)))
+
+    def resident_pod_remove(self, node, uid):
+        self._check(self.lib.ke_resident_pod_remove(self.h, int(node), int(uid)))
+
+    def resident_pods_get(self, node):
+        """ke_resident_pods_get: the node's list in its kept order."""
+        n = abi.i32()
+        out = np.zeros(abi.MAX_RESIDENT_PODS, abi.RESIDENT_POD_DTYPE)
+        self._check(self.lib.ke_resident_pods_get(self.h, int(node), len(out), abi.ptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def pdbs_load(self, disruptions_allowed):
+        """ke_pdbs_load: Status.DisruptionsAllowed per PDB; a resident record's pdb id is 1 + its index here."""
+        a = np.ascontiguousarray(disruptions_allowed, np.int32).reshape(-1)
+        self._check(self.lib.ke_pdbs_load(self.h, len(a), abi.ptr(a) if len(a) else None))
+
+    def preempt(self, pods, priorities, now_ns, args=None, victims_cap=abi.MAX_RESIDENT_PODS, candidates=False,
+                node_sets=None, extra_words=0):
+        """ke_preempt: per pod the dry-run victim selection over every node and the pick -- int32 [P] arrays node
+        (-1 = no candidate), n_victims, n_pdb_violations, n_candidates, n_skipped, n_no_victims, n_unfit, n_error,
+        `victims`: int64 [P, victims_cap] uids of the picked node's victims in the reference's order (0 beyond
+        min(n_victims, victims_cap)); with `candidates` also the bool [P, N] candidate matrix.  `args`: abi.PreemptArgs
+        or None; `node_sets` as for eval(); `extra_words`: bitmap words per pod beyond the minimum."""
+        pods = as_pod_array(pods)
+        self._stage(node_sets, None, None, None, None, None)
+        P, N = len(pods), self.num_nodes
+        pri = np.ascontiguousarray(priorities, np.int32).reshape(-1)
+        assert len(pri) == P
+        rec = np.zeros(P, abi.PREEMPTION_DTYPE)
+        victims = np.zeros((P, victims_cap), np.int64)
+        wpp = (N + 63) // 64 + extra_words
+        words = np.zeros((P, wpp), np.uint64) if candidates else None
+        self._check(self.lib.ke_preempt(self.h, P, abi.ptr(pods), abi.ptr(pri), int(now_ns),
+                                        C.cast(C.pointer(args), C.c_void_p) if args is not None else None, abi.ptr(rec),
+                                        int(victims_cap), abi.ptr(victims), wpp, abi.ptr(words)))
+        out = {k: np.ascontiguousarray(rec[k]) for k in rec.dtype.names}
+        out["victims"] = victims
+        if candidates:
+            out["candidates"] = unpack_node_sets(words[:, :(N + 63) // 64], N)
+            out["candidate_words"] = words
+        return out
+
     def schedule(self, pods, now_ns, matches=None, node_sets=None, node_scores=None, spread_groups=None,
                  spread_domains=None, spread_terms=None, spread_domain_terms=None):
         """ke_schedule; `matches` (optional): per pod the reservation indices it matches (KE_RSV_MATCHED pods);
