@@ -56,30 +56,6 @@ static const bool kFuseMatched = [] {
   return !e || std::atoi(e) != 0;
 }();
 
-// The release records of one completed call (ke_last_allocations / ke_unreserve read them from the Context):
-// taken when the call completes, restored when ke_schedule_wait collects it, so a wait on an earlier ticket
-// never pairs that call's nodes with a later call's cpusets / NUMA amounts / device minors.
-struct CallRecords {
-  std::vector<int32_t> chosen, resv;
-  std::vector<int64_t> uid, numa;
-  std::vector<uint8_t> quota;
-  std::vector<uint64_t> cpusets, dev;
-  std::vector<int8_t> vf;
-  int32_t resv_gen = 0;  // the reservation set `resv` indexes
-  void save(const Context& c) {
-    chosen = c.last_chosen, resv = c.last_resv, uid = c.last_uid, numa = c.last_numa_alloc, quota = c.last_quota;
-    cpusets = c.last_cpusets, dev = c.last_dev_alloc, vf = c.last_vf;
-    resv_gen = c.resv_gen;
-  }
-  void restore(Context& c) {
-    c.last_chosen.swap(chosen), c.last_uid.swap(uid), c.last_numa_alloc.swap(numa), c.last_quota.swap(quota);
-    c.last_cpusets.swap(cpusets), c.last_dev_alloc.swap(dev), c.last_vf.swap(vf);
-    // a reservation set loaded since names other reservations: as load_reservations does, the records drop them
-    if (resv_gen == c.resv_gen) c.last_resv.swap(resv);
-    else c.last_resv.assign(c.last_chosen.size(), 0);
-  }
-};
-
 // A ke_schedule_submit call: its device work in flight (`fin` set), or completed with its outputs kept until
 // ke_schedule_wait collects them.
 struct AsyncCall {
@@ -92,7 +68,10 @@ struct AsyncCall {
   int rc = KE_OK;
   std::string msg;
   std::vector<int32_t> chosen, score;
-  CallRecords rec;  // its release records (set when it completes)
+  // its release records: a copy of the Context's taken when it completes and restored when ke_schedule_wait collects
+  // it, so a wait on an earlier ticket never pairs that call's nodes with a later call's cpusets / NUMA amounts /
+  // device minors
+  CallRecords rec;
 };
 
 struct ke_ctx {
@@ -117,12 +96,9 @@ static void async_finish(ke_ctx* ctx, AsyncCall& a) {
   Context& c = ctx->c;
   // the completion wrote this call's device / cpuset / VF / NUMA records into the Context; a plain queue assumes
   // no reservation and no quota
-  c.last_chosen = a.chosen;
-  c.last_uid.resize((size_t)a.n);
-  for (int32_t p = 0; p < a.n; p++) c.last_uid[(size_t)p] = a.pods[p].uid;
-  c.last_quota.assign((size_t)a.n, 0);
-  c.last_resv.assign((size_t)a.n, 0);
-  a.rec.save(c);
+  c.last.resv.clear();
+  c.last.set_pods(a.n, a.chosen.data(), a.pods, false, c.resv_gen);
+  a.rec = c.last;
   const int32_t off = c.cfg.global_node_offset;
   const int64_t base = c.pending_base;  // the completion copied the pods there
   c.pending.reserve(c.pending.size() + (size_t)a.n);
@@ -201,11 +177,8 @@ static int check_cpuset(ke_ctx* ctx, const ke_pod* pods, int32_t n) {
 // call schedules any pod: a refusal after earlier segments ran would leave their Reserves applied.
 static int check_matches(Context& c, const ke_pod* pods, int32_t n) {
   const bool staged = !c.match_off.empty();
-  if (staged && (int32_t)c.match_off.size() != n + 1) {
-    c.match_off.clear();
-    c.match_ids.clear();
+  if (staged && (int32_t)c.match_off.size() != n + 1)
     return fail(KE_ERR_INVALID, "ke_pod_reservations lists for a different number of pods");
-  }
   for (int32_t p = 0; p < n; p++) {
     const int32_t cnt = staged ? c.match_off[(size_t)p + 1] - c.match_off[(size_t)p] : 0;
     const uint8_t rm = pods[p].reservation_matched;
@@ -277,6 +250,197 @@ static int check_matches(Context& c, const ke_pod* pods, int32_t n) {
   }
   return KE_OK;
 }
+
+// a ke_last_* view of one device-made kind of the last call's records
+template <class Kind, class T>
+static int last_flat(ke_ctx* ctx, int32_t n, T* out, Kind CallRecords::*kind, const char* what) {
+  if (!ctx || n < 0 || (n > 0 && !out)) return fail(KE_ERR_INVALID, what);
+  (ctx->c.last.*kind).flat(n, out);
+  return KE_OK;
+}
+
+// The staged ke_pod_reservations lists belong to the ke_schedule / ke_schedule_submit call that follows them, refused
+// or not: the entry point holds one of these, and the lists are consumed when it returns.
+struct StagedMatches {
+  Context& c;
+  ~StagedMatches() { c.match_off.clear(), c.match_ids.clear(); }
+};
+
+// One segment of a ke_schedule call (ke_segments.h): prepare -> schedule -> finish -> mirror -> refresh_quota.  It knows
+// what it has done to the reservation state so far (`ignoring`, `held`) and undoes exactly that when it is left without
+// resv_finish having assumed the pod: every error exit of the call is a plain return.  (A device failure leaves the
+// context's state undefined, KE_ERR_DEVICE: rebuild it; a reservation's capacity still does not stay visible.)
+struct SegmentRun {
+  Context& c;
+  const ke_pod* pods;
+  int32_t n_pods;
+  int64_t now;
+  int32_t *chosen, *score, *assumed;
+  const uint8_t* cls;  // PodClass bits per pod
+  const Segment seg;
+  int32_t len = seg.s1 - seg.s0;  // pods of the segment's record: with the fused pod once it has placed
+  bool fuse = false;              // the pod after the segment runs last in the segment's call
+  bool ignoring = false;          // resv_ignore_begin ran
+  const ke_pod* held = nullptr;   // the matched pod whose views / restore the reservation state carries
+  ~SegmentRun() {
+    release();
+    if (ignoring) resv_ignore_end(c);
+  }
+  const int32_t* ids(int32_t p) const { return c.match_ids.data() + c.match_off[(size_t)p]; }
+  int32_t n_ids(int32_t p) const { return c.match_off[(size_t)p + 1] - c.match_off[(size_t)p]; }
+  // the held pod's views' rows, nomination and restore back to what every other pod sees
+  void release() {
+    if (!held) return;
+    for (const DsView& v : c.ds_views) resv_node_restore(c, v.node);
+    for (const NumaRsvView& v : c.numa_views) resv_node_restore(c, v.node);
+    int32_t none = 0;
+    resv_finish(c, -1, *held, &none);
+    held = nullptr;
+  }
+  // ---- the view sequences: trials on the current state, each in the order its plugins' restores need --------------
+  template <class Fn, class V, class O>
+  int trials(Fn device_views, const ke_pod& pod, const std::vector<V>& views, std::vector<O>& out) {
+    return views.empty() ? KE_OK : device_views(&c, pod, now, views, out);
+  }
+  // a binding pod's cpuset and Score on the nomination / the Filter's affinity (NUMA policies)
+  int cpuset_pass(const ke_pod& pod) {
+    const int rc = trials(device_rsv_views, pod, c.numa_cs_views, c.numa_cs_out);
+    if (!rc && !c.numa_cs_views.empty()) resv_numa_cs_apply(c);
+    return rc;
+  }
+  // an ignored pod: its allocate-ignoring-reservation trials and NUMA hints, then DeviceShare's ignore / own views
+  int ignored_views(const ke_pod& pod) {
+    flush_mirror(c);
+    resv_ignore_views(c, pod);
+    int rc = trials(device_rsv_views, pod, c.rsv_views, c.rsv_view_out);
+    if (!rc) rc = trials(device_numa_views, pod, c.numa_views, c.numa_view_out);
+    if (!rc) resv_ds_views(c, pod, nullptr, 0), rc = trials(device_ds_views, pod, c.ds_views, c.ds_view_out);
+    if (rc) return rc;
+    resv_ignore_ovr(c);
+    return cpuset_pass(pod);
+  }
+  // a matched pod: its allocate-from-reservation trials, DeviceShare's on the rows with its matched restore, then
+  // NodeNUMAResource's hints over the trials; the nomination last
+  int matched_views(int32_t p) {
+    const ke_pod& pod = *(held = &pods[p]);
+    resv_views(c, pod, ids(p), n_ids(p));
+    int rc = trials(device_rsv_views, pod, c.rsv_views, c.rsv_view_out);
+    if (!rc) resv_ds_views(c, pod, ids(p), n_ids(p)), rc = trials(device_ds_views, pod, c.ds_views, c.ds_view_out);
+    if (!rc) resv_numa_views(c, pod, ids(p), n_ids(p)), rc = trials(device_numa_views, pod, c.numa_views, c.numa_view_out);
+    if (!rc) rc = resv_prepare(c, pod, ids(p), n_ids(p), pod.reservation_matched == KE_RSV_AFFINITY);
+    return rc ? rc : cpuset_pass(pod);
+  }
+  // the pod after a plain segment ("fused"): its nomination and rows are taken now, on the state before
+  // the segment, when it needs no view and no allocate-from-reservation decision; else it stays a segment of its own
+  int try_fuse(int32_t p) {
+    if (int rc = device_refresh(&c, now, false)) return rc;  // the segment's rows (no host wait)
+    held = &pods[p];
+    resv_views(c, pods[p], ids(p), n_ids(p));
+    fuse = c.rsv_views.empty();
+    if (fuse) resv_ds_views(c, pods[p], ids(p), n_ids(p)), fuse = c.ds_views.empty();
+    if (fuse) resv_numa_views(c, pods[p], ids(p), n_ids(p)), fuse = c.numa_views.empty();
+    if (int rc = fuse ? resv_prepare(c, pods[p], ids(p), n_ids(p), false) : KE_OK) return rc;
+    fuse = fuse && c.rsv_ovr.empty() && c.numa_cs_views.empty();
+    if (!fuse) release();
+    return KE_OK;
+  }
+
+  int prepare() {
+    mirror_join(c);  // (the previous segment's host mirror thread: this one reads the node state)
+    if (seg.ign) resv_ignore_begin(c), ignoring = true;
+    if (seg.ign && seg.alone) return ignored_views(pods[seg.s0]);
+    if (seg.matched()) return matched_views(seg.s0);
+    const int32_t p = seg.s1;  // (matched, not ignoring: PC_ALONE alone)
+    if (kFuseMatched && p < n_pods &&
+        may_fuse(seg, (cls[p] & (PC_ALONE | PC_IGNORED)) == PC_ALONE && pods[p].reservation_matched == KE_RSV_MATCHED,
+                 !(c.staged[(size_t)p].flags & (PF_CPUSET | PF_DS | PF_DS_HINT)), !c.quotas.empty(), device_sharded(&c)))
+      return try_fuse(p);
+    return KE_OK;
+  }
+
+  int schedule() {
+    c.rsv_fused = fuse;
+    const int rc = device_schedule(&c, len + fuse, pods + seg.s0, now, chosen + seg.s0, score ? score + seg.s0 : nullptr);
+    c.rsv_fused = false;
+    return rc;
+  }
+  // The Reservation plugin's outcome of the held pod, at position `pos` of the segment's record: k_rsv_pick's winner is
+  // the placement, its ScoreReservation joins the score, the pod is assumed with the cpuset / NUMA amounts / minors it got
+  int matched_outcome(int32_t pos) {
+    const int32_t p = seg.s0 + pos;
+    const int32_t local = chosen[p] < 0 ? -1 : chosen[p] - c.cfg.global_node_offset;
+    int32_t pick[4] = {local, 0, 0, -1};  // no usable matched reservation: no Reservation score
+    if (int rc = !c.rsv_pairs.empty() || c.rsv_affinity ? device_rsv_result(&c, pick) : KE_OK) return rc;
+    if (local >= 0 && local != pick[0]) return fail(KE_ERR_DEVICE, "k_rsv_pick winner differs from the placement");
+    if (local >= 0 && score) score[p] = (int32_t)((int64_t)score[p] + c.cfg.weight_reservation * (int64_t)pick[1]);
+    resv_finish(c, local, *held, &assumed[p], c.last.cpuset(pos), c.last.numa(pos), c.last.dev(pos));
+    held = nullptr;
+    return KE_OK;
+  }
+
+  int finish() {
+    if (ignoring) resv_ignore_end(c), ignoring = false;
+    if (fuse && device_rsv_gate(&c)) {
+      // k_rsv_check: a plain pod took a node of the fused pod's reservations and the pod placed nothing; its nomination
+      // and rows are undone and it runs next as a segment of its own (the call's per-pod outputs: the segment's only)
+      release();
+      chosen[seg.s1] = -1;
+      c.last.truncate((size_t)len);
+      if (c.last_pod_lat.size() > (size_t)len) c.last_pod_lat.resize((size_t)len);
+      if (!c.last_batch_ms.empty()) c.last_batch_ms.pop_back();
+      c.last_rsv_fused_gated++;
+      fuse = false;
+    } else if (fuse) {
+      if (int rc = matched_outcome(len)) return rc;
+      c.last_rsv_fused++, len++;
+    }
+    return seg.matched() ? matched_outcome(0) : KE_OK;
+  }
+
+  // Host mirror of the Reserves the device already applied to its rows: keep the object state (assign cache,
+  // NodeInfo.Requested) in step so later re-derivations include these pods.
+  void mirror() {
+    const auto tp = std::chrono::steady_clock::now();
+    c.pending.reserve(c.pending.size() + (size_t)len);
+    const int64_t base = c.pending_base;  // device_schedule copied the segment's pods there during its wait
+    for (int32_t i = 0; i < len; i++) {
+      const int32_t p = seg.s0 + i, node = chosen[p] - c.cfg.global_node_offset;
+      if (chosen[p] < 0 || node < 0 || node >= c.n_nodes) continue;
+      // LoadAware assign + NodeInfo.Requested: deferred (flush_mirror), the device rows carry them
+      c.pending.push_back({node, now, base + i});
+      // the allocations (read back only when the call's batches could make them): only a pod that has one touches the node
+      const uint64_t dev = c.last.dev(i);
+      const int64_t* numa = c.last.numa(i);
+      const uint64_t* cs = c.last.cpuset(i);
+      const bool cpus = cs && (cs[0] | cs[1] | cs[2] | cs[3]);
+      if (!dev && !numa && !cpus) continue;
+      mirror_join(c);  // (the earlier calls' mirror may still be running on its thread)
+      NodeState& ns = c.nodes[node];
+      const bool was_dirty = ns.dirty;
+      if (dev) host_ds_reserve(c.cfg, ns, make_dev_pod(c.cfg, pods[p], pod_hints(c, pods[p]), &c.tmpl), dev, c.last.vf(i));
+      if (numa) host_numa_reserve(ns, numa);
+      ns.dirty = was_dirty;  // the device rows already carry these Reserves
+      // cpuset Reserve: the CPU table and the zones' NUMA status (not patched on the device: re-derived from this mirror)
+      if (cpus) host_cpuset_reserve(ns, make_dev_pod(c.cfg, pods[p]), cs);
+    }
+    c.host_ms[7] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
+  }
+
+  // ElasticQuota: a Reserve into the system / default quota (limit_is_max) with runtime quota on shrinks
+  // totalResourceExceptSystemAndDefaultUsed (group_quota_manager.go:268-271, 127-151) and every later pod sees limits
+  // refreshed from it: the host takes the device's used, shrinks the total by the pod's masked request and recomputes
+  int refresh_quota() {
+    const ke_pod& pod = pods[seg.s1 - 1];
+    if (!seg.barrier || chosen[seg.s1 - 1] < 0) return KE_OK;
+    if (int rc = device_quota_sync(&c)) return rc;
+    const ke_quota& q = c.quotas[(size_t)pod.quota - 1];
+    c.qargs.total[0] -= q.has_max[0] ? pod.requests[KE_RES_CPU] : 0;
+    c.qargs.total[1] -= q.has_max[1] ? pod.requests[KE_RES_MEMORY] : 0;
+    const int rc = quota_compute_limits(c.qargs, c.quotas, c.qlimit, c.qlimit_has);
+    if (!rc) c.quota_dirty = true;
+    return rc;
+  }
+};
 
 extern "C" {
 
@@ -1210,27 +1374,11 @@ int ke_quota_state(ke_ctx* ctx, int32_t q, int64_t* limit, uint8_t* limit_has, i
   return KE_OK;
 }
 
-int ke_last_cpusets(ke_ctx* ctx, int32_t n, uint64_t* out) {
-  if (!ctx || n < 0 || (n > 0 && !out)) return fail(KE_ERR_INVALID, "ke_last_cpusets arguments");
-  const auto& a = ctx->c.last_cpusets;
-  for (int64_t i = 0; i < (int64_t)n * 4; i++) out[i] = i < (int64_t)a.size() ? a[i] : 0;
-  return KE_OK;
-}
+int ke_last_cpusets(ke_ctx* ctx, int32_t n, uint64_t* out) { return last_flat(ctx, n, out, &CallRecords::cpusets, "ke_last_cpusets arguments"); }
 
-int ke_last_numa_allocations(ke_ctx* ctx, int32_t n, int64_t* out) {
-  if (!ctx || n < 0 || (n > 0 && !out)) return fail(KE_ERR_INVALID, "ke_last_numa_allocations arguments");
-  const auto& a = ctx->c.last_numa_alloc;
-  constexpr int W = KE_MAX_NUMA * KE_NRES;
-  for (int64_t i = 0; i < (int64_t)n * W; i++) out[i] = i < (int64_t)a.size() ? a[i] : 0;
-  return KE_OK;
-}
+int ke_last_numa_allocations(ke_ctx* ctx, int32_t n, int64_t* out) { return last_flat(ctx, n, out, &CallRecords::numas, "ke_last_numa_allocations arguments"); }
 
-int ke_last_device_allocations(ke_ctx* ctx, int32_t n, uint64_t* minors) {
-  if (!ctx || n < 0 || (n > 0 && !minors)) return fail(KE_ERR_INVALID, "ke_last_device_allocations arguments");
-  const auto& a = ctx->c.last_dev_alloc;
-  for (int32_t i = 0; i < n; i++) minors[i] = i < (int32_t)a.size() ? a[i] : 0;
-  return KE_OK;
-}
+int ke_last_device_allocations(ke_ctx* ctx, int32_t n, uint64_t* minors) { return last_flat(ctx, n, minors, &CallRecords::devs, "ke_last_device_allocations arguments"); }
 
 int ke_node_set_requested(ke_ctx* ctx, int32_t node, int64_t milli_cpu, int64_t memory) {
   if (ctx) async_drain(ctx);
@@ -1504,335 +1652,61 @@ int ke_preempt(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, const int32_t* p
   return device_preempt(&c, n_pods, pods, pre.data(), now_ns, out, victims_cap, victim_uids, words_per_pod, candidates);
 }
 
+// check, plan (ke_segments.h), then per segment prepare -> device_schedule -> finish -> mirror -> append
 static int schedule_sync(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns, int32_t* chosen, int32_t* score) {
   if (!ctx || (n_pods > 0 && !chosen)) return fail(KE_ERR_INVALID, "ke_schedule arguments");
   using clk = std::chrono::steady_clock;
-  auto tp = clk::now();
-  ctx->c.call_entry = tp;  // every pod of the call is dequeued now (ke_last_pod_latencies)
-  // the staged ke_pod_reservations lists belong to this call, refused or not
-  auto refuse = [&](int r) {
-    ctx->c.match_off.clear();
-    ctx->c.match_ids.clear();
-    return r;
-  };
-  int rc = check_pods(pods, n_pods, &ctx->c, true);
-  if (rc) return refuse(rc);
-  rc = check_numa_deviceshare(ctx, pods, n_pods);
-  if (rc) return refuse(rc);
-  rc = check_cpuset(ctx, pods, n_pods);
-  if (rc) return refuse(rc);
-  for (int32_t p = 0; p < n_pods; p++)
-    if (pods[p].quota < 0 || pods[p].quota > (int32_t)ctx->c.quotas.size())
-      return refuse(fail(KE_ERR_INVALID, "ke_pod.quota outside the loaded ElasticQuota tree"));
-  rc = check_matches(ctx->c, pods, n_pods);
-  if (rc) return refuse(rc);
-  rc = require_device(ctx);
-  if (rc) return refuse(rc);
-  ctx->c.host_ms[0] = std::chrono::duration<double, std::milli>(clk::now() - tp).count();
+  const auto tp = clk::now();
   Context& c = ctx->c;
-  // ElasticQuota: a Reserve into the system / default quota (limit_is_max) with runtime quota on
-  // shrinks totalResourceExceptSystemAndDefaultUsed (updateClusterTotalResourceNoLock,
-  // group_quota_manager.go:268-271, 127-151), and every later pod sees runtime limits refreshed from it.
-  // The queue is cut after each such pod; between the segments the host takes the device's used,
-  // shrinks the total by the pod's masked request and recomputes the limits (uploaded by the next
-  // segment).  Without such pods the queue is one segment.
-  auto barrier = [&](int32_t p) {
-    if (c.quotas.empty() || !c.qargs.enable_runtime_quota || pods[p].quota <= 0) return false;
-    return c.quotas[(size_t)pods[p].quota - 1].limit_is_max != 0;
-  };
-  std::vector<uint64_t> all_dev, all_cs;
-  std::vector<int8_t> all_vf;
-  std::vector<int64_t> all_numa;
-  std::vector<double> all_batch_ms, all_lat;
-  double all_ms = 0;
-  bool numa_out = false, multi = false;
-  const int32_t off = c.cfg.global_node_offset;
-  // A pod with matched reservations (KE_RSV_MATCHED with a non-empty list) is a segment of its own: its
-  // rows carry its matched restore and k_rsv_pick adds the Reservation score (resv_prepare / resv_finish).
-  std::vector<int32_t> moff, mids;
-  moff.swap(c.match_off);  // consumed by this call
-  mids.swap(c.match_ids);
-  auto matched = [&](int32_t p) {
-    return pods[p].reservation_matched == KE_RSV_AFFINITY ||
-           (!moff.empty() && moff[(size_t)p + 1] > moff[(size_t)p]);
-  };
-  // A run of KE_RSV_IGNORED pods is a segment of its own: its rows carry every reservation's matched restore.
-  // An ignored pod that may bind CPUs beside CPU-holding reservations is alone too (its trials read the state).
-  auto ignored = [&](int32_t p) { return pods[p].reservation_matched == KE_RSV_IGNORED; };
-  auto ign_views = [&](int32_t p) { return ignored(p) && resv_ignore_needs_views(c, pods[p], c.staged[(size_t)p].flags); };
-  auto alone = [&](int32_t p) { return matched(p) || ign_views(p); };
-  std::vector<int32_t> assumed((size_t)n_pods, 0);
-  c.last_rsv_fused = c.last_rsv_fused_gated = 0;
-  for (int32_t s0 = 0; s0 < n_pods || (n_pods == 0 && s0 == 0);) {
-    int32_t s1 = s0;
-    const bool ign = s0 < n_pods && ignored(s0);
-    while (s1 < n_pods && !barrier(s1) && !alone(s1) && ignored(s1) == ign) s1++;
-    // a barrier pod ends its segment; a matched one is alone
-    if (s1 < n_pods && (s1 == s0 || (!alone(s1) && barrier(s1) && ignored(s1) == ign))) s1++;
-    int32_t len = s1 - s0;
-    const bool rsv = len == 1 && matched(s0);
-    mirror_join(c);  // (the previous segment's host mirror thread: this one reads the node state)
-    if (ign) resv_ignore_begin(c);
-    if (ign && len == 1 && ign_views(s0)) {  // its trials on the current state, as the matched pods' below
-      flush_mirror(c);
-      resv_ignore_views(c, pods[s0]);
-      if (!c.rsv_views.empty()) {
-        rc = device_rsv_views(&c, pods[s0], now_ns, c.rsv_views, c.rsv_view_out);
-        if (rc) return resv_ignore_end(c), rc;
-      }
-      if (!c.numa_views.empty()) {  // NUMA policies: the hints over tryAllocateIgnoreReservation (k_numa_views)
-        rc = device_numa_views(&c, pods[s0], now_ns, c.numa_views, c.numa_view_out);
-        if (rc) return resv_ignore_end(c), rc;
-      }
-      resv_ds_views(c, pods[s0], nullptr, 0);  // DeviceShare's ignore / own views (k_ds_views)
-      if (!c.ds_views.empty()) {
-        rc = device_ds_views(&c, pods[s0], now_ns, c.ds_views, c.ds_view_out);
-        if (rc) return resv_ignore_end(c), rc;
-      }
-      resv_ignore_ovr(c);
-      if (!c.numa_cs_views.empty()) {  // its cpuset and Score on the Filter's affinity
-        rc = device_rsv_views(&c, pods[s0], now_ns, c.numa_cs_views, c.numa_cs_out);
-        if (rc) return resv_ignore_end(c), rc;
-        resv_numa_cs_apply(c);
-      }
-    }
-    if (rsv) {
-      const int32_t* ids = mids.data() + moff[(size_t)s0];
-      const int32_t n_ids = moff[(size_t)s0 + 1] - moff[(size_t)s0];
-      resv_views(c, pods[s0], ids, n_ids);  // allocate-from-reservation trials on the current state first
-      if (!c.rsv_views.empty()) {
-        rc = device_rsv_views(&c, pods[s0], now_ns, c.rsv_views, c.rsv_view_out);
-        if (rc) return rc;
-      }
-      resv_ds_views(c, pods[s0], ids, n_ids);  // DeviceShare's trials, on the rows with the pod's matched restore
-      if (!c.ds_views.empty()) {
-        rc = device_ds_views(&c, pods[s0], now_ns, c.ds_views, c.ds_view_out);
-        if (rc) {
-          for (const DsView& v : c.ds_views) resv_node_restore(c, v.node);
-          c.ds_views.clear();
-          return rc;
-        }
-      }
-      resv_numa_views(c, pods[s0], ids, n_ids);  // NodeNUMAResource's hints over the trials (NUMA policies)
-      if (!c.numa_views.empty()) {
-        rc = device_numa_views(&c, pods[s0], now_ns, c.numa_views, c.numa_view_out);
-        if (rc) {
-          for (const NumaRsvView& v : c.numa_views) resv_node_restore(c, v.node);
-          for (const DsView& v : c.ds_views) resv_node_restore(c, v.node);
-          c.numa_views.clear();
-          c.ds_views.clear();
-          return rc;
-        }
-      }
-      rc = resv_prepare(c, pods[s0], ids, n_ids, pods[s0].reservation_matched == KE_RSV_AFFINITY);
-      if (rc) return rc;
-      if (!c.numa_cs_views.empty()) {  // a binding pod's cpuset of the nominated reservation (NUMA policies)
-        rc = device_rsv_views(&c, pods[s0], now_ns, c.numa_cs_views, c.numa_cs_out);
-        if (rc) {
-          int32_t dummy = 0;
-          resv_finish(c, -1, pods[s0], &dummy);
-          return rc;
-        }
-        resv_numa_cs_apply(c);
-      }
-    }
-    // a device failure leaves the pods of earlier segments Reserved on the device and the context's state
-    // undefined (KE_ERR_DEVICE: rebuild the context); the matched-restore state is still undone so the
-    // reservation's capacity does not stay visible to later calls
-    auto undo_rsv = [&]() {
-      int32_t dummy = 0;
-      if (rsv) resv_finish(c, -1, pods[s0], &dummy);
-      if (ign) resv_ignore_end(c);
-    };
-    // A plain segment followed by a matched pod without allocate-from-reservation views or decisions (DESIGN.md §4k,
-    // "fused"): the pod's nomination and rows are taken now, on the state before the segment, and it runs last in the
-    // segment's call -- k_rsv_check gates it on the device when a plain pod of the segment took a node of its
-    // reservations, and the host then runs it as a segment of its own.
-    bool fuse = kFuseMatched && !ign && !rsv && len >= 1 && s1 < n_pods && pods[s1].reservation_matched == KE_RSV_MATCHED &&
-                matched(s1) && c.quotas.empty() && !device_sharded(&c) && (size_t)s1 < c.staged.size() &&
-                !(c.staged[(size_t)s1].flags & (PF_CPUSET | PF_DS | PF_DS_HINT));
-    if (fuse) {
-      rc = device_refresh(&c, now_ns, false);  // the segment's rows (no host wait)
-      if (rc) return rc;
-      const int32_t* ids = mids.data() + moff[(size_t)s1];
-      const int32_t n_ids = moff[(size_t)s1 + 1] - moff[(size_t)s1];
-      resv_views(c, pods[s1], ids, n_ids);
-      fuse = c.rsv_views.empty();
-      if (fuse) {
-        resv_ds_views(c, pods[s1], ids, n_ids);
-        fuse = c.ds_views.empty();
-      }
-      if (fuse) {
-        resv_numa_views(c, pods[s1], ids, n_ids);
-        fuse = c.numa_views.empty();
-      }
-      if (!fuse) {  // its own segment after all: the views' rows back as they were
-        for (const DsView& v : c.ds_views) resv_node_restore(c, v.node);
-        for (const NumaRsvView& v : c.numa_views) resv_node_restore(c, v.node);
-        int32_t dummy = 0;
-        resv_finish(c, -1, pods[s1], &dummy);
-      } else {
-        rc = resv_prepare(c, pods[s1], ids, n_ids, false);
-        if (rc) return rc;
-        if (!c.rsv_ovr.empty() || !c.numa_cs_views.empty()) {
-          int32_t dummy = 0;
-          resv_finish(c, -1, pods[s1], &dummy);
-          fuse = false;
-        }
-      }
-    }
-    c.rsv_fused = fuse;
-    rc = device_schedule(&c, fuse ? len + 1 : len, pods + s0, now_ns, chosen + (n_pods ? s0 : 0), score ? score + s0 : nullptr);
-    c.rsv_fused = false;
-    if (rc && fuse) {
-      int32_t dummy = 0;
-      resv_finish(c, -1, pods[s1], &dummy);
-    }
-    if (rc) return undo_rsv(), rc;
-    if (ign) resv_ignore_end(c);
-    if (fuse && device_rsv_gate(&c)) {
-      // a plain pod took a node of the fused pod's reservations: the pod placed nothing; its nomination and rows are
-      // undone and it runs next as a segment of its own (the call's per-pod outputs: the segment's only)
-      int32_t dummy = 0;
-      resv_finish(c, -1, pods[s1], &dummy);
-      chosen[s1] = -1;
-      auto cut = [&](auto& v, size_t per) {
-        if (v.size() > per * (size_t)len) v.resize(per * (size_t)len);
-      };
-      cut(c.last_dev_alloc, 1);
-      cut(c.last_cpusets, 4);
-      cut(c.last_vf, 2 * KE_MAX_MINORS);
-      cut(c.last_numa_alloc, (size_t)KE_MAX_NUMA * KE_NRES);
-      cut(c.last_pod_lat, 1);
-      if (!c.last_batch_ms.empty()) c.last_batch_ms.pop_back();
-      c.last_rsv_fused_gated++;
-      fuse = false;
-    } else if (fuse) {  // the Reservation plugin's outcome of the fused pod, as for a matched segment below
-      const int32_t local = chosen[s1] < 0 ? -1 : chosen[s1] - off;
-      int32_t pick[4] = {local, 0, 0, -1};
-      if (!c.rsv_pairs.empty()) rc = device_rsv_result(&c, pick);
-      if (!rc && local >= 0 && local != pick[0]) rc = fail(KE_ERR_DEVICE, "k_rsv_pick winner differs from the placement");
-      if (rc) {
-        int32_t dummy = 0;
-        resv_finish(c, -1, pods[s1], &dummy);
-        return rc;
-      }
-      if (local >= 0 && score) score[s1] = (int32_t)((int64_t)score[s1] + c.cfg.weight_reservation * (int64_t)pick[1]);
-      const size_t L = (size_t)len;
-      resv_finish(c, local, pods[s1], &assumed[(size_t)s1],
-                  c.last_cpusets.size() >= 4 * (L + 1) ? c.last_cpusets.data() + 4 * L : nullptr,
-                  c.last_numa_alloc.size() >= (L + 1) * KE_MAX_NUMA * KE_NRES ? c.last_numa_alloc.data() + L * KE_MAX_NUMA * KE_NRES : nullptr,
-                  c.last_dev_alloc.size() > L ? c.last_dev_alloc[L] : 0);
-      c.last_rsv_fused++;
-      len++;
-      s1++;
-    }
-    if (rsv) {
-      const int32_t local = chosen[s0] < 0 ? -1 : chosen[s0] - off;
-      int32_t pick[4] = {local, 0, 0, -1};  // no usable matched reservation: no Reservation score
-      if (!c.rsv_pairs.empty() || c.rsv_affinity) rc = device_rsv_result(&c, pick);
-      if (rc) return undo_rsv(), rc;
-      if (local >= 0 && local != pick[0])
-        return undo_rsv(), fail(KE_ERR_DEVICE, "k_rsv_pick winner differs from the placement");
-      if (local >= 0 && score) score[s0] = (int32_t)((int64_t)score[s0] + c.cfg.weight_reservation * (int64_t)pick[1]);
-      resv_finish(c, local, pods[s0], &assumed[(size_t)s0], c.last_cpusets.size() >= 4 ? c.last_cpusets.data() : nullptr,
-                  c.last_numa_alloc.size() >= (size_t)(KE_MAX_NUMA * KE_NRES) ? c.last_numa_alloc.data() : nullptr,
-                  c.last_dev_alloc.empty() ? 0 : c.last_dev_alloc[0]);
-    }
-    if (n_pods == 0) break;
-    tp = clk::now();
-    // Host mirror of the Reserves the device already applied to its rows: keep the object state
-    // (assign cache, NodeInfo.Requested) in step so later re-derivations include these pods.
-    c.pending.reserve(c.pending.size() + (size_t)len);
-    const int64_t base = c.pending_base;  // device_schedule copied pods[s0 .. s1) there during its wait
-    for (int32_t i = 0; i < len; i++) {
-      const int32_t p = s0 + i;
-      const int32_t node = chosen[p] - off;
-      if (chosen[p] < 0 || node < 0 || node >= c.n_nodes) continue;
-      // LoadAware assign + NodeInfo.Requested: deferred (flush_mirror), the device rows carry them
-      c.pending.push_back({node, now_ns, base + i});
-      // the allocations (read back only when the call's batches could make them): the node's state is touched
-      // only for a pod that has one
-      const bool dev = i < (int32_t)c.last_dev_alloc.size() && c.last_dev_alloc[i];
-      const bool numa = (int64_t)c.last_numa_alloc.size() >= (int64_t)(i + 1) * KE_MAX_NUMA * KE_NRES;
-      const uint64_t* cs = (int64_t)c.last_cpusets.size() >= (int64_t)(i + 1) * 4 ? &c.last_cpusets[(size_t)i * 4] : nullptr;
-      const bool cpus = cs && (cs[0] | cs[1] | cs[2] | cs[3]);
-      if (!dev && !numa && !cpus) continue;
-      mirror_join(c);  // (the earlier calls' mirror may still be running on its thread)
-      NodeState& ns = c.nodes[node];
-      const bool was_dirty = ns.dirty;
-      if (dev)
-        host_ds_reserve(c.cfg, ns, make_dev_pod(c.cfg, pods[p], pod_hints(c, pods[p]), &c.tmpl), c.last_dev_alloc[i],
-                        (int64_t)c.last_vf.size() >= (int64_t)(i + 1) * 2 * KE_MAX_MINORS ? &c.last_vf[(size_t)i * 2 * KE_MAX_MINORS] : nullptr);
-      if (numa) host_numa_reserve(ns, &c.last_numa_alloc[(size_t)i * KE_MAX_NUMA * KE_NRES]);
-      ns.dirty = was_dirty;  // the device rows already carry these Reserves
-      // cpuset Reserve: the CPU table (the device one is patched too) and the zones' NUMA status (not
-      // patched on the device: re-derived from this mirror)
-      if (cpus) host_cpuset_reserve(ns, make_dev_pod(c.cfg, pods[p]), cs);
-    }
-    c.host_ms[7] += std::chrono::duration<double, std::milli>(clk::now() - tp).count();
-    const bool whole = s0 == 0 && s1 == n_pods;  // one segment: the last_* outputs are already whole
-    if (!whole) {
-      c.last_dev_alloc.resize((size_t)len, 0);  // (a segment without DeviceShare batches reads none back)
-      c.last_cpusets.resize((size_t)len * 4, 0);
-      all_dev.insert(all_dev.end(), c.last_dev_alloc.begin(), c.last_dev_alloc.end());
-      if (c.last_vf.empty()) all_vf.resize(all_vf.size() + (size_t)len * 2 * KE_MAX_MINORS, -1);
-      else all_vf.insert(all_vf.end(), c.last_vf.begin(), c.last_vf.end());
-      all_cs.insert(all_cs.end(), c.last_cpusets.begin(), c.last_cpusets.end());
-      numa_out = numa_out || !c.last_numa_alloc.empty();
-      if (c.last_numa_alloc.empty()) all_numa.resize(all_numa.size() + (size_t)len * KE_MAX_NUMA * KE_NRES, 0);
-      else all_numa.insert(all_numa.end(), c.last_numa_alloc.begin(), c.last_numa_alloc.end());
-      all_batch_ms.insert(all_batch_ms.end(), c.last_batch_ms.begin(), c.last_batch_ms.end());
-      all_lat.insert(all_lat.end(), c.last_pod_lat.begin(), c.last_pod_lat.end());
-      all_ms += c.last_total_ms;
-    }
-    // the placed system / default pod (also when it ends the only segment): refresh the runtime
-    if (barrier(s1 - 1) && chosen[s1 - 1] >= 0) {
-      rc = device_quota_sync(&c);
-      if (rc) return rc;
-      const ke_quota& q = c.quotas[(size_t)pods[s1 - 1].quota - 1];
-      c.qargs.total[0] -= q.has_max[0] ? pods[s1 - 1].requests[KE_RES_CPU] : 0;
-      c.qargs.total[1] -= q.has_max[1] ? pods[s1 - 1].requests[KE_RES_MEMORY] : 0;
-      rc = quota_compute_limits(c.qargs, c.quotas, c.qlimit, c.qlimit_has);
-      if (rc) return rc;
-      c.quota_dirty = true;
-    }
-    if (whole) break;
-    s0 = s1;
-    multi = true;
-  }
-  if (multi) {
-    c.last_dev_alloc.swap(all_dev);
-    c.last_vf.swap(all_vf);
-    c.last_cpusets.swap(all_cs);
-    if (numa_out) c.last_numa_alloc.swap(all_numa);
-    else c.last_numa_alloc.clear();
-    c.last_batch_ms.swap(all_batch_ms);
-    c.last_pod_lat.swap(all_lat);
-    c.last_total_ms = all_ms;
-  }
-  // release records of this call (ke_last_allocations / ke_unreserve)
-  c.last_chosen.assign(chosen, chosen + n_pods);
-  c.last_uid.resize((size_t)n_pods);
-  c.last_quota.resize((size_t)n_pods);
-  c.last_resv.swap(assumed);
+  c.call_entry = tp;  // every pod of the call is dequeued now (ke_last_pod_latencies)
+  int rc;  // every refusal is raised before any pod is scheduled
+  if ((rc = check_pods(pods, n_pods, &c, true)) || (rc = check_numa_deviceshare(ctx, pods, n_pods)) ||
+      (rc = check_cpuset(ctx, pods, n_pods)))
+    return rc;
+  for (int32_t p = 0; p < n_pods; p++)
+    if (pods[p].quota < 0 || pods[p].quota > (int32_t)c.quotas.size())
+      return fail(KE_ERR_INVALID, "ke_pod.quota outside the loaded ElasticQuota tree");
+  if ((rc = check_matches(c, pods, n_pods)) || (rc = require_device(ctx))) return rc;
+  c.host_ms[0] = std::chrono::duration<double, std::milli>(clk::now() - tp).count();
+  std::vector<uint8_t> cls((size_t)n_pods, 0);  // PodClass bits
+  const bool barriers = !c.quotas.empty() && c.qargs.enable_runtime_quota;
   for (int32_t p = 0; p < n_pods; p++) {
-    c.last_uid[(size_t)p] = pods[p].uid;
-    c.last_quota[(size_t)p] = chosen[p] >= 0 && pods[p].quota > 0 && !c.quotas.empty();
+    const bool ignored = pods[p].reservation_matched == KE_RSV_IGNORED;
+    const bool matched = pods[p].reservation_matched == KE_RSV_AFFINITY ||
+                         (!c.match_off.empty() && c.match_off[(size_t)p + 1] > c.match_off[(size_t)p]);
+    if (barriers && pods[p].quota > 0 && c.quotas[(size_t)pods[p].quota - 1].limit_is_max) cls[(size_t)p] |= PC_BARRIER;
+    if (matched || (ignored && resv_ignore_needs_views(c, pods[p], c.staged[(size_t)p].flags))) cls[(size_t)p] |= PC_ALONE;
+    if (ignored) cls[(size_t)p] |= PC_IGNORED;
   }
+  const std::vector<Segment> segs = plan_segments(n_pods, cls.data());
+  CallRecords all;  // the segments' records joined; resv: what each matched pod was assumed into
+  CallTimes times;
+  all.resv.assign((size_t)n_pods, 0);
+  c.last_rsv_fused = c.last_rsv_fused_gated = 0;
+  for (size_t k = 0; k < segs.size(); k++) {
+    SegmentRun run{c, pods, n_pods, now_ns, chosen, score, all.resv.data(), cls.data(), segs[k]};
+    if ((rc = run.prepare()) || (rc = run.schedule()) || (rc = run.finish())) return rc;
+    if (n_pods == 0) break;  // (the empty call still refreshes the rows)
+    run.mirror();
+    all.append(c.last, (size_t)run.len);
+    times.add(c.last_total_ms, c.last_batch_ms, c.last_pod_lat);
+    if ((rc = run.refresh_quota())) return rc;
+    k += run.fuse;  // (the next segment was the fused pod)
+  }
+  all.set_pods(n_pods, chosen, pods, !c.quotas.empty(), c.resv_gen);
+  c.last = std::move(all);
+  c.last_total_ms = times.total_ms;
+  c.last_batch_ms.swap(times.batch_ms);
+  c.last_pod_lat.swap(times.pod_lat);
   return KE_OK;
 }
 
 int ke_schedule(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns, int32_t* chosen, int32_t* score) {
-  if (ctx) async_drain(ctx);
-  if (ctx) {
-    const int rc = take_node_sets(ctx, n_pods, pods, true);
-    if (rc) {  // (the staged ke_pod_reservations lists belong to this call too)
-      ctx->c.match_off.clear();
-      ctx->c.match_ids.clear();
-      return rc;
-    }
-  }
+  if (!ctx) return fail(KE_ERR_INVALID, "ke_schedule arguments");
+  async_drain(ctx);
+  const StagedMatches consumed{ctx->c};
+  const int rc = take_node_sets(ctx, n_pods, pods, true);
+  if (rc) return rc;
   return schedule_sync(ctx, n_pods, pods, now_ns, chosen, score);
 }
 
@@ -1840,13 +1714,10 @@ int ke_schedule_submit(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t 
   if (!ctx || n_pods < 0 || (n_pods > 0 && !pods) || !ticket) return fail(KE_ERR_INVALID, "ke_schedule_submit arguments");
   using clk = std::chrono::steady_clock;
   Context& c = ctx->c;
+  const StagedMatches consumed{c};
   {
     const int rc = take_node_sets(ctx, n_pods, pods, true);
-    if (rc) {
-      c.match_off.clear();
-      c.match_ids.clear();
-      return rc;
-    }
+    if (rc) return rc;
   }
   int in_flight = 0;
   for (const AsyncCall& a : ctx->async) in_flight += a.fin != nullptr;
@@ -1904,7 +1775,7 @@ int ke_schedule_submit(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t 
   a.score.assign((size_t)n_pods, 0);
   const int rc = schedule_sync(ctx, n_pods, pods, now_ns, a.chosen.data(), a.score.data());
   if (rc) return rc;
-  a.rec.save(c);
+  a.rec = c.last;
   *ticket = a.ticket;
   ctx->async.push_back(std::move(a));
   return KE_OK;
@@ -1924,35 +1795,13 @@ int ke_schedule_wait(ke_ctx* ctx, int64_t ticket, int32_t* chosen, int32_t* scor
   if (score) std::copy(a.score.begin(), a.score.end(), score);
   // release records of this call (ke_last_allocations / ke_unreserve): the last collected call, device-enqueued
   // or run at once alike
-  a.rec.restore(ctx->c);
+  ctx->c.last.restore(std::move(a.rec), ctx->c.resv_gen);
   return KE_OK;
-}
-
-// the release record of position p of the last ke_schedule
-static ke_pod_allocation last_allocation(const Context& c, int32_t p) {
-  ke_pod_allocation a{};
-  memset(a.vf_rank, -1, sizeof a.vf_rank);
-  a.node = p < (int32_t)c.last_chosen.size() ? c.last_chosen[(size_t)p] : -1;
-  if (a.node < 0) return a;
-  a.reservation = p < (int32_t)c.last_resv.size() ? c.last_resv[(size_t)p] : 0;
-  a.reservation_generation = c.resv_gen;
-  a.reservation_uid = a.reservation > 0 ? c.resv[(size_t)a.reservation - 1].uid : 0;
-  a.quota_assigned = c.last_quota[(size_t)p];
-  constexpr int W = KE_MAX_NUMA * KE_NRES;
-  for (int q = 0; q < 4; q++)
-    a.cpuset[q] = (int64_t)c.last_cpusets.size() >= (int64_t)(p + 1) * 4 ? c.last_cpusets[(size_t)p * 4 + q] : 0;
-  for (int w = 0; w < W; w++)
-    a.numa[w] = (int64_t)c.last_numa_alloc.size() >= (int64_t)(p + 1) * W ? c.last_numa_alloc[(size_t)p * W + w] : 0;
-  a.device_minors = p < (int32_t)c.last_dev_alloc.size() ? c.last_dev_alloc[(size_t)p] : 0;
-  for (int k = 0; k < 2 * KE_MAX_MINORS; k++)
-    a.vf_rank[k / KE_MAX_MINORS][k % KE_MAX_MINORS] =
-        (int64_t)c.last_vf.size() >= (int64_t)(p + 1) * 2 * KE_MAX_MINORS ? c.last_vf[(size_t)p * 2 * KE_MAX_MINORS + k] : (int8_t)-1;
-  return a;
 }
 
 int ke_last_allocations(ke_ctx* ctx, int32_t n, ke_pod_allocation* out) {
   if (!ctx || n < 0 || (n > 0 && !out)) return fail(KE_ERR_INVALID, "ke_last_allocations arguments");
-  for (int32_t p = 0; p < n; p++) out[p] = last_allocation(ctx->c, p);
+  for (int32_t p = 0; p < n; p++) out[p] = ctx->c.last.allocation(p, ctx->c.resv_gen, ctx->c.resv);
   return KE_OK;
 }
 
@@ -2003,14 +1852,14 @@ int ke_unreserve(ke_ctx* ctx, const ke_pod* pod, int32_t queue_pos) {
   if (ctx) async_drain(ctx);
   if (!ctx || !pod) return fail(KE_ERR_INVALID, "ke_unreserve arguments");
   Context& c = ctx->c;
-  if (queue_pos < 0 || queue_pos >= (int32_t)c.last_chosen.size())
+  if (queue_pos < 0 || queue_pos >= (int32_t)c.last.chosen.size())
     return fail(KE_ERR_NOT_FOUND, "ke_unreserve: no such position in the last ke_schedule");
-  if (c.last_uid[(size_t)queue_pos] != pod->uid) return fail(KE_ERR_INVALID, "ke_unreserve: pod uid differs from the queue's");
-  if (c.last_chosen[(size_t)queue_pos] < 0) return KE_OK;  // not placed, or already unreserved
-  const ke_pod_allocation a = last_allocation(c, queue_pos);
+  if (c.last.uid[(size_t)queue_pos] != pod->uid) return fail(KE_ERR_INVALID, "ke_unreserve: pod uid differs from the queue's");
+  if (c.last.chosen[(size_t)queue_pos] < 0) return KE_OK;  // not placed, or already unreserved
+  const ke_pod_allocation a = c.last.allocation(queue_pos, c.resv_gen, c.resv);
   const int rc = ke_pod_release(ctx, pod, &a, KE_RELEASE_UNRESERVE);
   if (rc) return rc;
-  c.last_chosen[(size_t)queue_pos] = -1;
+  c.last.chosen[(size_t)queue_pos] = -1;
   return KE_OK;
 }
 

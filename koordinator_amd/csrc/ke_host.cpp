@@ -810,7 +810,7 @@ int load_reservations(Context& c, int32_t n, const ke_reservation* rs, const ke_
   for (int32_t i = 0; i < n; i++) c.resv_by_node[(size_t)rs[i].node].push_back(i);
   for (int32_t node : old) resv_node_restore(c, node);  // the old restore leaves
   for (const ke_reservation& r : c.resv) resv_node_restore(c, r.node);
-  c.last_resv.clear();  // release records of earlier calls no longer name these reservations
+  c.last.resv.clear();  // release records of earlier calls no longer name these reservations
   c.resv_gen++;
   return KE_OK;
 }

@@ -14,6 +14,7 @@
 #include "../../include/koord_eval.h"
 #include "ke_attach.h"
 #include "ke_preempt.h"
+#include "ke_segments.h"
 #include "ke_types.h"
 
 namespace ke {
@@ -145,20 +146,15 @@ struct Context {
   bool ext_enabled = false;      // NodeResourcesFitPlus / ScarceResourceAvoidance in the profile: the ext SoA exists
   int32_t n_bind_nodes = 0;      // nodes with a CPU bind policy (a cpu request may bind CPUs there)
   int32_t n_policy_nodes = 0;    // nodes with a NUMA topology policy
-  std::vector<uint64_t> last_cpusets;    // per pod of the last ke_schedule: 4 words (CPU-id bitset)
-  std::vector<int64_t> last_numa_alloc;  // per pod of the last ke_schedule: [KE_MAX_NUMA*KE_NRES]
-  std::vector<uint64_t> last_dev_alloc;  // per pod of the last ke_schedule
-  // per pod of the last ke_schedule: the chosen node (-1 once unreserved), the pod uid and whether its
-  // ElasticQuota Reserve ran (ke_last_allocations / ke_unreserve)
-  std::vector<int32_t> last_chosen;
-  std::vector<int64_t> last_uid;
-  std::vector<uint8_t> last_quota;
+  // the per-pod outputs of the last ke_schedule (ke_segments.h; ke_last_allocations / ke_unreserve); while a call
+  // runs, the device-made kinds of its current segment
+  CallRecords last;
   DeviceState* dev = nullptr;
   // last ke_schedule timing
   double last_total_ms = 0.0;
   std::vector<double> last_batch_ms;
   double kstat_eval_ms = 0, kstat_select_ms = 0, kstat_resolve_ms = 0, kstat_fixup_ms = 0, kstat_handoff_ms = 0;
-  int32_t last_pipelined = 0;
+  int32_t last_pipelined = 0;  // batches of the last ke_schedule that ran pipelined (two streams)
   // ke_debug_call_boundary of the last completed device call; call_behind: the call being enqueued follows one
   // still in flight (ke_schedule_submit sets it); prev_end_tick: the last completed call's final batch end stamp
   int64_t call_boundary[4] = {0, 0, 0, 0};
@@ -170,7 +166,7 @@ struct Context {
   double last_enqueue_ms = 0;  // host time spent enqueueing the last ke_schedule's launches
   // host wall ms of the last ke_schedule by phase: argument checks, row refresh, pod upload, launch
   // setup, enqueue, wait for the device, statistics readback, host mirror of the Reserves
-  double host_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // batches of the last ke_schedule that ran pipelined (two streams)
+  double host_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double kstat_resolve_prologue_ms = 0, kstat_resolve_loop_ms = 0;
   double kstat_resolve_phase_ms[6] = {0, 0, 0, 0, 0, 0};
   double kstat_resolve_sub_ms[5] = {0, 0, 0, 0, 0};  // ke_debug_resolve_subphases
@@ -282,8 +278,8 @@ struct Context {
   std::vector<RsvPair> rsv_pairs;
   std::vector<int32_t> rsv_nominated;
   bool rsv_affinity = false;  // the segment's pod has a required reservation affinity
-  bool rsv_fused = false;
-  int64_t last_rsv_fused = 0, last_rsv_fused_gated = 0;  // fused matched pods placed / gated (statistics)     // the call's last pod is a matched pod fused behind plain pods (ke_schedule)
+  bool rsv_fused = false;  // the call's last pod is a matched pod fused behind plain pods (ke_schedule)
+  int64_t last_rsv_fused = 0, last_rsv_fused_gated = 0;  // fused matched pods placed / gated (statistics)
   std::vector<RsvOvr> rsv_ovr;  // its allocate-from-reservation decisions per node (SoA::rovr)
   // its allocate-from-reservation trials (resv_views -> k_rsv_views): per view the reservation and the outcome
   std::vector<RsvView> rsv_views;
@@ -305,8 +301,7 @@ struct Context {
   std::vector<RsvView> numa_cs_views;
   std::vector<int32_t> numa_cs_ovr, numa_cs_pair;
   std::vector<RsvViewOut> numa_cs_out;
-  std::vector<int32_t> last_resv;  // per pod of the last ke_schedule: 1 + the reservation assumed, 0 = none
-  int32_t resv_gen = 0;            // ke_reservations_generation: bumped by every load_reservations
+  int32_t resv_gen = 0;  // ke_reservations_generation: bumped by every load_reservations
   // per-pod latency of the last ke_schedule (ke_last_pod_latencies): the call's entry on the host clock, and
   // per pod the ms from it to its batch's Reserve end
   std::chrono::steady_clock::time_point call_entry{};
@@ -319,7 +314,6 @@ struct Context {
   std::vector<std::vector<std::pair<int32_t, int32_t>>> label_sets{{}};
   std::map<std::vector<std::pair<int32_t, int32_t>>, int> label_set_ids{{{}, 0}};
   std::vector<int32_t> model_keys{0};
-  std::vector<int8_t> last_vf;  // [pod][2][KE_MAX_MINORS]
 };
 
 // the hint record of a pod (nullptr: none); the index was validated by validate_pod_hints

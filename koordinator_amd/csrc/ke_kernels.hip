@@ -9217,14 +9217,10 @@ static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
   std::memcpy(chosen, h + ho.chosen, 4 * np);
   if (score && c.want_score) std::memcpy(score, h + ho.score, 4 * np);
   // allocations none of the call's batches can make were not read back (readers take absent entries as zero)
-  ctx->last_dev_alloc.assign(reinterpret_cast<const uint64_t*>(h + ho.dev),
-                             reinterpret_cast<const uint64_t*>(h + ho.dev) + (c.any_ds ? np : 0));
-  ctx->last_cpusets.assign(reinterpret_cast<const uint64_t*>(h + ho.cs),
-                           reinterpret_cast<const uint64_t*>(h + ho.cs) + (c.any_cpu ? 4 * np : 0));
-  ctx->last_vf.assign(reinterpret_cast<const int8_t*>(h + ho.vf),
-                      reinterpret_cast<const int8_t*>(h + ho.vf) + (c.vf_out ? 2 * DS_MINORS * np : 0));
-  ctx->last_numa_alloc.assign(reinterpret_cast<const int64_t*>(h + ho.numa),
-                              reinterpret_cast<const int64_t*>(h + ho.numa) + (c.numa ? 16 * np : 0));
+  ctx->last.fill_device(np, reinterpret_cast<const uint64_t*>(h + ho.dev), c.any_ds,
+                        reinterpret_cast<const uint64_t*>(h + ho.cs), c.any_cpu,
+                        reinterpret_cast<const int8_t*>(h + ho.vf), c.vf_out,
+                        reinterpret_cast<const int64_t*>(h + ho.numa), c.numa);
   int32_t herr = 0, kerr = 0;
   std::memcpy(&herr, h + ho.err, 4);
   std::memcpy(&kerr, h + ho.kerr, 4);
@@ -9905,7 +9901,7 @@ int device_schedule_enqueue(Context* ctx, int32_t n_pods, const ke_pod* pods, in
   if (rc) return rc;
   ctx->host_ms[1] = ms_since(tp);
   ctx->last_batch_ms.clear();
-  ctx->last_dev_alloc.clear();
+  ctx->last.clear_device();
   ctx->last_total_ms = 0;
   ctx->last_pod_lat.clear();
   if (n_pods == 0) return KE_OK;
