@@ -1676,6 +1676,63 @@ int ke_debug_node_state(ke_ctx* ctx, int32_t node, ke_node* out, int32_t cpu_cap
                         int32_t zone_cap, ke_numa_zone* zones, int32_t* n_zones, int32_t dev_cap, ke_device* devs,
                         int32_t* n_devs);
 
+/* ---- gangs: all-or-nothing pod groups rolled back inside the replay (additive: KE_ABI_VERSION stays 14) ----
+ * Coscheduling (pkg/scheduler/plugins/coscheduling/core/core.go) for ke_schedule, which replaces SchedulePod and owns
+ * Reserve.  A gang run is a contiguous stretch of a call's pods that belong to one gang (the queue sort and the
+ * GangSchedulingContext keep a gang's pods together).  `assumed` are the members the gang's match policy already
+ * counts from earlier cycles: waiting pods under only-waiting, waiting plus bound pods under waiting-and-running.  Pods
+ * of a gang that is already once-satisfied are passed without a run, as PreFilter passes them (core.go:280).
+ * With need = max(min_member - assumed, 0) the members are handled in queue order:
+ *  1. An earlier member of the run failed: the member is not tried (PreFilter returns the context's failedMessage,
+ *     core.go:295-297).  KE_GANG_SKIPPED, chosen = -1.
+ *  2. Otherwise it is scheduled exactly as any pod of the call: quota admission, Filter, Score, the pick, Reserve.
+ *  3. It is placed nowhere (no feasible node, or ElasticQuota's PreFilter refuses it): the run's failed member,
+ *     KE_GANG_FAILED (PostFilter, core.go:304-341).  KE_GANG_STRICT and the run not yet satisfied: every member of the
+ *     run placed so far is unreserved (rejectGangGroup -> Unreserve of every plugin): KE_GANG_ROLLED_BACK, chosen = -1,
+ *     the node it had in tried_node.  KE_GANG_NON_STRICT: nothing is undone.
+ *  4. It is placed: the waiting count goes up (Permit, core.go:346-374); once it reaches need the run is satisfied and
+ *     its placed members are KE_GANG_PLACED.  Later members of a satisfied run are ordinary pods: one that fits nowhere
+ *     is KE_GANG_FAILED and rolls nothing back (core.go:314-316).  Convention: Bind completes before the next member's
+ *     cycle, so setResourceSatisfied has happened.
+ *  5. The run ends unsatisfied without a failed member, or is non-strict after a failure: the placed members stay placed,
+ *     KE_GANG_WAITING (they sit in Permit; the timeout and the ke_unreserve are the caller's).
+ * Pods outside a run have status 0.  A pod behind a rolled-back run sees every row, record and quota figure as if the
+ * run had never been there.  Parity-unpinned (as NodeResourcesFit is): upstream's "PreFilter Unschedulable reaches
+ * PostFilter" is not in the reference tree; rule 3 treats a quota refusal as the member's PostFilter.
+ * Refused (KE_ERR_UNSUPPORTED unless noted): a run longer than ke_config.pod_batch; a member that is a DeviceShare,
+ * cpuset, hinted or NUMA-policy pod, reservation-matched / ignored, or a quota barrier (a limit_is_max quota with the
+ * runtime quota on); a context with NUMA policy state, CPU bind policy nodes or node shards; staged ke_pod_reservations
+ * lists; any spread kind in the call; an ElasticQuota tree together with node sets or score tables.  KE_ERR_INVALID:
+ * overlapping, unsorted or out-of-range runs, min_member < 1, assumed < 0, runs staged for a pod count that differs from the call's. */
+#define KE_GANG_STRICT 0
+#define KE_GANG_NON_STRICT 1
+#define KE_GANG_NONE 0
+#define KE_GANG_PLACED 1
+#define KE_GANG_WAITING 2
+#define KE_GANG_FAILED 3
+#define KE_GANG_SKIPPED 4
+#define KE_GANG_ROLLED_BACK 5
+typedef struct ke_gang_run {
+  int32_t first, count; /* pods [first, first + count) of the call */
+  int32_t min_member;   /* >= 1 */
+  int32_t assumed;      /* >= 0 */
+  int32_t mode;         /* KE_GANG_STRICT / KE_GANG_NON_STRICT */
+  int32_t reserved;     /* 0 */
+} ke_gang_run;
+/* The runs of the next ke_schedule / ke_schedule_submit of n_pods pods (ascending, disjoint), staged like
+ * ke_pod_node_sets and consumed by that call whether it goes on or not. */
+int ke_pod_gangs(ke_ctx* ctx, int32_t n_pods, int32_t n_runs, const ke_gang_run* runs);
+/* Per pod of the last ke_schedule (or the call ke_schedule_wait collected last): its KE_GANG_* status and, for a
+ * KE_GANG_ROLLED_BACK member, the node it had (ke_config.global_node_offset applied), else -1.  A call without runs
+ * answers 0 / -1. */
+int ke_last_gang_status(ke_ctx* ctx, int32_t n, int32_t* status, int32_t* tried_node);
+/* The last ke_schedule, or the call ke_schedule_wait collected last (the counters travel with the ticket, as the
+ * statuses do): out4[0] runs, out4[1] runs rolled back, out4[2] inverse Reserves applied on the device,
+ * out4[3] batches that ended early because the next run would not have fitted whole. */
+int ke_debug_gangs(ke_ctx* ctx, int64_t* out4);
+/* sizeof() of {ke_gang_run}; returns their count (ke_abi_struct_sizes keeps its list) */
+int ke_abi_gang_struct_sizes(int32_t* sizes, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -466,8 +466,16 @@ class Preemption(C.Structure):  # ke_preemption
                 ("n_no_victims", i32), ("n_unfit", i32), ("n_error", i32)]
 
 
+class GangRun(C.Structure):  # ke_gang_run
+    _fields_ = [("first", i32), ("count", i32), ("min_member", i32), ("assumed", i32), ("mode", i32), ("reserved", i32)]
+
+
 # ke_abi_preempt_struct_sizes' list (ke_abi_struct_sizes' ends with ke_pod_diagnosis and stays as it is)
 PREEMPT_STRUCTS = [ResidentPod, PreemptArgs, Preemption]
+GANG_STRUCTS = [GangRun]  # ke_abi_gang_struct_sizes' list
+GANG_RUN_DTYPE = np.dtype(GangRun)
+GANG_STRICT, GANG_NON_STRICT = 0, 1
+GANG_NONE, GANG_PLACED, GANG_WAITING, GANG_FAILED, GANG_SKIPPED, GANG_ROLLED_BACK = range(6)
 RESIDENT_POD_DTYPE = np.dtype(ResidentPod)
 PREEMPTION_DTYPE = np.dtype(Preemption)
 RESERVATION_DTYPE = np.dtype(Reservation)
@@ -587,6 +595,10 @@ EXPORTS = {
     "ke_preempt": (C.c_int, [C.c_void_p, i32, C.c_void_p, C.c_void_p, i64, C.c_void_p, C.c_void_p, i32, C.c_void_p, i32,
                              C.c_void_p]),
     "ke_abi_preempt_struct_sizes": (C.c_int, [C.POINTER(i32), i32]),
+    "ke_pod_gangs": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
+    "ke_last_gang_status": (C.c_int, [C.c_void_p, i32, C.c_void_p, C.c_void_p]),
+    "ke_debug_gangs": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ke_abi_gang_struct_sizes": (C.c_int, [C.POINTER(i32), i32]),
     "ke_node_devices_set": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
     "ke_node_gpu_partitions": (C.c_int, [C.c_void_p, i32, i32, i32, i32, C.c_void_p]),
     "ke_node_devices_delete": (C.c_int, [C.c_void_p, i32]),
@@ -713,9 +725,28 @@ def load_library(path=LIB_PATH):
     for s, n in zip(PREEMPT_STRUCTS, sizes):
         if C.sizeof(s) != n:
             raise RuntimeError(f"ABI layout mismatch for {s.__name__}: python {C.sizeof(s)} != C {n}")
+    sizes = (i32 * len(GANG_STRUCTS))()
+    if lib.ke_abi_gang_struct_sizes(sizes, len(GANG_STRUCTS)) != len(GANG_STRUCTS):
+        raise RuntimeError("ABI mismatch: the gang structs' count")
+    for s, n in zip(GANG_STRUCTS, sizes):
+        if C.sizeof(s) != n:
+            raise RuntimeError(f"ABI layout mismatch for {s.__name__}: python {C.sizeof(s)} != C {n}")
     if path == LIB_PATH:
         _lib = lib
     return lib
+
+
+def gang_runs(runs):
+    """(n_runs, void*) of ke_pod_gangs' runs: a GANG_RUN_DTYPE array, or tuples (first, count, min_member[, assumed[,
+    mode]]).  Returns (n_runs, array): ke_pod_gangs copies the runs, so the caller holds the array for that call only."""
+    if isinstance(runs, np.ndarray) and runs.dtype == GANG_RUN_DTYPE:
+        a = np.ascontiguousarray(runs)
+    else:
+        a = np.zeros(len(runs), GANG_RUN_DTYPE)
+        for i, r in enumerate(runs):
+            r = tuple(r) + (0,) * (5 - len(r))
+            a[i] = (r[0], r[1], r[2], r[3], r[4], 0)
+    return len(a), a
 
 
 def ptr(arr):

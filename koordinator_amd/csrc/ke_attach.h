@@ -1,7 +1,7 @@
-// A call's per-pod attachments ("the staging block"), free of HIP: the six kinds a call can carry --
+// A call's per-pod attachments ("the staging block"), free of HIP: the kinds a call can carry --
 // node set ids (§4o), score table ids (§4p), spread group ids (§4r), spread domain group ids (§4s), spread term
-// records (§4t) and spread domain term records (§4u) -- from their staging to the kernel mode, the upload layout and
-// the host's share of the Reserves.
+// records (§4t), spread domain term records (§4u) and gang words (§4w) -- from their staging to the kernel mode, the
+// upload layout and the host's share of the Reserves.
 // ke_host.h and ke_kernels.hip include it; tests/plan/attach_check.cpp compiles it alone with g++.
 #pragma once
 #include <stdint.h>
@@ -60,11 +60,14 @@ struct CallAttach {
   const int32_t* domains = nullptr;
   const PodTerms* terms = nullptr;
   const PodTerms* dterms = nullptr;
+  // the gang words of the call's pods (ke_gang.h; nullptr: no run).  Not a kernel mode: the words stay
+  // outside the ns() chain, and only the gang batches' Reserve kernel reads them.
+  const int32_t* gangs = nullptr;
   std::vector<int32_t> listed;
   int32_t n_pods = 0;  // the pod count every array present was checked against
 
   void reset() {
-    sets = scores = groups = domains = nullptr;
+    sets = scores = groups = domains = gangs = nullptr;
     terms = dterms = nullptr;
     listed.clear();
     n_pods = 0;
@@ -95,6 +98,7 @@ struct AttachLayout {
   int64_t domains = -1;  // spread domain group ids
   int64_t terms = -1;    // spread term records
   int64_t dterms = -1;   // spread domain term records
+  int64_t gangs = -1;    // gang words (behind every other section: their offsets are those of a call without runs)
   int64_t total = 0;
   AttachLayout(const CallAttach& a, int64_t n_pods) {
     const bool dt = a.dterms, st = dt || a.terms, sd = st || a.domains, sg = sd || a.groups, id = sg || a.sets || a.scores;
@@ -103,6 +107,7 @@ struct AttachLayout {
     if (sd) domains = total, total += n_pods;
     if (st) terms = total, total += TERM_WORDS * n_pods;
     if (dt) dterms = total, total += TERM_WORDS * n_pods;
+    if (a.gangs) gangs = total, total += n_pods;
   }
 };
 

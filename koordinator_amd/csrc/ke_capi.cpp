@@ -360,6 +360,7 @@ struct SegmentRun {
 
   int schedule() {
     c.rsv_fused = fuse;
+    c.att.gangs = c.gang_words.empty() ? nullptr : c.gang_words.data() + seg.s0;  // the segment's gang words
     const int rc = device_schedule(&c, len + fuse, pods + seg.s0, now, chosen + seg.s0, score ? score + seg.s0 : nullptr);
     c.rsv_fused = false;
     return rc;
@@ -1129,6 +1130,7 @@ static const struct {
 static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool sched, bool filter_only = false) {
   Context& c = ctx->c;
   c.att.reset();
+  if (!sched) c.pod_gangs.take(), c.gang_words.clear();  // (runs belong to a ke_schedule call: any other call drops them)
   if (!(c.pod_sets.on || c.pod_scores.on || c.pod_groups.on || c.pod_domains.on || c.pod_terms.on || c.pod_dterms.on))
     return KE_OK;
   bool on[N_ID_KINDS], any[N_ID_KINDS] = {false, false, false, false};
@@ -1228,6 +1230,78 @@ static int take_node_sets(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, bool 
   for (int k = 0; k < N_ID_KINDS; k++)
     if (any[k] && !(filter_only && k == AK_SCORES)) c.att.*ID_KINDS[k].view = (c.*ID_KINDS[k].slot).call.data();
   c.att.n_pods = n_pods;
+  return KE_OK;
+}
+
+// ---- gang runs (include/koord_eval.h; the run logic is ke_gang.h's) ----
+int ke_pod_gangs(ke_ctx* ctx, int32_t n_pods, int32_t n_runs, const ke_gang_run* runs) {
+  if (!ctx) return fail(KE_ERR_INVALID, "ke_pod_gangs arguments");
+  const char* why = "";
+  const int rc = gang_validate(n_pods, n_runs, runs, &why);
+  if (rc) return fail(rc, why);
+  ctx->c.pod_gangs.stage(runs, n_runs);
+  ctx->c.pod_gangs_n = n_pods;
+  return KE_OK;
+}
+int ke_abi_gang_struct_sizes(int32_t* sizes, int32_t n) {
+  const int32_t all[] = {(int32_t)sizeof(ke_gang_run)};
+  const int32_t m = (int32_t)(sizeof(all) / sizeof(all[0]));
+  for (int32_t i = 0; i < n && i < m; i++) sizes[i] = all[i];
+  return m;
+}
+int ke_last_gang_status(ke_ctx* ctx, int32_t n, int32_t* status, int32_t* tried_node) {
+  if (!ctx || n < 0 || (n > 0 && (!status || !tried_node))) return fail(KE_ERR_INVALID, "ke_last_gang_status arguments");
+  const CallRecords& r = ctx->c.last;
+  for (int32_t p = 0; p < n; p++) {
+    status[p] = r.gang_status.at(p) ? *r.gang_status.at(p) : KE_GANG_NONE;
+    tried_node[p] = r.gang_tried.at(p) ? *r.gang_tried.at(p) : -1;
+  }
+  return KE_OK;
+}
+int ke_debug_gangs(ke_ctx* ctx, int64_t* out4) {
+  if (!ctx || !out4) return fail(KE_ERR_INVALID, "ke_debug_gangs arguments");
+  for (int i = 0; i < 4; i++) out4[i] = ctx->c.last.gang_counts[i];
+  return KE_OK;
+}
+
+// The staged runs of this ke_schedule / ke_schedule_submit call (behind take_node_sets, which reset Context::att),
+// consumed whether the call goes on or not.  Every refusal of a gang call is raised here, before any state changes and
+// without a device; a call with at least one run goes on with Context::gang_words, its pods' gang words.
+static int take_gangs(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods) {
+  Context& c = ctx->c;
+  c.gang_words.clear();
+  if (!c.pod_gangs.take()) return KE_OK;
+  const std::vector<ke_gang_run>& runs = c.pod_gangs.call;
+  if (c.pod_gangs_n != n_pods) return fail(KE_ERR_INVALID, "the call's n_pods differs from the staged ke_pod_gangs runs'");
+  if (runs.empty()) return KE_OK;
+  int rc = check_pods(pods, n_pods, &c, true);
+  if (rc) return rc;
+  auto no = [](const char* what) { return fail(KE_ERR_UNSUPPORTED, std::string("gangs: ") + what); };
+  if (c.att.groups || c.att.domains || c.att.terms || c.att.dterms)
+    return no("a call with spread group / spread domain ids or term lists");
+  if ((c.att.sets || c.att.scores) && !c.quotas.empty()) return no("an ElasticQuota tree together with node sets or score tables");
+  if (c.cfg.global_node_offset != 0 || (c.dev && device_sharded(&c))) return no("a node-sharded context");
+  if (!c.match_off.empty()) return no("a call with staged ke_pod_reservations lists");
+  if (c.numa_enabled || c.n_policy_nodes > 0) return no("a context with NUMA topology policy state");
+  if (c.n_bind_nodes > 0) return no("a context with CPU bind policy nodes");
+  const bool barriers = !c.quotas.empty() && c.qargs.enable_runtime_quota;
+  for (const ke_gang_run& r : runs) {
+    if (r.count > c.cfg.pod_batch) return no("a run longer than ke_config.pod_batch");
+    for (int32_t p = r.first; p < r.first + r.count; p++) {
+      if (pods[p].reservation_matched != KE_RSV_NONE) return no("a reservation-matched / ignored / affinity member");
+      if (pods[p].numa_topology_policy != KE_NUMA_POLICY_NONE) return no("a NUMA-policy member");
+      if (pods[p].quota < 0 || pods[p].quota > (int32_t)c.quotas.size())
+        return fail(KE_ERR_INVALID, "ke_pod.quota outside the loaded ElasticQuota tree");
+      if (barriers && pods[p].quota > 0 && c.quotas[(size_t)pods[p].quota - 1].limit_is_max)
+        return no("a member whose quota Reserve refreshes the runtime quota (a segment barrier)");
+      const uint32_t f = make_dev_pod(c.cfg, pods[p], pod_hints(c, pods[p]), &c.tmpl).flags;
+      if (f & PF_DS_HINT) return no("a member with device hints");
+      if (f & PF_DS) return no("a DeviceShare member");
+      if (f & PF_CPUSET) return no("a cpuset member");
+    }
+  }
+  c.gang_words = gang_words(n_pods, (int32_t)runs.size(), runs.data());
+  c.att.gangs = c.gang_words.data();  // (ke_schedule: each segment's own words, SegmentRun::schedule)
   return KE_OK;
 }
 
@@ -1705,7 +1779,9 @@ int ke_schedule(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns,
   if (!ctx) return fail(KE_ERR_INVALID, "ke_schedule arguments");
   async_drain(ctx);
   const StagedMatches consumed{ctx->c};
-  const int rc = take_node_sets(ctx, n_pods, pods, true);
+  int rc = take_node_sets(ctx, n_pods, pods, true);
+  if (!rc) rc = take_gangs(ctx, n_pods, pods);
+  else ctx->c.pod_gangs.take();
   if (rc) return rc;
   return schedule_sync(ctx, n_pods, pods, now_ns, chosen, score);
 }
@@ -1716,7 +1792,9 @@ int ke_schedule_submit(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t 
   Context& c = ctx->c;
   const StagedMatches consumed{c};
   {
-    const int rc = take_node_sets(ctx, n_pods, pods, true);
+    int rc = take_node_sets(ctx, n_pods, pods, true);
+    if (!rc) rc = take_gangs(ctx, n_pods, pods);
+    else c.pod_gangs.take();
     if (rc) return rc;
   }
   int in_flight = 0;

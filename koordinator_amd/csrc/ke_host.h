@@ -13,6 +13,7 @@
 
 #include "../../include/koord_eval.h"
 #include "ke_attach.h"
+#include "ke_gang.h"
 #include "ke_preempt.h"
 #include "ke_segments.h"
 #include "ke_types.h"
@@ -266,6 +267,12 @@ struct Context {
   AttachSlot<int32_t> pod_sets, pod_scores, pod_groups, pod_domains;
   AttachSlot<PodTerms> pod_terms, pod_dterms;
   CallAttach att;
+  // Gang runs (ke_pod_gangs, ke_gang.h): the staged runs with the pod count they were staged for, the
+  // gang words of the call in progress (att.gangs points at its current segment's); the statuses and ke_debug_gangs'
+  // counters are the call's record's (CallRecords)
+  AttachSlot<ke_gang_run> pod_gangs;
+  int32_t pod_gangs_n = 0;
+  std::vector<int32_t> gang_words;
   // Resident pods and PDB budgets (ke_resident_pods_load / ke_pdbs_load; ke_preempt.h): the caller's
   // statement of which pods sit on which node, beside the rows and never folded into them.  The device copies are
   // uploaded whole by the next ke_preempt after a change (residents.dirty / pdb_dirty).

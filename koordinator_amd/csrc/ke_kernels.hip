@@ -317,6 +317,15 @@ __device__ __forceinline__ void quota_reserve_r(const SoA& s, const DevPod& p, Q
   }
 }
 
+// the inverse of quota_reserve_r of an admitted pod (a gang rollback): the masked request again
+__device__ __forceinline__ void quota_unreserve_r(const SoA& s, const DevPod& p, QuotaRegs& Q, int lane) {
+  const int32_t m = s.qm[(int)p.quota - 1];
+  int64_t req[2];
+#pragma unroll
+  for (int r = 0; r < 2; r++) req[r] = qm_max(m, r) ? -p.req[r] : 0;
+  quota_reserve_r(s, p, Q, req, lane);
+}
+
 // Amplify (node_resource_amplification.go:170-175) with the ratio's IEEE bits from the CPU SoA
 __device__ __forceinline__ int64_t amplify_bits(int64_t q, int64_t ratio_bits) {
   const double r = __longlong_as_double(ratio_bits);
@@ -2973,6 +2982,12 @@ __device__ __forceinline__ void ext_fast_reserve(NodeFast& f, const DevPod& p, c
   for (int q = 0; q < NUM_XS; q++) f.xr[q] += q < k.xs_n ? p.xreq[q] : 0;
   f.room -= 1;
 }
+// its inverse (a gang rollback)
+__device__ __forceinline__ void ext_fast_unreserve(NodeFast& f, const DevPod& p, const KArgs& k) {
+#pragma unroll
+  for (int q = 0; q < NUM_XS; q++) f.xr[q] -= q < k.xs_n ? p.xreq[q] : 0;
+  f.room += 1;
+}
 __device__ __forceinline__ void ext_store(const SoA& s, int64_t node, const NodeFast& f, const KArgs& k) {
 #pragma unroll
   for (int q = 0; q < NUM_XS; q++)
@@ -3171,6 +3186,29 @@ __device__ __forceinline__ void fast_reserve(NodeFast& f, const DevPod& p, const
   f.nreq[0] += reqd[0];
   f.nreq[1] += reqd[1];
   f.nreq0s += reqd[0];
+  fast_bounds(f);
+}
+
+// The inverse of fast_reserve (a gang rollback): the same terms under the same conditions with the
+// signs turned.  Exact: the int64 terms are integer arithmetic, the doubles hold integers below 2^53 and only sums /
+// differences of them are formed, so x - e + e == x.  The node flags do not change during a call.
+__device__ __forceinline__ void fast_unreserve(NodeFast& f, const DevPod& p, const double (&estd)[2],
+                                               const double (&reqd)[2]) {
+  const uint32_t nf = f.nflags;
+  if ((nf & NF_HAS_METRIC) && !(nf & NF_NM_NIL)) {
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      if (nf & nf_fh_on(0, q)) f.fh[0][q] += p.est[q];
+      f.sa[0][q] += estd[q];
+      if (p.flags & PF_PROD) {
+        if (nf & nf_fh_on(1, q)) f.fh[1][q] += p.est[q];
+        f.sa[1][q] += estd[q];
+      }
+    }
+  }
+  f.nreq[0] -= reqd[0];
+  f.nreq[1] -= reqd[1];
+  f.nreq0s -= reqd[0];
   fast_bounds(f);
 }
 
@@ -6110,18 +6148,26 @@ __device__ __forceinline__ ChgSet chg_init(ResLds& L, uint32_t* glb, int n_nodes
   return ChgSet{L.chg, glb};
 }
 
-template <bool DS, bool NUMA, bool QUOTA, bool EXT, int NS>
+// What a gang batch's replay reads and writes besides (GANG instantiations only): the call's gang words,
+// its per-pod status and tried-node outputs, and two counters (runs rolled back, inverse Reserves)
+struct GangIO {
+  const int32_t* words;
+  int32_t* status;
+  int32_t* tried;
+  int32_t* counts;
+};
+template <bool DS, bool NUMA, bool QUOTA, bool EXT, int NS, bool GANG = false>
 __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const SoA& s, const int base, const int B,
                                              const KArgs& k, int32_t* __restrict__ chosen,
                                              int32_t* __restrict__ chosen_score, int32_t global_offset,
                                              uint64_t* __restrict__ stamps, int batch_index,
                                              uint64_t* __restrict__ dev_alloc, int64_t* __restrict__ numa_alloc,
                                              int64_t* __restrict__ touched_out, int32_t* __restrict__ touched_cnt,
-                                             uint64_t* __restrict__ pst);
+                                             uint64_t* __restrict__ pst, const GangIO gio = GangIO{});
 
 // One batch: prologue on every thread of the workgroup (the batch's pods and exact candidate lists
 // into LDS), replay on wave 0 (the other waves skip it).
-template <bool DS, bool NUMA, bool QUOTA, bool EXT = true, int NS = 0>
+template <bool DS, bool NUMA, bool QUOTA, bool EXT = true, int NS = 0, bool GANG = false>
 __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const SoA& s, const DevPod* __restrict__ pods,
                                               const int base, const int B, const KArgs& k,
                                               const uint32_t* __restrict__ cand, const int32_t* __restrict__ cand_cnt,
@@ -6133,7 +6179,8 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
                                               int32_t* __restrict__ touched_cnt = nullptr,
                                               bool has_t = false, bool keep = false, int LS = KMAX,
                                               bool sorted = false, int32_t* __restrict__ pub_done = nullptr,
-                                              const THelp th = THelp{nullptr, nullptr, nullptr, 0, 0, nullptr}) {
+                                              const THelp th = THelp{nullptr, nullptr, nullptr, 0, 0, nullptr},
+                                              const GangIO gio = GangIO{}) {
   const int tid = threadIdx.x;
   constexpr int RES_THREADS = res_threads<NUMA>();
   if (tid == 0) pstamps[PST * batch_index] = __builtin_amdgcn_s_memrealtime();
@@ -6198,8 +6245,8 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
     for (int u = 12; u < 16; u++) pstamps[PST * batch_index + u] = 0;
   }
   // plain batch: the speculative replay on every wave (a grouped batch, NS_GROUPS: the sequential replay below, whose
-  // Reserves keep the spread group counts)
-  if constexpr (!DS && !NUMA && !QUOTA && NS < NS_GROUPS) {
+  // Reserves keep the spread group counts; a gang batch, GANG: the sequential replay too, which can roll a run back)
+  if constexpr (!DS && !NUMA && !QUOTA && NS < NS_GROUPS && !GANG) {
     __builtin_amdgcn_s_setprio(3);
     replay_spec<EXT, NS>(L, C, s, base, B, k, chosen, chosen_score, global_offset, stamps, batch_index, dev_alloc,
                      touched_out, touched_cnt, pstamps + PST * batch_index, has_t, keep, LS, sorted, th);
@@ -6209,8 +6256,8 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
   if (tid >= 64) return;  // the replay is one wavefront: wave-level ordering only from here on
   // the next batch's eval waves may share this SIMD (pipelined schedule): the replay issues first
   __builtin_amdgcn_s_setprio(3);
-  replay_batch<DS, NUMA, QUOTA, EXT, NS>(L, C, s, base, B, k, chosen, chosen_score, global_offset, stamps, batch_index,
-                                dev_alloc, numa_alloc, touched_out, touched_cnt, pstamps + PST * batch_index);
+  replay_batch<DS, NUMA, QUOTA, EXT, NS, GANG>(L, C, s, base, B, k, chosen, chosen_score, global_offset, stamps, batch_index,
+                                dev_alloc, numa_alloc, touched_out, touched_cnt, pstamps + PST * batch_index, gio);
   __builtin_amdgcn_s_setprio(0);
 }
 
@@ -6240,15 +6287,24 @@ __device__ __forceinline__ void resolve_batch(ResLds& L, const ChgSet& C, const 
 //   lane's Reserve does load + saturating add + store for every member; behind it and the wave_lds_sync every lane
 //   < n_chg, the new owner included, reads its node's counts for pod j+1's terms.  As with NS_GROUPS, lane c is the
 //   only reader and writer of its node's counts during the batch.
-template <bool DS, bool NUMA, bool QUOTA, bool EXT, int NS>
+//   GANG (a batch holding gang members; plain batches with or without quota, NS < NS_GROUPS): pod j's gang
+//   word is wave-uniform, fetched one pod ahead like its record.  The run's state -- first position, waiting count,
+//   failed and satisfied flags -- is wave-uniform; lane j keeps pod j's owner lane and status beside o_node.  A member
+//   behind a failed member of its run is not tried.  A strict run's member that is placed nowhere before the run is
+//   satisfied rolls the run back: for every placed member m of the run, in queue order, the owner lane (readlane of lane
+//   m's owner register) applies the inverse Reserve with pod m's record from LDS, every lane the inverse quota Reserve,
+//   and lane m turns its outputs to unplaced.  The node stays a changed slot: its bit stays set, its lane keeps it and
+//   n_chg stays, so every later pod re-evaluates it from the restored registers and the write-back stores them.
+template <bool DS, bool NUMA, bool QUOTA, bool EXT, int NS, bool GANG>
 __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const SoA& s, const int base, const int B,
                                              const KArgs& k, int32_t* __restrict__ chosen,
                                              int32_t* __restrict__ chosen_score, int32_t global_offset,
                                              uint64_t* __restrict__ stamps, int batch_index,
                                              uint64_t* __restrict__ dev_alloc, int64_t* __restrict__ numa_alloc,
                                              int64_t* __restrict__ touched_out, int32_t* __restrict__ touched_cnt,
-                                             uint64_t* __restrict__ pst) {
+                                             uint64_t* __restrict__ pst, const GangIO gio) {
   static_assert(!NS || (!DS && !NUMA), "node sets: plain batches only");
+  static_assert(!GANG || (!DS && !NUMA && NS < NS_GROUPS), "gang batches: plain pods, no spread kind");
   const uint32_t* const s_cand = L.cand;
   const DevPod* const s_pod = L.pod;
   const int lane = threadIdx.x & 63;
@@ -6303,11 +6359,24 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
   bool dclosed = false;
   int32_t dbonus = 0;
   if constexpr (NS == NS_DTERMS) dr = s.dt_rec[base];
+  // GANG: pod j's gang word and the run's state (wave-uniform); lane j: pod j's owner lane, status, rolled-back node
+  int32_t gw = 0;
+  int g_first = 0, g_wait = 0, g_rolled = 0, g_inv = 0;
+  bool g_failed = false, g_sat = false;
+  int32_t o_owner = -1, o_status = KE_GANG_NONE, o_tried = -1;
+  if constexpr (GANG) gw = __builtin_amdgcn_readfirstlane(gio.words[base]);
   RPROF_DECL
   for (int j = 0; j < B; j++) {
     const bool more = j + 1 < B;
     const DevPod pod_n = s_pod[more ? j + 1 : j];
     const int jn = more ? j + 1 : j;
+    int32_t gw_n = 0;
+    bool g_skip = false;  // a member behind its run's failed member: not tried
+    if constexpr (GANG) {
+      gw_n = __builtin_amdgcn_readfirstlane(gio.words[base + jn]);
+      if (gw & GW_FIRST) g_first = j, g_wait = 0, g_failed = false, g_sat = gw_need(gw) == 0;
+      g_skip = (gw & GW_MEMBER) && g_failed;
+    }
     int gid_n = 0;
     uint32_t gcap_n = 65535u;
     if constexpr (NS >= NS_GROUPS) {
@@ -6398,7 +6467,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
     }
     // ElasticQuota PreFilter: a refused pod is placed nowhere
     int64_t qreq[2] = {0, 0};
-    const bool adm = !QUOTA || !pod.quota || quota_admit_r(s, pod, k, Q, qreq);
+    const bool adm = (!GANG || !g_skip) && (!QUOTA || !pod.quota || quota_admit_r(s, pod, k, Q, qreq));
     const uint32_t w = adm ? max(bu, bc) : 0u;
     if (w != 0) {
       int owner;
@@ -6518,6 +6587,37 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
         o_node = key_node(w) + global_offset;
         o_score = key_score(w);
       }
+      if constexpr (GANG) {
+        if (gw & GW_MEMBER) {  // Permit: the waiting count; the run's placed members are PLACED once it reaches need
+          if (lane == j) o_owner = owner, o_status = g_sat ? KE_GANG_PLACED : KE_GANG_WAITING;
+          g_wait++;
+          if (!g_sat && g_wait >= gw_need(gw)) {
+            g_sat = true;
+            if (lane >= g_first && lane <= j && o_status == KE_GANG_WAITING) o_status = KE_GANG_PLACED;
+          }
+        }
+      }
+    } else if (GANG && (gw & GW_MEMBER)) {
+      if (lane == j) o_status = g_skip ? KE_GANG_SKIPPED : KE_GANG_FAILED;
+      if (!g_skip && !g_sat) {  // PostFilter of a run not yet satisfied
+        g_failed = true;
+        if (gw & GW_STRICT) {
+          g_rolled++;
+          for (int m = g_first; m < j; m++) {  // (wave-uniform bounds and conditions: readlane of lane m's registers)
+            if (__builtin_amdgcn_readlane(o_node, m) < 0) continue;
+            const int ow = __builtin_amdgcn_readlane(o_owner, m);
+            const DevPod pm = s_pod[m];
+            const double em[2] = {L.pd[m][0], L.pd[m][1]}, rm[2] = {L.pd[m][2], L.pd[m][3]};
+            if (lane == ow) {
+              fast_unreserve(fast, pm, em, rm);
+              if (EXT && (k.flags & AF_EXT)) ext_fast_unreserve(fast, pm, k);
+            }
+            if (QUOTA && pm.quota) quota_unreserve_r(s, pm, Q, lane);
+            if (lane == m) o_tried = o_node, o_node = -1, o_score = -1, o_owner = -1, o_status = KE_GANG_ROLLED_BACK;
+            g_inv++;
+          }
+        }
+      }
     } else if (NUMA && lane == 0) {
 #pragma unroll
       for (int t = 0; t < 16; t++) numa_alloc[(int64_t)(base + j) * 16 + t] = 0;
@@ -6560,6 +6660,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
     for (int u = 0; u < 4; u++) pdd[u] = pdd_n[u];
     ck = ck_n;
     chg = chg_n;
+    if constexpr (GANG) gw = gw_n;
     RPROF(6)
   }
   RPROF_FLUSH(0, B)
@@ -6567,6 +6668,16 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
     chosen[base + lane] = o_node;
     chosen_score[base + lane] = o_score;
     dev_alloc[base + lane] = o_alloc;
+  }
+  if constexpr (GANG) {
+    if (lane < B) {
+      gio.status[base + lane] = o_status;
+      gio.tried[base + lane] = o_tried;
+    }
+    if (lane == 0) {  // (the call's batches run one after another on one stream: no other writer)
+      gio.counts[0] += g_rolled;
+      gio.counts[1] += g_inv;
+    }
   }
   if (QUOTA)
 #pragma unroll
@@ -7811,6 +7922,10 @@ struct CallBufs {
   PinnedVec<uint8_t> h_out;      // the read-back staging (HostOutLayout)
   DevBuf<uint64_t> d_sd_mask;    // [n_pods] eligible-domain masks of a call with spread domain ids (k_domain_masks)
   DevBuf<uint16_t> d_dt_tbl;     // [n_pods][POD_TERMS][64] cells of a call with spread domain term lists (k_domain_terms)
+  // a call with gang runs: status [n_pods], tried node [n_pods], counters [2]; and where its gang words
+  // lie in d_pods' staging block (nullptr: no run)
+  DevBuf<int32_t> d_gang;
+  const int32_t* d_gang_words = nullptr;
   std::vector<hipEvent_t> tev;   // the call's events (pool): span, the call's end per stream, samples
 };
 
@@ -8693,6 +8808,7 @@ static int upload_pods(Context* ctx, int32_t n_pods, const ke_pod* pods, const A
     for (int32_t p = 0; p < n_pods; p++) h_words[lay.ids + p] = (a.sets ? a.sets[p] : 0) | (a.scores ? a.scores[p] << 16 : 0);
     d->soa.ns_ids = d_words + lay.ids;
   }
+  d->call.d_gang_words = section(lay.gangs, a.gangs);
   if (tail) *tail = h_words + ns_words;
   if (block_bytes) *block_bytes = bytes;
   if (!tail && bytes) {
@@ -8822,6 +8938,12 @@ static ResolveFn pick_resolve(bool ds, bool numa, bool quota, int ns) {
   });
 }
 static unsigned resolve_threads(bool numa) { return numa ? res_threads<true>() : res_threads<false>(); }
+// a batch holding gang members: QUOTA with NS = 0, or NS in {0, NS_SETS, NS_SCORES} without quota; named
+// at the end of this file, like the NS_DTERMS instantiations
+struct GangIO;
+using ResolveGangFn = void (*)(SoA, const DevPod*, const int32_t*, int, KArgs, const uint32_t*, const int32_t*, int32_t*,
+                               int32_t*, int32_t, uint64_t*, uint64_t*, int, uint64_t*, uint32_t*, int, int, GangIO);
+static ResolveGangFn pick_resolve_gang(bool quota, int ns);
 // QUOTA x EXT, or NS x EXT without quota
 using ResolveRunFn = decltype(&k_resolve_run<false, false>);
 static ResolveRunFn pick_resolve_run(bool quota, bool ext, int ns) {
@@ -9193,7 +9315,36 @@ struct Completion {
   int64_t copies, fills;
   int n_pipelined;
   PlacedAttach placed;  // the call's attachments whose Reserves the host tables follow (apply_placements)
+  std::vector<int32_t> gang_words;  // the call's gang words (empty: no run), and the batches its cut rule ended early
+  int gang_cuts = 0;
 };
+
+// A gang call's statuses into the call's records and ke_debug_gangs' counters -- after the five rules (ke_gang.h) have
+// been replayed on the host over what the device reports: each member placed where the device had it, each undo counted.
+// The device and the host state machine must agree on every status.
+static int complete_gangs(const Completion& c, const int32_t* chosen) {
+  Context* const ctx = c.ctx;
+  const size_t np = (size_t)c.n_pods;
+  // (a call without runs answers 0 / -1: with two calls in flight the context's record may still hold the other one's)
+  ctx->last.fill_gangs(0, nullptr, nullptr, false);
+  if (c.gang_words.empty()) return KE_OK;
+  const int32_t* const status = reinterpret_cast<const int32_t*>(c.h + c.ho.gang);
+  const int32_t *const tried = status + np, *const counts = status + 2 * np;
+  std::vector<int32_t> h_chosen(np), h_status(np), h_tried(np);
+  const GangCounts cnt = gang_machine(
+      c.n_pods, c.gang_words.data(),
+      [&](int32_t p) { return status[p] == KE_GANG_ROLLED_BACK ? tried[p] : chosen[p]; }, [](int32_t, int32_t) {},
+      h_chosen.data(), h_status.data(), h_tried.data());
+  for (size_t p = 0; p < np; p++)
+    if (h_chosen[p] != chosen[p] || h_status[p] != status[p] || h_tried[p] != tried[p])
+      return fail(KE_ERR_DEVICE, "internal: the replay's gang statuses differ from the run rules (placements invalid)");
+  if (cnt.rolled_back != counts[0] || cnt.inverses != counts[1])
+    return fail(KE_ERR_DEVICE, "internal: the replay's gang rollback counts differ from the run rules");
+  ctx->last.fill_gangs(np, status, tried, true);
+  const int64_t all[4] = {cnt.runs, counts[0], counts[1], c.gang_cuts};
+  std::copy(all, all + 4, ctx->last.gang_counts);
+  return KE_OK;
+}
 
 static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
   Context* const ctx = c.ctx;
@@ -9239,6 +9390,7 @@ static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
                                                       : "internal: a hinted pod reached a kernel without the hint path");
   }
   apply_placements(*ctx, c.placed, chosen);
+  if (int rc = complete_gangs(c, chosen)) return rc;
   float ms = 0;
   HIP_OK(hipEventElapsedTime(&ms, c.e0, c.e1));
   std::vector<float> samples;  // (eval, select) per sampled batch
@@ -9329,6 +9481,7 @@ struct ScheduleCall {
   bool published = false;  // the last eval_select's select published its lists itself
   int n_copies = 0, n_fills = 0;  // host-counted copies / fills of the call (ke_debug_call_boundary)
   int n_pipelined = 0;
+  int gang_cuts = 0;  // batches the gang cut rule ended early (plan_batches)
   // the call's timing events, from the buffer set's pool (creating them per call cost the host ~3 us an event)
   int every = 0;
   hipEvent_t e0 = nullptr, e1 = nullptr, done_ev[3] = {};
@@ -9338,7 +9491,14 @@ struct ScheduleCall {
       : ctx(ctx_), d(ctx_->dev), c(d->call), n_pods(n), pods(p), want_score(ws), N(ctx_->n_nodes), fused(ctx_->rsv_fused),
         numa(d->has(ST_NUMA)), quota(!ctx_->quotas.empty()), sharded(d->world > 1 || d->comm || d->host_fn),
         matched(!ctx_->rsv_pairs.empty() || ctx_->rsv_affinity), att(ctx_->att), lay(ctx_->att, n) {}
-  int batch_ns(int b) const { return att.batch_ns(batches[(size_t)b].grouped); }
+  // a batch holding a gang member (grouped by its gang words, not by a spread kind: a gang call carries none)
+  bool gang_batch(int b) const {
+    if (!att.gangs) return false;
+    for (int q = 0; q < batches[(size_t)b].pods; q++)
+      if (att.gangs[bases[(size_t)b] + q] & GW_MEMBER) return true;
+    return false;
+  }
+  int batch_ns(int b) const { return att.batch_ns(batches[(size_t)b].grouped && !att.gangs); }
   int run_ns() const { return att.batch_ns(false); }  // (a pipelined run holds no grouped batch)
 
   hipError_t copy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
@@ -9365,7 +9525,7 @@ struct ScheduleCall {
     knob = select_knob(std::getenv("KOORDEVAL_SELECT_PARTS"));
     ctx->last_ds_cuts = 0;
     batches = plan_batches(c.host_pods.data(), n_pods, ctx->cfg.pod_batch, !sharded && !numa && N > 0, fused,
-                           att.plan_groups(), att.plan_domains(), att.plan_dterms());
+                           att.plan_groups(), att.plan_domains(), att.plan_dterms(), att.gangs, &gang_cuts);
     for (const Batch& b : batches) any_cpu = any_cpu || b.cpu;
     if (any_cpu && !d->has(ST_CPU)) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
     n_batches = (int)batches.size();
@@ -9410,6 +9570,12 @@ struct ScheduleCall {
     // (every singleton batch's k_cpuset_reserve writes its pod's entry; the table is read back, and so zeroed by
     // k_call_begin, only in a call with a cpuset pod)
     RC_OK(c.d_cpusets.reserve(4 * np));
+    if (att.gangs) {  // status, tried node, the two counters: every pod's entry starts as "outside a run"
+      RC_OK(c.d_gang.reserve(2 * np + 2));
+      HIP_OK(fill_async(c.d_gang, 0, sizeof(int32_t) * np, d->stream));
+      HIP_OK(fill_async(c.d_gang + np, 0xFF, sizeof(int32_t) * np, d->stream));
+      HIP_OK(fill_async(c.d_gang + 2 * np, 0, sizeof(int32_t) * 2, d->stream));
+    }
     bool any_hint = false;
     for (const DevPod& q : c.host_pods) any_hint = any_hint || (q.flags & PF_DS_HINT);
     d->soa.vfo = nullptr;
@@ -9790,7 +9956,15 @@ struct ScheduleCall {
     }
     // one pod: the single-node Reserve (cpuset accumulator when it binds) -- but a grouped singleton takes the
     // replay, which keeps the spread group counts
-    if (bp == 1 && !batches[b].grouped) {
+    if (gang_batch(b)) {
+      const auto resolve = pick_resolve_gang(quota, batch_ns(b));
+      if (!resolve || ds || cpu || numa) return no_variant("k_resolve_gang with a DeviceShare / cpuset batch, NUMA, or quota with node sets");
+      const size_t np = (size_t)n_pods;
+      hipLaunchKernelGGL(resolve, dim3(1), dim3(resolve_threads(false)), 0, d->stream, d->soa, c.d_pods, bbase, bp, k,
+                         d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score, ctx->cfg.global_node_offset, d_st, d_pst, b,
+                         c.d_devalloc, d->d_chg, N, (int)sel[(size_t)b].sorted,
+                         GangIO{c.d_gang_words, c.d_gang, c.d_gang + np, c.d_gang + 2 * np});
+    } else if (bp == 1 && !batches[b].grouped) {
       int elo = 0, ehi = 0;  // nodes whose affinities this batch's eval stored in d_aff (binding batches)
       if (cpu && numa) {
         ehi = N;
@@ -9858,7 +10032,7 @@ struct ScheduleCall {
     for (const Batch& bt : batches) any_ds = any_ds || bt.ds || bt.hint;
     const bool vf_out = d->soa.vfo != nullptr;
     const size_t np = (size_t)n_pods, nb = (size_t)n_batches;
-    const HostOutLayout ho(ol, np, nb, want_score, any_ds, any_cpu, vf_out, numa);
+    const HostOutLayout ho(ol, np, nb, want_score, any_ds, any_cpu, vf_out, numa, att.gangs != nullptr);
     if (!c.h_out.resize(ho.total)) return fail(KE_ERR_DEVICE, "hipHostMalloc of the readback staging buffer");
     uint8_t* const h = c.h_out.data();
     HIP_OK(copy_async(h, c.d_out + ho.blk0, ho.blk_bytes, hipMemcpyDeviceToHost, d->stream));
@@ -9868,6 +10042,7 @@ struct ScheduleCall {
     if (vf_out) HIP_OK(copy_async(h + ho.vf, d->d_vfo, 2 * DS_MINORS * np, hipMemcpyDeviceToHost, d->stream));
     if (numa) HIP_OK(copy_async(h + ho.numa, c.d_numaalloc, 8 * 16 * np, hipMemcpyDeviceToHost, d->stream));
     if (numa) HIP_OK(copy_async(h + ho.dcnt, d->d_defer_cnt, 4 * nb, hipMemcpyDeviceToHost, d->stream));
+    if (att.gangs) HIP_OK(copy_async(h + ho.gang, c.d_gang, 4 * (2 * np + 2), hipMemcpyDeviceToHost, d->stream));
     // the call's end on every stream: its completion waits for these events, not for the streams
     HIP_OK(hipEventRecord(done_ev[0], d->stream));
     HIP_OK(hipEventRecord(done_ev[1], d->estream));
@@ -9887,6 +10062,8 @@ struct ScheduleCall {
     cp.entry = ctx->call_entry, cp.behind = ctx->call_behind;
     cp.copies = n_copies, cp.fills = n_fills, cp.n_pipelined = n_pipelined;
     cp.placed = PlacedAttach(att, n_pods);
+    if (att.gangs) cp.gang_words.assign(att.gangs, att.gangs + n_pods);
+    cp.gang_cuts = gang_cuts;
     *fin = [cp = std::move(cp)](int32_t* chosen, int32_t* score) { return complete_call(cp, chosen, score); };
     return KE_OK;
   }
@@ -10102,5 +10279,34 @@ static DiagEvalFn pick_diag_eval_dterms(bool numa, bool cpu) {
 // ---- ke_preempt's kernels: named here alone, so they lie behind every kernel that existed before -----
 static PreemptSimFn pick_preempt_sim(int ns) { return ns == NS_SETS ? k_preempt_sim<NS_SETS> : ns == 0 ? k_preempt_sim<> : nullptr; }
 static PreemptPickFn pick_preempt_pick(int ns) { return ns == NS_SETS ? k_preempt_pick<NS_SETS> : ns == 0 ? k_preempt_pick<> : nullptr; }
+
+// ---- gang batches --------------------------------------------------------------------------------------
+// k_resolve with the rollback: a batch holding gang members, a singleton included.  Named here and nowhere else, behind
+// every kernel that existed before it.
+template <bool QUOTA, int NS>
+__global__ __launch_bounds__(res_threads<false>()) void k_resolve_gang(SoA s, const DevPod* __restrict__ pods,
+                                                                       const int32_t* __restrict__ batch_base, int batch_pods,
+                                                                       KArgs k, const uint32_t* __restrict__ cand,
+                                                                       const int32_t* __restrict__ cand_cnt,
+                                                                       int32_t* __restrict__ chosen,
+                                                                       int32_t* __restrict__ chosen_score, int32_t global_offset,
+                                                                       uint64_t* __restrict__ stamps, uint64_t* __restrict__ pstamps,
+                                                                       int batch_index, uint64_t* __restrict__ dev_alloc,
+                                                                       uint32_t* __restrict__ chg_glb, int n_nodes, int sorted,
+                                                                       GangIO gio) {
+  __shared__ ResLds L;
+  const ChgSet C = chg_init(L, chg_glb, n_nodes);
+  resolve_batch<false, false, QUOTA, true, NS, true>(L, C, s, pods, *batch_base, batch_pods, k, cand, cand_cnt, chosen,
+                                                     chosen_score, global_offset, stamps, pstamps, batch_index, dev_alloc,
+                                                     nullptr, nullptr, nullptr, false, false, KMAX, sorted != 0, nullptr,
+                                                     THelp{nullptr, nullptr, nullptr, 0, 0, nullptr}, gio);
+}
+static ResolveGangFn pick_resolve_gang(bool quota, int ns) {
+  if (quota) return ns ? nullptr : k_resolve_gang<true, 0>;
+  return ns == NS_SCORES ? k_resolve_gang<false, NS_SCORES>
+         : ns == NS_SETS ? k_resolve_gang<false, NS_SETS>
+         : ns == 0       ? k_resolve_gang<false, 0>
+                         : nullptr;
+}
 
 }  // namespace ke

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "ke_gang.h"
 #include "ke_types.h"
 
 #ifndef KE_HD
@@ -92,10 +93,28 @@ struct Batch {
 // of whose term groups is a member group of an earlier pod of that batch, so every group a pod reads keeps its snapshot
 // counts for the whole batch (reads after reads, writes after writes and writes after reads share a batch).  The
 // `grouped` mark of such a batch comes with `group_ids`.  With every record empty the plan is the one without them.
+// `gangs` (the call's gang word per pod, ke_gang.h; nullptr: none): a run lies in one batch -- a batch
+// ends before a run that would not fit in it whole (*gang_cuts counts these) -- a batch holding a member holds no
+// DeviceShare pod (a DSB_CUT in mid-run would lose the run's state), and it is `grouped`.  Batches without a member are
+// planned as without the words, and with every word zero the plan is the one without them.
 inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bool ds_batch, bool fused,
                                        const int32_t* group_ids = nullptr, const int32_t* domain_ids = nullptr,
-                                       const PodTerms* dterms = nullptr) {
+                                       const PodTerms* dterms = nullptr, const int32_t* gangs = nullptr,
+                                       int* gang_cuts = nullptr) {
   std::vector<Batch> batches;
+  if (gang_cuts) *gang_cuts = 0;
+  bool has_gang = false, has_ds = false;  // of the batch being filled
+  // pod p0 + bp may not join the bp pods from p0 on: a run that does not fit whole, or a member beside a DeviceShare pod
+  auto gang_stop = [&](int p0, int bp) {
+    if (!gangs || bp == 0) return false;
+    const int32_t w = gangs[p0 + bp];
+    if ((w & GW_FIRST) && bp + gang_run_len(gangs, n_pods, p0 + bp) > B) {
+      if (gang_cuts) (*gang_cuts)++;
+      return true;
+    }
+    const bool ds = (pods[p0 + bp].flags & PF_DS) != 0;
+    return ((w & GW_MEMBER) && has_ds) || (ds && has_gang);
+  };
   // pod p0 + bp reads a spread domain group that one of the bp pods from p0 on is a member of
   auto reads_written = [&](int p0, int bp) {  // (called with domain lists only)
     const PodTerms& r = dterms[p0 + bp];
@@ -122,10 +141,11 @@ inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bo
       continue;
     }
     int bp = 0;
-    bool has_ds = false;
+    has_ds = has_gang = false;
     while (p + bp < n_pods && bp < B && !(fused && p + bp == n_pods - 1) && !alone(pods[p + bp].flags) &&
-           !repeats(p, bp) && (!dterms || !reads_written(p, bp))) {
+           !repeats(p, bp) && (!dterms || !reads_written(p, bp)) && !gang_stop(p, bp)) {
       has_ds = has_ds || (pods[p + bp].flags & PF_DS);
+      has_gang = has_gang || (gangs && (gangs[p + bp] & GW_MEMBER));
       bp++;
     }
     batches.push_back({bp, has_ds, false, has_ds && bp > 1, false});
@@ -137,6 +157,9 @@ inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bo
   if (domain_ids)
     for (size_t b = 0, p = 0; b < batches.size(); p += (size_t)batches[b].pods, b++)
       for (int q = 0; q < batches[b].pods; q++) batches[b].grouped = batches[b].grouped || domain_ids[p + (size_t)q] != 0;
+  if (gangs)
+    for (size_t b = 0, p = 0; b < batches.size(); p += (size_t)batches[b].pods, b++)
+      for (int q = 0; q < batches[b].pods; q++) batches[b].grouped = batches[b].grouped || (gangs[p + (size_t)q] & GW_MEMBER);
   return batches;
 }
 
@@ -242,10 +265,11 @@ struct SchedLayout {
 struct HostOutLayout {
   size_t blk0 = 0, blk_bytes = 0;  // the part of the device block one copy brings
   size_t chosen = 0, score = 0, err = 0, fst = 0, st = 0, pst = 0, est = 0, kerr = 0, dev = 0, cs = 0, vf = 0, numa = 0,
-         dcnt = 0, total = 0;
+         dcnt = 0, gang = 0, total = 0;
   HostOutLayout() = default;
+  // (gangs: the call's gang block -- status [np], tried node [np], two counters -- behind everything else)
   HostOutLayout(const OutLayout& ol, size_t np, size_t nb, bool want_score, bool any_ds, bool any_cpu, bool vf_out,
-                bool numa_on) {
+                bool numa_on, bool gangs = false) {
     blk0 = want_score ? ol.score : ol.chosen;
     blk_bytes = ol.end - blk0;
     chosen = ol.chosen - blk0, score = ol.score - blk0, err = ol.err - blk0, fst = ol.fst - blk0;
@@ -254,6 +278,7 @@ struct HostOutLayout {
     kerr = take(4), dev = take(any_ds ? 8 * np : 0), cs = take(any_cpu ? 32 * np : 0);
     vf = take(vf_out ? 2 * DS_MINORS * np : 0), numa = take(numa_on ? 8 * 16 * np : 0);
     dcnt = take(numa_on ? 4 * nb : 0);
+    gang = take(gangs ? 4 * (2 * np + 2) : 0);
     total = take.off;
   }
 };

@@ -81,6 +81,8 @@ struct CallRecords {
   PerPod<uint64_t, 4> cpusets;                      // CPU-id bitset
   PerPod<int8_t, 2 * KE_MAX_MINORS> vfs;            // VF ranks [2][KE_MAX_MINORS], absent: -1
   PerPod<int64_t, KE_MAX_NUMA * KE_NRES> numas;     // NUMA amounts [2*id + r]
+  PerPod<int32_t, 1> gang_status, gang_tried;       // KE_GANG_* and a rolled-back member's node (a call with gang runs)
+  int64_t gang_counts[4] = {0, 0, 0, 0};            // ke_debug_gangs: runs, runs rolled back, inverse Reserves, cut batches
   size_t n = 0;          // pods the device-made kinds cover
   int32_t resv_gen = 0;  // the reservation set `resv` indexes (ke_reservations_generation)
   // per pod: 0 / nullptr = absent
@@ -94,10 +96,19 @@ struct CallRecords {
     devs.fill(d, np, has_dev), cpusets.fill(cs, np, has_cs), vfs.fill(v, np, has_vf), numas.fill(nu, np, has_numa);
     n = np;
   }
-  void clear_device() { fill_device(0, nullptr, false, nullptr, false, nullptr, false, nullptr, false); }
+  void fill_gangs(size_t np, const int32_t* status, const int32_t* tried, bool has) {
+    gang_status.fill(status, np, has), gang_tried.fill(tried, np, has);
+    std::fill(gang_counts, gang_counts + 4, (int64_t)0);
+  }
+  void clear_device() {
+    fill_device(0, nullptr, false, nullptr, false, nullptr, false, nullptr, false);
+    fill_gangs(0, nullptr, nullptr, false);
+  }
   void append(const CallRecords& seg, size_t len) {
     devs.append(seg.devs, n, len, 0), cpusets.append(seg.cpusets, n, len, 0);
     vfs.append(seg.vfs, n, len, -1), numas.append(seg.numas, n, len, 0);
+    gang_status.append(seg.gang_status, n, len, 0), gang_tried.append(seg.gang_tried, n, len, -1);
+    for (int i = 0; i < 4; i++) gang_counts[i] += seg.gang_counts[i];
     n += len;
   }
   // the call's pods: chosen node, uid, whether the ElasticQuota Reserve ran; `resv` keeps what the call assumed
@@ -108,6 +119,7 @@ struct CallRecords {
   }
   void truncate(size_t len) {  // a gated fused pod: the segment's pods only
     devs.truncate(len), cpusets.truncate(len), vfs.truncate(len), numas.truncate(len);
+    gang_status.truncate(len), gang_tried.truncate(len);
     n = std::min(n, len);
   }
   // ke_schedule_wait collects a call.  A reservation set loaded since names other reservations: `resv` drops them.

@@ -623,18 +623,39 @@ class Evaluator:
             out["candidate_words"] = words
         return out
 
+    def pod_gangs(self, n_pods, runs):
+        """ke_pod_gangs: the gang runs of the next schedule / submit of `n_pods` pods; `runs`: an abi.GANG_RUN_DTYPE
+        array, or tuples (first, count, min_member[, assumed[, mode]]), ascending and disjoint."""
+        n, a = abi.gang_runs(runs)
+        self._check(self.lib.ke_pod_gangs(self.h, int(n_pods), n, abi.ptr(a) if n else None))
+
+    def last_gang_status(self, n=None):
+        """ke_last_gang_status of the last schedule() / wait(): (status, tried_node) per pod."""
+        n = self._last_n if n is None else n
+        status, tried = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._check(self.lib.ke_last_gang_status(self.h, n, abi.ptr(status), abi.ptr(tried)))
+        return status, tried
+
+    def debug_gangs(self):
+        """ke_debug_gangs of the last call: runs, runs rolled back, inverse Reserves, batches the cut rule ended."""
+        out = np.zeros(4, np.int64)
+        self._check(self.lib.ke_debug_gangs(self.h, abi.ptr(out)))
+        return {"runs": int(out[0]), "rolled_back": int(out[1]), "inverse_reserves": int(out[2]), "cuts": int(out[3])}
+
     def schedule(self, pods, now_ns, matches=None, node_sets=None, node_scores=None, spread_groups=None,
-                 spread_domains=None, spread_terms=None, spread_domain_terms=None):
+                 spread_domains=None, spread_terms=None, spread_domain_terms=None, gangs=None):
         """ke_schedule; `matches` (optional): per pod the reservation indices it matches (KE_RSV_MATCHED pods);
         `node_sets` (optional): the node set id per pod (0 = every node); `node_scores` (optional): the score table
         id per pod (0 = no offset); `spread_groups` (optional): the spread group id per pod (0 = none);
         `spread_domains` (optional): the spread domain group id per pod (0 = none); `spread_terms` (optional): the
         pair (terms, members) of pod_spread_terms(); `spread_domain_terms` (optional): that of
-        pod_spread_domain_terms()."""
+        pod_spread_domain_terms(); `gangs` (optional): the call's gang runs as for pod_gangs()."""
         pods = as_pod_array(pods)
         if matches is not None:
             self.pod_reservations(matches)
         self._stage(node_sets, node_scores, spread_groups, spread_domains, spread_terms, spread_domain_terms)
+        if gangs is not None:
+            self.pod_gangs(len(pods), gangs)
         chosen = np.zeros(len(pods), np.int32)
         score = np.zeros(len(pods), np.int32)
         self._check(self.lib.ke_schedule(self.h, len(pods), abi.ptr(pods), int(now_ns), abi.ptr(chosen), abi.ptr(score)))
@@ -642,12 +663,14 @@ class Evaluator:
         return chosen, score
 
     def submit(self, pods, now_ns, node_sets=None, node_scores=None, spread_groups=None, spread_domains=None,
-               spread_terms=None, spread_domain_terms=None):
+               spread_terms=None, spread_domain_terms=None, gangs=None):
         """ke_schedule_submit: enqueue a queue slice behind the calls in flight; returns its ticket (wait() collects
         it).  The pod array is kept alive here until then.  `node_sets`, `node_scores`, `spread_groups`,
-        `spread_domains`, `spread_terms` and `spread_domain_terms` as for schedule()."""
+        `spread_domains`, `spread_terms`, `spread_domain_terms` and `gangs` as for schedule()."""
         pods = as_pod_array(pods)
         self._stage(node_sets, node_scores, spread_groups, spread_domains, spread_terms, spread_domain_terms)
+        if gangs is not None:
+            self.pod_gangs(len(pods), gangs)
         t = C.c_int64()
         self._check(self.lib.ke_schedule_submit(self.h, len(pods), abi.ptr(pods), int(now_ns), C.byref(t)))
         self._inflight[t.value] = pods
