@@ -1651,6 +1651,10 @@ int ke_debug_spread_groups_check(ke_ctx* ctx, int64_t* mismatched);
 /* The same for the spread domains: (group, domain) counts and (map, node) entries of the device's tables that differ
  * from the host's copy. */
 int ke_debug_spread_domains_check(ke_ctx* ctx, int64_t* mismatched);
+/* Number of nodes whose DeviceShare words on the device -- the per-minor total / used fields and the mask words, the
+ * used-key bits among them -- differ from a from-scratch derivation from the host's device cache (0 = consistent, also
+ * without a device copy; nodes waiting for a refresh are skipped).  Additive: KE_ABI_VERSION stays 14. */
+int ke_debug_devices_check(ke_ctx* ctx, int64_t* mismatched_nodes);
 /* Launch the batch eval kernel `iters` times back to back over the current node SoA for `n_pods`
  * (<= 64) pods and return the HIP-event average milliseconds per launch (roofline measurement). */
 int ke_bench_eval_kernel(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods, int64_t now_ns, int32_t iters,
@@ -1732,6 +1736,24 @@ int ke_last_gang_status(ke_ctx* ctx, int32_t n, int32_t* status, int32_t* tried_
 int ke_debug_gangs(ke_ctx* ctx, int64_t* out4);
 /* sizeof() of {ke_gang_run}; returns their count (ke_abi_struct_sizes keeps its list) */
 int ke_abi_gang_struct_sizes(int32_t* sizes, int32_t n);
+/* DeviceShare members (additive: KE_ABI_VERSION stays 14; off by default, answered without a device).  With on != 0 a
+ * member of a run may be a DeviceShare pod -- GPU whole or shared (core / memory / memory-ratio), RDMA, FPGA, on nodes
+ * with or without partition tables, honor policies and topology scopes -- and members share batches with DeviceShare
+ * pods.  A rolled-back member's devices are returned on the device as ke_pod_release returns them on the host
+ * (updateCacheUsed(allocation, pod, false) -> updateDeviceUsed, device_cache.go:132-209): per taken minor the amounts
+ * Reserve added, fillGPUTotalMem's derived key included (devicehandler_gpu.go:98-133), are subtracted with
+ * quotav1.SubtractWithNonNegativeResult over the keys of both (device_cache.go:184-209), and a minor whose used is all
+ * zero afterwards (quotav1.IsZero) has its used entry deleted: its used keys are absent again, also keys that were
+ * present with value 0 before the run.  Such a member reads as unplaced: chosen -1, device_minors 0 in
+ * ke_last_allocations / ke_last_device_allocations, ke_unreserve a no-op.
+ * Still refused with the switch on (KE_ERR_UNSUPPORTED): members with device hints / joint allocation / VFs, cpuset and
+ * NUMA-policy members, everything else on the list above; a DeviceShare member together with an ElasticQuota tree or in a
+ * context without nodes (node sets and score tables refuse every DeviceShare pod of a ke_schedule call already). */
+int ke_set_gang_devices(ke_ctx* ctx, int32_t on);
+/* The last ke_schedule, or the call ke_schedule_wait collected last: out4[0] DeviceShare inverses applied on the device,
+ * out4[1] DeviceShare batch cuts taken inside an open run, out4[2] changed slots adopted for members an earlier launch
+ * of the batch placed, out4[3] launches that went on from a restored run state. */
+int ke_debug_gang_devices(ke_ctx* ctx, int64_t* out4);
 
 #ifdef __cplusplus
 }

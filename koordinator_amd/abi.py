@@ -598,6 +598,8 @@ EXPORTS = {
     "ke_pod_gangs": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
     "ke_last_gang_status": (C.c_int, [C.c_void_p, i32, C.c_void_p, C.c_void_p]),
     "ke_debug_gangs": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ke_set_gang_devices": (C.c_int, [C.c_void_p, i32]),
+    "ke_debug_gang_devices": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ke_abi_gang_struct_sizes": (C.c_int, [C.POINTER(i32), i32]),
     "ke_node_devices_set": (C.c_int, [C.c_void_p, i32, i32, C.c_void_p]),
     "ke_node_gpu_partitions": (C.c_int, [C.c_void_p, i32, i32, i32, i32, C.c_void_p]),
@@ -670,6 +672,7 @@ EXPORTS = {
     "ke_debug_kernel_phases": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ke_debug_check_records": (C.c_int, [C.c_void_p, i64, C.POINTER(i64)]),
     "ke_debug_spread_groups_check": (C.c_int, [C.c_void_p, C.POINTER(i64)]),
+    "ke_debug_devices_check": (C.c_int, [C.c_void_p, C.POINTER(i64)]),
     "ke_debug_spread_domains_check": (C.c_int, [C.c_void_p, C.POINTER(i64)]),
     "ke_last_host_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ke_last_resolve_split": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

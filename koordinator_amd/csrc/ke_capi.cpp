@@ -37,6 +37,7 @@ int device_check_records(Context* ctx, int64_t now, int64_t* bad);
 // (weak: a host-only build of this file, without ke_kernels.hip, links without it -- there is no device copy to check)
 int device_spread_groups_check(Context* ctx, int64_t* bad) __attribute__((weak));
 int device_spread_domains_check(Context* ctx, int64_t* bad) __attribute__((weak));
+int device_devices_check(Context* ctx, int64_t* bad) __attribute__((weak));
 int device_preempt(Context* ctx, int32_t n_pods, const ke_pod* pods, const PreemptPod* pre, int64_t now, ke_preemption* out,
                    int32_t victims_cap, int64_t* victim_uids, int32_t words_per_pod, uint64_t* candidates)
     __attribute__((weak));
@@ -1263,6 +1264,17 @@ int ke_debug_gangs(ke_ctx* ctx, int64_t* out4) {
   for (int i = 0; i < 4; i++) out4[i] = ctx->c.last.gang_counts[i];
   return KE_OK;
 }
+int ke_set_gang_devices(ke_ctx* ctx, int32_t on) {
+  if (ctx) async_drain(ctx);
+  if (!ctx) return fail(KE_ERR_INVALID, "null context");
+  ctx->c.gang_devices = on != 0;
+  return KE_OK;
+}
+int ke_debug_gang_devices(ke_ctx* ctx, int64_t* out4) {
+  if (!ctx || !out4) return fail(KE_ERR_INVALID, "ke_debug_gang_devices arguments");
+  for (int i = 0; i < 4; i++) out4[i] = ctx->c.last.gang_dev_counts[i];
+  return KE_OK;
+}
 
 // The staged runs of this ke_schedule / ke_schedule_submit call (behind take_node_sets, which reset Context::att),
 // consumed whether the call goes on or not.  Every refusal of a gang call is raised here, before any state changes and
@@ -1296,7 +1308,12 @@ static int take_gangs(ke_ctx* ctx, int32_t n_pods, const ke_pod* pods) {
         return no("a member whose quota Reserve refreshes the runtime quota (a segment barrier)");
       const uint32_t f = make_dev_pod(c.cfg, pods[p], pod_hints(c, pods[p]), &c.tmpl).flags;
       if (f & PF_DS_HINT) return no("a member with device hints");
-      if (f & PF_DS) return no("a DeviceShare member");
+      if ((f & PF_DS) && c.gang_devices) {
+        if (!c.quotas.empty()) return no("a DeviceShare member together with an ElasticQuota tree");
+        if (c.n_nodes <= 0) return no("a DeviceShare member in a context without nodes");
+      } else if (f & PF_DS) {
+        return no("a DeviceShare member");
+      }
       if (f & PF_CPUSET) return no("a cpuset member");
     }
   }
@@ -2048,6 +2065,15 @@ int ke_debug_spread_domains_check(ke_ctx* ctx, int64_t* mismatched) {
   *mismatched = 0;
   if (!ctx->c.dev || !device_spread_domains_check) return KE_OK;  // (no device copy yet)
   return device_spread_domains_check(&ctx->c, mismatched);
+}
+
+int ke_debug_devices_check(ke_ctx* ctx, int64_t* mismatched_nodes) {
+  if (ctx) async_drain(ctx);
+  if (!ctx || !mismatched_nodes) return fail(KE_ERR_INVALID, "ke_debug_devices_check arguments");
+  *mismatched_nodes = 0;
+  flush_mirror(ctx->c);
+  if (!ctx->c.dev || !device_devices_check) return KE_OK;  // (no device copy yet)
+  return device_devices_check(&ctx->c, mismatched_nodes);
 }
 
 int ke_set_pipeline(ke_ctx* ctx, int32_t on) {

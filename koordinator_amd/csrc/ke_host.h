@@ -273,6 +273,7 @@ struct Context {
   AttachSlot<ke_gang_run> pod_gangs;
   int32_t pod_gangs_n = 0;
   std::vector<int32_t> gang_words;
+  bool gang_devices = false;  // ke_set_gang_devices: a member may be a DeviceShare pod
   // Resident pods and PDB budgets (ke_resident_pods_load / ke_pdbs_load; ke_preempt.h): the caller's
   // statement of which pods sit on which node, beside the rows and never folded into them.  The device copies are
   // uploaded whole by the next ke_preempt after a change (residents.dirty / pdb_dirty).

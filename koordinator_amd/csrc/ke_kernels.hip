@@ -234,6 +234,7 @@ constexpr int DSB_MAX = 0, DSB_CNT = 64, DSB_CUT = 128, DSB_WORDS = 129;
 // kerr bits: an input the kernels refuse mid-call (the call returns KE_ERR_UNSUPPORTED)
 constexpr int32_t KERR_HINT_ROUTE = 2;  // a hinted pod reached a kernel instantiated without the hint path (H)
 constexpr int32_t KERR_LDS_WAIT = 4;    // a bounded intra-workgroup LDS wait of the replay expired (internal)
+constexpr int32_t KERR_GANG_STATE = 8;  // a gang run's state restored behind a DSB_CUT lies outside its batch (internal)
 
 // ---------------------------------------------------------------------------------------------
 // ElasticQuota PreFilter / Reserve (elasticquota/plugin.go:223-275,345-359; plugin_helper.go:281-301;
@@ -2498,6 +2499,13 @@ __device__ __forceinline__ void ext_reserve(const SoA& s, int64_t i, const DevPo
   for (int q = 0; q < NUM_XS; q++)
     if (q < k.xs_n) s.xf[(XF_REQ + q) * s.stride + i] += p.xreq[q];
   s.xf[XF_PODS * s.stride + i] -= 1;
+}
+// its inverse (a gang rollback in a DeviceShare batch)
+__device__ __forceinline__ void ext_unreserve(const SoA& s, int64_t i, const DevPod& p, const KArgs& k) {
+#pragma unroll
+  for (int q = 0; q < NUM_XS; q++)
+    if (q < k.xs_n) s.xf[(XF_REQ + q) * s.stride + i] -= p.xreq[q];
+  s.xf[XF_PODS * s.stride + i] += 1;
 }
 
 template <bool DS, bool NUMA, bool DEFER = false, bool FB_AFF = false, bool CPU = false, bool H = false>
@@ -6155,7 +6163,89 @@ struct GangIO {
   int32_t* status;
   int32_t* tried;
   int32_t* counts;
+  // DeviceShare members ("DeviceShare members"): the call's pod records, for a rollback that reaches a
+  // member an earlier launch of the batch placed.  counts[GC_DS ..] are ke_debug_gang_devices' four counters,
+  // counts[GC_STATE ..] the run's state across a DSB_CUT: first position in the call, waiting count, satisfied, failed
+  const DevPod* pods = nullptr;
 };
+
+// The inverse of the DeviceShare Reserve (ds_reserve / ds_reserve_wave) of pod p on node i, whose Reserve took `minors`
+// (bit 16 * type + minor): what ke_pod_release does on the host -- updateCacheUsed(allocation, pod, false) ->
+// updateDeviceUsed (device_cache.go:184-209).  Per taken instance the amounts Reserve added (the request and
+// fillGPUTotalMem's derived key, devicehandler_gpu.go:98-133) are subtracted with quotav1.SubtractWithNonNegativeResult
+// over the keys of both, and an instance whose used is all zero afterwards loses its used keys (quotav1.IsZero: the
+// minor's entry is deleted).  One lane; plain vector stores.
+__device__ __noinline__ void ds_unreserve(const SoA& s, int64_t i, const DevPod& p, uint64_t minors) {
+  uint64_t msk[4];
+#pragma unroll
+  for (int w = 0; w < 4; w++) msk[w] = dsmask(s, w, i);
+  for (int t = 0; t < 3; t++) {
+    const int nk = DS_NK[t];
+    const int w = ds_hu_word(t);
+    for (uint32_t rest = (uint32_t)(minors >> (16 * t)) & 0xFFFFu; rest; rest &= rest - 1) {
+      const int m = __builtin_ctz(rest);
+      int64_t alloc[3] = {0, 0, 0};
+      bool has[3] = {false, false, false};
+      if (t == KE_DEV_GPU) {
+        const bool htm = (msk[DSM_GPU_HT] >> ds_ht_bit(0, m, 1)) & 1;
+        const int64_t tm = htm ? dsf(s, DS_TBASE[0] + m * 3 + 1, i) : 0;
+        if (p.flags & PF_DS_H_CORE) has[0] = true, alloc[0] = p.ds_req[0];
+        if (p.flags & PF_DS_H_RATIO) {  // memoryRatioToBytes
+          has[2] = true, alloc[2] = p.ds_req[2];
+          has[1] = true, alloc[1] = p.ds_req[2] * tm / 100;
+        } else if (p.flags & PF_DS_H_MEM) {  // memoryBytesToRatio: int64(float64(b)/float64(total)*100)
+          has[1] = true, alloc[1] = p.ds_req[1];
+          has[2] = true, alloc[2] = (int64_t)((double)p.ds_req[1] / (double)tm * 100.0);
+        }
+      } else {
+        has[0] = true, alloc[0] = p.ds_req[2 + t];
+      }
+      bool zero = true;
+      for (int key = 0; key < nk; key++) {
+        const int b = ds_hu_bit(t, m, key);
+        const int field = DS_UBASE[t] + m * nk + key;
+        const bool hu = (msk[w] >> b) & 1;
+        int64_t v = hu ? dsf(s, field, i) : 0;
+        if (has[key]) {
+          v -= alloc[key];
+          v = v > 0 ? v : 0;
+          s.ds[field * s.stride + i] = v;
+          msk[w] |= 1ull << b;
+        } else if (hu && v < 0) {
+          v = 0;
+          s.ds[field * s.stride + i] = v;
+        }
+        zero = zero && (!((msk[w] >> b) & 1) || v == 0);
+      }
+      if (zero)
+        for (int key = 0; key < nk; key++) {
+          s.ds[(DS_UBASE[t] + m * nk + key) * s.stride + i] = 0;
+          msk[w] &= ~(1ull << ds_hu_bit(t, m, key));
+        }
+    }
+  }
+#pragma unroll
+  for (int w = 1; w < 4; w++) s.dsm[w * s.stride + i] = msk[w];
+}
+// Reserve of pod p on a full row (SIGN 1), and its inverse (SIGN -1, a gang rollback in a DeviceShare batch): LoadAware
+// assign -- the pod counted at its estimate in every non-prod term, and in the prod terms when it is prod -- and
+// NodeInfo.Requested += requests
+template <int SIGN>
+__device__ __forceinline__ void row_reserve(NodeRegs& n, const DevPod& p) {
+  if ((n.flags & NF_HAS_METRIC) && !(n.flags & NF_NM_NIL)) {
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      if (n.flags & nf_fh_on(0, q)) n.fh[0][q] -= SIGN * p.est[q];
+      n.sa[0][q] -= SIGN * p.est[q];
+      if (p.flags & PF_PROD) {
+        if (n.flags & nf_fh_on(1, q)) n.fh[1][q] -= SIGN * p.est[q];
+        n.sa[1][q] -= SIGN * p.est[q];
+      }
+    }
+  }
+  n.nreq[0] += SIGN * p.req[0];
+  n.nreq[1] += SIGN * p.req[1];
+}
 template <bool DS, bool NUMA, bool QUOTA, bool EXT, int NS, bool GANG = false>
 __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const SoA& s, const int base, const int B,
                                              const KArgs& k, int32_t* __restrict__ chosen,
@@ -6304,7 +6394,8 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
                                              int64_t* __restrict__ touched_out, int32_t* __restrict__ touched_cnt,
                                              uint64_t* __restrict__ pst, const GangIO gio) {
   static_assert(!NS || (!DS && !NUMA), "node sets: plain batches only");
-  static_assert(!GANG || (!DS && !NUMA && NS < NS_GROUPS), "gang batches: plain pods, no spread kind");
+  static_assert(!GANG || (!NUMA && NS < NS_GROUPS), "gang batches: no NUMA policies, no spread kind");
+  static_assert(!GANG || !DS || !QUOTA, "gang batches with DeviceShare members: no ElasticQuota tree");
   const uint32_t* const s_cand = L.cand;
   const DevPod* const s_pod = L.pod;
   const int lane = threadIdx.x & 63;
@@ -6365,6 +6456,22 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
   bool g_failed = false, g_sat = false;
   int32_t o_owner = -1, o_status = KE_GANG_NONE, o_tried = -1;
   if constexpr (GANG) gw = __builtin_amdgcn_readfirstlane(gio.words[base]);
+  // GANG with DS: ke_debug_gang_devices' counters; a launch whose first pod lies inside a run -- the remainder of a batch
+  // a DSB_CUT stopped there -- takes the run's state from the call's gang block (g_first < 0: the run began before `base`)
+  int g_dsinv = 0, g_cutrun = 0, g_adopt = 0, g_rest = 0;
+  if constexpr (GANG && DS) {
+    if ((gw & GW_MEMBER) && !(gw & GW_FIRST)) {
+      g_first = __builtin_amdgcn_readfirstlane(gio.counts[GC_STATE + 0]) - base;
+      g_wait = __builtin_amdgcn_readfirstlane(gio.counts[GC_STATE + 1]);
+      g_sat = __builtin_amdgcn_readfirstlane(gio.counts[GC_STATE + 2]) != 0;
+      g_failed = __builtin_amdgcn_readfirstlane(gio.counts[GC_STATE + 3]) != 0;
+      g_rest = 1;
+      if (g_first > 0 || g_first <= -MAX_BATCH) {  // no run start a cut of this batch can have stored: the call fails
+        if (lane == 0) __hip_atomic_fetch_or(s.kerr, KERR_GANG_STATE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        g_first = 0;  // (the rollback loop stays inside the launch's pods)
+      }
+    }
+  }
   RPROF_DECL
   for (int j = 0; j < B; j++) {
     const bool more = j + 1 < B;
@@ -6458,9 +6565,23 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
         const uint32_t cmax = wave_max_u32(craw);
         // snapshot max-attaining nodes that changed since: the rest still attain m0
         const int lost = __popcll(__ballot(lane < n_chg && snap == m0));
-        const bool safe = m0 == 0 ? cmax == 0 : (cmax <= m0 && L.dsc[j] > lost);
+        bool safe = m0 == 0 ? cmax == 0 : (cmax <= m0 && L.dsc[j] > lost);
+        // (a gang batch: with no node changed the snapshot is the current state -- a singleton's argmax select leaves
+        // no count of the max-attaining nodes behind, and the first pod of a launch never stops it)
+        if constexpr (GANG) safe = safe || n_chg == 0;
         if (!safe) {
           if (lane == 0) s.dsb[DSB_CUT] = (uint32_t)(base + j);
+          if constexpr (GANG) {  // a cut inside an open run: the relaunch of pods j.. goes on from the run's state
+            if ((gw & GW_MEMBER) && !(gw & GW_FIRST)) {
+              g_cutrun = 1;
+              if (lane == 0) {
+                gio.counts[GC_STATE + 0] = base + g_first;
+                gio.counts[GC_STATE + 1] = g_wait;
+                gio.counts[GC_STATE + 2] = g_sat;
+                gio.counts[GC_STATE + 3] = g_failed;
+              }
+            }
+          }
           break;
         }
       }
@@ -6504,19 +6625,7 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
           fast_reserve(fast, pod, estd, reqd);
           if (EXT && (k.flags & AF_EXT)) ext_fast_reserve(fast, pod, k);  // NodeInfo (NonZero)Requested, Pods
         } else {
-          if ((mine.flags & NF_HAS_METRIC) && !(mine.flags & NF_NM_NIL)) {
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-              if (mine.flags & nf_fh_on(0, q)) mine.fh[0][q] -= pod.est[q];
-              mine.sa[0][q] -= pod.est[q];
-              if (pod.flags & PF_PROD) {
-                if (mine.flags & nf_fh_on(1, q)) mine.fh[1][q] -= pod.est[q];
-                mine.sa[1][q] -= pod.est[q];
-              }
-            }
-          }
-          mine.nreq[0] += pod.req[0];
-          mine.nreq[1] += pod.req[1];
+          row_reserve<1>(mine, pod);
         }
         if (!FAST && (k.flags & AF_EXT)) ext_reserve(s, my_node, pod, k);  // read back by the next re-evaluations
         if constexpr (NS >= NS_GROUPS) {  // the spread group's count on this node (a winner is below its cap: no wrap)
@@ -6594,6 +6703,10 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
           if (!g_sat && g_wait >= gw_need(gw)) {
             g_sat = true;
             if (lane >= g_first && lane <= j && o_status == KE_GANG_WAITING) o_status = KE_GANG_PLACED;
+            if constexpr (DS) {  // the members an earlier launch of the batch placed: their statuses in the call's block
+              if (lane < -g_first && gio.status[base + g_first + lane] == KE_GANG_WAITING)
+                gio.status[base + g_first + lane] = KE_GANG_PLACED;
+            }
           }
         }
       }
@@ -6604,17 +6717,63 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
         if (gw & GW_STRICT) {
           g_rolled++;
           for (int m = g_first; m < j; m++) {  // (wave-uniform bounds and conditions: readlane of lane m's registers)
-            if (__builtin_amdgcn_readlane(o_node, m) < 0) continue;
-            const int ow = __builtin_amdgcn_readlane(o_owner, m);
-            const DevPod pm = s_pod[m];
-            const double em[2] = {L.pd[m][0], L.pd[m][1]}, rm[2] = {L.pd[m][2], L.pd[m][3]};
-            if (lane == ow) {
-              fast_unreserve(fast, pm, em, rm);
-              if (EXT && (k.flags & AF_EXT)) ext_fast_unreserve(fast, pm, k);
+            if constexpr (DS) {
+              // full rows, the ext words in memory, the devices in the global SoA: three inverses.  A member an earlier
+              // launch of the batch placed (m < 0) has its node, minors and status in the call's outputs and its record
+              // in the call's pod array; its node becomes a changed slot of this launch unless it is one already
+              const int pos = base + m;
+              const int32_t on = m >= 0 ? __builtin_amdgcn_readlane(o_node, m) : __builtin_amdgcn_readfirstlane(chosen[pos]);
+              if (on < 0) continue;
+              const int nd = on - global_offset;
+              uint64_t am;  // the member's minors: lane m's o_alloc, or what the earlier launch wrote
+              if (m >= 0)
+                am = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(o_alloc >> 32), m) << 32) |
+                     (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)o_alloc, m);
+              else
+                am = dev_alloc[pos];
+              const DevPod pm = m >= 0 ? s_pod[m] : gio.pods[pos];
+              int ow = __ffsll((unsigned long long)__ballot(lane < n_chg && my_node == nd)) - 1;
+              if (ow < 0) {  // adopted: lane n_chg loads the row (no pod's spare row is in flight behind a failed pod)
+                ow = n_chg++;
+                g_adopt++;
+                if (lane == ow) {
+                  load_row_sc1(s, nd, spare);
+                  my_node = nd;
+                  regs_from_row(spare, mine);
+                  prepare_row(mine);
+                  my_expired = node_expired(mine, k);
+                  chg_set(C, my_node);
+                }
+              }
+              if (lane == ow) {
+                row_reserve<-1>(mine, pm);  // the inverse: the same terms under the same conditions
+                if (k.flags & AF_EXT) ext_unreserve(s, my_node, pm, k);
+                if ((pm.flags & PF_DS) && am) ds_unreserve(s, my_node, pm, am);
+              }
+              if ((pm.flags & PF_DS) && am) g_dsinv++;
+              if (m >= 0) {
+                if (lane == m) o_tried = o_node, o_node = -1, o_score = -1, o_owner = -1, o_alloc = 0, o_status = KE_GANG_ROLLED_BACK;
+              } else if (lane == 0) {
+                chosen[pos] = -1;
+                chosen_score[pos] = -1;
+                dev_alloc[pos] = 0;
+                gio.tried[pos] = on;
+                gio.status[pos] = KE_GANG_ROLLED_BACK;
+              }
+              g_inv++;
+            } else {
+              if (__builtin_amdgcn_readlane(o_node, m) < 0) continue;
+              const int ow = __builtin_amdgcn_readlane(o_owner, m);
+              const DevPod pm = s_pod[m];
+              const double em[2] = {L.pd[m][0], L.pd[m][1]}, rm[2] = {L.pd[m][2], L.pd[m][3]};
+              if (lane == ow) {
+                fast_unreserve(fast, pm, em, rm);
+                if (EXT && (k.flags & AF_EXT)) ext_fast_unreserve(fast, pm, k);
+              }
+              if (QUOTA && pm.quota) quota_unreserve_r(s, pm, Q, lane);
+              if (lane == m) o_tried = o_node, o_node = -1, o_score = -1, o_owner = -1, o_status = KE_GANG_ROLLED_BACK;
+              g_inv++;
             }
-            if (QUOTA && pm.quota) quota_unreserve_r(s, pm, Q, lane);
-            if (lane == m) o_tried = o_node, o_node = -1, o_score = -1, o_owner = -1, o_status = KE_GANG_ROLLED_BACK;
-            g_inv++;
           }
         }
       }
@@ -6677,6 +6836,12 @@ __device__ __forceinline__ void replay_batch(ResLds& L, const ChgSet& C, const S
     if (lane == 0) {  // (the call's batches run one after another on one stream: no other writer)
       gio.counts[0] += g_rolled;
       gio.counts[1] += g_inv;
+      if constexpr (DS) {
+        gio.counts[GC_DS + 0] += g_dsinv;
+        gio.counts[GC_DS + 1] += g_cutrun;
+        gio.counts[GC_DS + 2] += g_adopt;
+        gio.counts[GC_DS + 3] += g_rest;
+      }
     }
   }
   if (QUOTA)
@@ -8943,7 +9108,7 @@ static unsigned resolve_threads(bool numa) { return numa ? res_threads<true>() :
 struct GangIO;
 using ResolveGangFn = void (*)(SoA, const DevPod*, const int32_t*, int, KArgs, const uint32_t*, const int32_t*, int32_t*,
                                int32_t*, int32_t, uint64_t*, uint64_t*, int, uint64_t*, uint32_t*, int, int, GangIO);
-static ResolveGangFn pick_resolve_gang(bool quota, int ns);
+static ResolveGangFn pick_resolve_gang(bool quota, int ns, bool ds);
 // QUOTA x EXT, or NS x EXT without quota
 using ResolveRunFn = decltype(&k_resolve_run<false, false>);
 static ResolveRunFn pick_resolve_run(bool quota, bool ext, int ns) {
@@ -9343,6 +9508,7 @@ static int complete_gangs(const Completion& c, const int32_t* chosen) {
   ctx->last.fill_gangs(np, status, tried, true);
   const int64_t all[4] = {cnt.runs, counts[0], counts[1], c.gang_cuts};
   std::copy(all, all + 4, ctx->last.gang_counts);
+  for (int i = 0; i < 4; i++) ctx->last.gang_dev_counts[i] = counts[GC_DS + i];
   return KE_OK;
 }
 
@@ -9385,6 +9551,7 @@ static int complete_call(const Completion& c, int32_t* chosen, int32_t* score) {
     (void)hipMemset(d->d_parts_done, 0, sizeof(int32_t) * 2 * MAX_BATCH);  // (an aborted launch's counts)
     return fail(KE_ERR_DEVICE, "pipelined schedule: a device-side hand-off timed out (placements invalid)");
   }
+  if (kerr & KERR_GANG_STATE) return fail(KE_ERR_DEVICE, "internal: a gang run's state behind a cut lies outside its batch");
   if (kerr & (KERR_HINT_ROUTE | KERR_LDS_WAIT)) {  // internal errors: the placements are not the reference's
     return fail(KE_ERR_DEVICE, (kerr & KERR_LDS_WAIT) ? "internal: a replay LDS wait expired (placements invalid)"
                                                       : "internal: a hinted pod reached a kernel without the hint path");
@@ -9525,7 +9692,8 @@ struct ScheduleCall {
     knob = select_knob(std::getenv("KOORDEVAL_SELECT_PARTS"));
     ctx->last_ds_cuts = 0;
     batches = plan_batches(c.host_pods.data(), n_pods, ctx->cfg.pod_batch, !sharded && !numa && N > 0, fused,
-                           att.plan_groups(), att.plan_domains(), att.plan_dterms(), att.gangs, &gang_cuts);
+                           att.plan_groups(), att.plan_domains(), att.plan_dterms(), att.gangs, &gang_cuts,
+                           ctx->gang_devices && !quota);
     for (const Batch& b : batches) any_cpu = any_cpu || b.cpu;
     if (any_cpu && !d->has(ST_CPU)) return fail(KE_ERR_DEVICE, "cpuset pod without the CPU SoA");
     n_batches = (int)batches.size();
@@ -9571,10 +9739,10 @@ struct ScheduleCall {
     // k_call_begin, only in a call with a cpuset pod)
     RC_OK(c.d_cpusets.reserve(4 * np));
     if (att.gangs) {  // status, tried node, the two counters: every pod's entry starts as "outside a run"
-      RC_OK(c.d_gang.reserve(2 * np + 2));
+      RC_OK(c.d_gang.reserve(2 * np + GC_WORDS));
       HIP_OK(fill_async(c.d_gang, 0, sizeof(int32_t) * np, d->stream));
       HIP_OK(fill_async(c.d_gang + np, 0xFF, sizeof(int32_t) * np, d->stream));
-      HIP_OK(fill_async(c.d_gang + 2 * np, 0, sizeof(int32_t) * 2, d->stream));
+      HIP_OK(fill_async(c.d_gang + 2 * np, 0, sizeof(int32_t) * GC_WORDS, d->stream));
     }
     bool any_hint = false;
     for (const DevPod& q : c.host_pods) any_hint = any_hint || (q.flags & PF_DS_HINT);
@@ -9957,13 +10125,18 @@ struct ScheduleCall {
     // one pod: the single-node Reserve (cpuset accumulator when it binds) -- but a grouped singleton takes the
     // replay, which keeps the spread group counts
     if (gang_batch(b)) {
-      const auto resolve = pick_resolve_gang(quota, batch_ns(b));
-      if (!resolve || ds || cpu || numa) return no_variant("k_resolve_gang with a DeviceShare / cpuset batch, NUMA, or quota with node sets");
+      const auto resolve = pick_resolve_gang(quota, batch_ns(b), ds);
+      if (!resolve || (ds && !ctx->gang_devices) || cpu || numa)
+        return no_variant("k_resolve_gang with a DeviceShare / cpuset batch, NUMA, or quota with node sets");
       const size_t np = (size_t)n_pods;
       hipLaunchKernelGGL(resolve, dim3(1), dim3(resolve_threads(false)), 0, d->stream, d->soa, c.d_pods, bbase, bp, k,
                          d->d_cand, d->d_cand_cnt, d_chosen, d_chosen_score, ctx->cfg.global_node_offset, d_st, d_pst, b,
                          c.d_devalloc, d->d_chg, N, (int)sel[(size_t)b].sorted,
-                         GangIO{c.d_gang_words, c.d_gang, c.d_gang + np, c.d_gang + 2 * np});
+                         GangIO{c.d_gang_words, c.d_gang, c.d_gang + np, c.d_gang + 2 * np, c.d_pods});
+      bool again = false;  // (a singleton never stops: its first pod sees no changed node)
+      if (batches[b].cut && bp > 1 && (rc = cut_check(b, &again))) return rc;
+      rerun = again;
+      if (again) return KE_OK;
     } else if (bp == 1 && !batches[b].grouped) {
       int elo = 0, ehi = 0;  // nodes whose affinities this batch's eval stored in d_aff (binding batches)
       if (cpu && numa) {
@@ -10013,7 +10186,16 @@ struct ScheduleCall {
     if (cut <= bases[b] || cut >= end) return fail(KE_ERR_DEVICE, "DeviceShare batch cut out of range");
     batches[b].pods = end - cut;  // (its pod count changed: its select is planned again)
     bases[b] = cut;
-    sel[(size_t)b] = plan_select(N, batches[b], SEL_EXACT, sharded, knob);
+    if (att.gangs) batches[b].grouped = gang_batch(b);  // (a gang call's batches are grouped by their members alone)
+    // a cut inside an open gang run: a later rollback may reach the run's members before the cut and adopt their nodes
+    // as changed slots, so pod j of the relaunch needs its exact top-(j + 1 + P), P = the run's positions before the cut
+    int open_members = 0;
+    if (att.gangs && (att.gangs[cut] & GW_MEMBER) && !(att.gangs[cut] & GW_FIRST))
+      for (int p = cut - 1; p >= 0 && (att.gangs[p] & GW_MEMBER); p--) {
+        open_members++;
+        if (att.gangs[p] & GW_FIRST) break;
+      }
+    sel[(size_t)b] = plan_select(N, batches[b], SEL_EXACT, sharded, knob, open_members);
     HIP_OK(copy_async(d_bases + b, &bases[b], sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
     ctx->last_ds_cuts++;
     *again = true;
@@ -10042,7 +10224,7 @@ struct ScheduleCall {
     if (vf_out) HIP_OK(copy_async(h + ho.vf, d->d_vfo, 2 * DS_MINORS * np, hipMemcpyDeviceToHost, d->stream));
     if (numa) HIP_OK(copy_async(h + ho.numa, c.d_numaalloc, 8 * 16 * np, hipMemcpyDeviceToHost, d->stream));
     if (numa) HIP_OK(copy_async(h + ho.dcnt, d->d_defer_cnt, 4 * nb, hipMemcpyDeviceToHost, d->stream));
-    if (att.gangs) HIP_OK(copy_async(h + ho.gang, c.d_gang, 4 * (2 * np + 2), hipMemcpyDeviceToHost, d->stream));
+    if (att.gangs) HIP_OK(copy_async(h + ho.gang, c.d_gang, 4 * (2 * np + GC_WORDS), hipMemcpyDeviceToHost, d->stream));
     // the call's end on every stream: its completion waits for these events, not for the streams
     HIP_OK(hipEventRecord(done_ev[0], d->stream));
     HIP_OK(hipEventRecord(done_ev[1], d->estream));
@@ -10222,6 +10404,33 @@ int device_spread_groups_check(Context* ctx, int64_t* bad) {
   return KE_OK;
 }
 
+// the device's DeviceShare SoA -- fields and mask words of every node whose host state the device has -- against a
+// from-scratch host derivation (test of the Reserves, and of a gang rollback's ds_unreserve)
+int device_devices_check(Context* ctx, int64_t* bad) {
+  DeviceState* d = ctx->dev;
+  *bad = 0;
+  if (!d->soa.ds || !d->soa.dsm) return KE_OK;  // (no device copy)
+  HIP_OK(hipSetDevice(d->device));
+  const int64_t S = d->capacity, n = std::min<int64_t>(ctx->n_nodes, S);
+  std::vector<int64_t> f((size_t)(NUM_DS_FIELDS * S));
+  std::vector<uint64_t> m((size_t)(NUM_DS_MASKS * S));
+  HIP_OK(hipMemcpyAsync(f.data(), d->soa.ds, sizeof(int64_t) * f.size(), hipMemcpyDeviceToHost, d->stream));
+  HIP_OK(hipMemcpyAsync(m.data(), d->soa.dsm, sizeof(uint64_t) * m.size(), hipMemcpyDeviceToHost, d->stream));
+  HIP_OK(hipStreamSynchronize(d->stream));
+  for (int64_t i = 0; i < n; i++) {
+    const NodeState& ns = ctx->nodes[(size_t)i];
+    if (ns.dirty) continue;  // (the next refresh replaces its rows)
+    int64_t hf[NUM_DS_FIELDS];
+    uint64_t hm[NUM_DS_MASKS];
+    derive_ds_row(ns, hf, hm);
+    bool same = true;
+    for (int w = 0; w < NUM_DS_FIELDS; w++) same = same && f[(size_t)(w * S + i)] == hf[w];
+    for (int w = 0; w < NUM_DS_MASKS; w++) same = same && m[(size_t)(w * S + i)] == hm[w];
+    *bad += !same;
+  }
+  return KE_OK;
+}
+
 // ... and the spread domain counts and maps
 int device_spread_domains_check(Context* ctx, int64_t* bad) {
   DeviceState* d = ctx->dev;
@@ -10301,7 +10510,26 @@ __global__ __launch_bounds__(res_threads<false>()) void k_resolve_gang(SoA s, co
                                                      nullptr, nullptr, nullptr, false, false, KMAX, sorted != 0, nullptr,
                                                      THelp{nullptr, nullptr, nullptr, 0, 0, nullptr}, gio);
 }
-static ResolveGangFn pick_resolve_gang(bool quota, int ns) {
+// a DeviceShare batch holding members (ke_set_gang_devices): full rows, the device SoA, the run's state across a cut
+__global__ __launch_bounds__(res_threads<false>()) void k_resolve_gang_ds(SoA s, const DevPod* __restrict__ pods,
+                                                                          const int32_t* __restrict__ batch_base, int batch_pods,
+                                                                          KArgs k, const uint32_t* __restrict__ cand,
+                                                                          const int32_t* __restrict__ cand_cnt,
+                                                                          int32_t* __restrict__ chosen,
+                                                                          int32_t* __restrict__ chosen_score, int32_t global_offset,
+                                                                          uint64_t* __restrict__ stamps, uint64_t* __restrict__ pstamps,
+                                                                          int batch_index, uint64_t* __restrict__ dev_alloc,
+                                                                          uint32_t* __restrict__ chg_glb, int n_nodes, int sorted,
+                                                                          GangIO gio) {
+  __shared__ ResLds L;
+  const ChgSet C = chg_init(L, chg_glb, n_nodes);
+  resolve_batch<true, false, false, true, 0, true>(L, C, s, pods, *batch_base, batch_pods, k, cand, cand_cnt, chosen,
+                                                   chosen_score, global_offset, stamps, pstamps, batch_index, dev_alloc,
+                                                   nullptr, nullptr, nullptr, false, false, KMAX, sorted != 0, nullptr,
+                                                   THelp{nullptr, nullptr, nullptr, 0, 0, nullptr}, gio);
+}
+static ResolveGangFn pick_resolve_gang(bool quota, int ns, bool ds) {
+  if (ds) return quota || ns ? nullptr : k_resolve_gang_ds;
   if (quota) return ns ? nullptr : k_resolve_gang<true, 0>;
   return ns == NS_SCORES ? k_resolve_gang<false, NS_SCORES>
          : ns == NS_SETS ? k_resolve_gang<false, NS_SETS>

@@ -97,10 +97,13 @@ struct Batch {
 // ends before a run that would not fit in it whole (*gang_cuts counts these) -- a batch holding a member holds no
 // DeviceShare pod (a DSB_CUT in mid-run would lose the run's state), and it is `grouped`.  Batches without a member are
 // planned as without the words, and with every word zero the plan is the one without them.
+// `gang_devices` (ke_set_gang_devices; DESIGN.md §4w, "DeviceShare members"): a member may be a DeviceShare pod and share
+// its batch with DeviceShare pods -- the replay keeps the run's state across a DSB_CUT -- so that rule is dropped; the
+// batch stays `grouped`, and `cut` as any DeviceShare batch of more than one pod.
 inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bool ds_batch, bool fused,
                                        const int32_t* group_ids = nullptr, const int32_t* domain_ids = nullptr,
                                        const PodTerms* dterms = nullptr, const int32_t* gangs = nullptr,
-                                       int* gang_cuts = nullptr) {
+                                       int* gang_cuts = nullptr, bool gang_devices = false) {
   std::vector<Batch> batches;
   if (gang_cuts) *gang_cuts = 0;
   bool has_gang = false, has_ds = false;  // of the batch being filled
@@ -113,7 +116,7 @@ inline std::vector<Batch> plan_batches(const DevPod* pods, int n_pods, int B, bo
       return true;
     }
     const bool ds = (pods[p0 + bp].flags & PF_DS) != 0;
-    return ((w & GW_MEMBER) && has_ds) || (ds && has_gang);
+    return !gang_devices && (((w & GW_MEMBER) && has_ds) || (ds && has_gang));
   };
   // pod p0 + bp reads a spread domain group that one of the bp pods from p0 on is a member of
   auto reads_written = [&](int p0, int bp) {  // (called with domain lists only)
@@ -209,11 +212,13 @@ struct SelectPlan {
 // stale lists, the k_patch schedule's count of select workgroups): these agree because the exact and stale lengths,
 // 64 and 128, both leave 1024 / L >= 8 = the cap of the parts, and the sites that passed 128 never ran for a
 // select-ahead batch (L = 192, 1024 / L = 5), whose lists k_fixlist sorts whatever the parts.
-inline SelectPlan plan_select(int n_nodes, const Batch& b, SelMode mode, bool sharded, SelectKnob kb) {
+// `extra` (an exact-mode batch only): entries beyond k_j -- the remainder of a batch a DSB_CUT stopped inside an open gang
+// run, whose rollback may adopt up to `extra` nodes of the run's earlier members as changed slots
+inline SelectPlan plan_select(int n_nodes, const Batch& b, SelMode mode, bool sharded, SelectKnob kb, int extra = 0) {
   SelectPlan s;
   s.mode = mode;
   s.L =mode == SEL_AHEAD ? KSTALE2 : mode == SEL_STALE ? KSTALE : KMAX;
-  s.kext = mode == SEL_AHEAD ? 2 * KMAX : mode == SEL_STALE ? KMAX : 0;
+  s.kext = mode == SEL_AHEAD ? 2 * KMAX : mode == SEL_STALE ? KMAX : std::min(extra, KMAX - b.pods);
   s.parts = n_nodes > 0 && !b.ds ? select_parts(n_nodes, b.pods, s.L, kb) : 1;
   s.rc_one = select_resident(0, n_nodes);
   s.rc_split = select_resident(0, select_part(0, n_nodes, s.parts));
@@ -235,6 +240,11 @@ struct Take16 {  // consecutive 16-byte aligned parts
 // word, the fixup stamps [2 nb], the batch end stamps [nb + 1] (st[0]: the call's start), the replay stamps
 // [PST nb], the eval start stamps [nb] -- and, not read back, one more eval stamp (a re-run remainder's).
 // k_call_begin zeroes the error word and the fixup stamps as one range: [err, st).
+// the tail of a call's gang block behind its statuses and tried nodes: ke_debug_gangs' two device
+// counters, ke_debug_gang_devices' four from GC_DS, and from GC_STATE the run's state across a DSB_CUT (first position in
+// the call, waiting count, satisfied, failed)
+constexpr int GC_DS = 2, GC_STATE = 6, GC_WORDS = 10;
+
 struct OutLayout {
   size_t score, chosen, err, fst, st, pst, est, end, total;
   OutLayout(size_t np, size_t nb) {
@@ -267,7 +277,7 @@ struct HostOutLayout {
   size_t chosen = 0, score = 0, err = 0, fst = 0, st = 0, pst = 0, est = 0, kerr = 0, dev = 0, cs = 0, vf = 0, numa = 0,
          dcnt = 0, gang = 0, total = 0;
   HostOutLayout() = default;
-  // (gangs: the call's gang block -- status [np], tried node [np], two counters -- behind everything else)
+  // (gangs: the call's gang block -- status [np], tried node [np], GC_WORDS words -- behind everything else)
   HostOutLayout(const OutLayout& ol, size_t np, size_t nb, bool want_score, bool any_ds, bool any_cpu, bool vf_out,
                 bool numa_on, bool gangs = false) {
     blk0 = want_score ? ol.score : ol.chosen;
@@ -278,7 +288,7 @@ struct HostOutLayout {
     kerr = take(4), dev = take(any_ds ? 8 * np : 0), cs = take(any_cpu ? 32 * np : 0);
     vf = take(vf_out ? 2 * DS_MINORS * np : 0), numa = take(numa_on ? 8 * 16 * np : 0);
     dcnt = take(numa_on ? 4 * nb : 0);
-    gang = take(gangs ? 4 * (2 * np + 2) : 0);
+    gang = take(gangs ? 4 * (2 * np + GC_WORDS) : 0);
     total = take.off;
   }
 };

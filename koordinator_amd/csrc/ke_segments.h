@@ -83,6 +83,8 @@ struct CallRecords {
   PerPod<int64_t, KE_MAX_NUMA * KE_NRES> numas;     // NUMA amounts [2*id + r]
   PerPod<int32_t, 1> gang_status, gang_tried;       // KE_GANG_* and a rolled-back member's node (a call with gang runs)
   int64_t gang_counts[4] = {0, 0, 0, 0};            // ke_debug_gangs: runs, runs rolled back, inverse Reserves, cut batches
+  // ke_debug_gang_devices: device inverses, cuts inside an open run, slots adopted, relaunches with a restored run state
+  int64_t gang_dev_counts[4] = {0, 0, 0, 0};
   size_t n = 0;          // pods the device-made kinds cover
   int32_t resv_gen = 0;  // the reservation set `resv` indexes (ke_reservations_generation)
   // per pod: 0 / nullptr = absent
@@ -99,6 +101,7 @@ struct CallRecords {
   void fill_gangs(size_t np, const int32_t* status, const int32_t* tried, bool has) {
     gang_status.fill(status, np, has), gang_tried.fill(tried, np, has);
     std::fill(gang_counts, gang_counts + 4, (int64_t)0);
+    std::fill(gang_dev_counts, gang_dev_counts + 4, (int64_t)0);
   }
   void clear_device() {
     fill_device(0, nullptr, false, nullptr, false, nullptr, false, nullptr, false);
@@ -108,7 +111,7 @@ struct CallRecords {
     devs.append(seg.devs, n, len, 0), cpusets.append(seg.cpusets, n, len, 0);
     vfs.append(seg.vfs, n, len, -1), numas.append(seg.numas, n, len, 0);
     gang_status.append(seg.gang_status, n, len, 0), gang_tried.append(seg.gang_tried, n, len, -1);
-    for (int i = 0; i < 4; i++) gang_counts[i] += seg.gang_counts[i];
+    for (int i = 0; i < 4; i++) gang_counts[i] += seg.gang_counts[i], gang_dev_counts[i] += seg.gang_dev_counts[i];
     n += len;
   }
   // the call's pods: chosen node, uid, whether the ElasticQuota Reserve ran; `resv` keeps what the call assumed

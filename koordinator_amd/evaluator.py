@@ -642,6 +642,23 @@ class Evaluator:
         self._check(self.lib.ke_debug_gangs(self.h, abi.ptr(out)))
         return {"runs": int(out[0]), "rolled_back": int(out[1]), "inverse_reserves": int(out[2]), "cuts": int(out[3])}
 
+    def devices_check(self):
+        """ke_debug_devices_check: nodes whose DeviceShare words on the device differ from the host's derivation."""
+        n = abi.i64()
+        self._check(self.lib.ke_debug_devices_check(self.h, C.byref(n)))
+        return n.value
+
+    def set_gang_devices(self, on):
+        """ke_set_gang_devices: with `on`, a member of a gang run may be a DeviceShare pod (off by default)."""
+        self._check(self.lib.ke_set_gang_devices(self.h, 1 if on else 0))
+
+    def debug_gang_devices(self):
+        """ke_debug_gang_devices of the last call: DeviceShare inverses, cuts inside an open run, slots adopted for
+        members an earlier launch placed, launches that went on from a restored run state."""
+        out = np.zeros(4, np.int64)
+        self._check(self.lib.ke_debug_gang_devices(self.h, abi.ptr(out)))
+        return {"device_inverses": int(out[0]), "cuts_in_run": int(out[1]), "adopted": int(out[2]), "restored": int(out[3])}
+
     def schedule(self, pods, now_ns, matches=None, node_sets=None, node_scores=None, spread_groups=None,
                  spread_domains=None, spread_terms=None, spread_domain_terms=None, gangs=None):
         """ke_schedule; `matches` (optional): per pod the reservation indices it matches (KE_RSV_MATCHED pods);
